@@ -12,9 +12,14 @@ Launch: `python bench.py` (1 GPU), `python bench.py --gpus N` (re-executes itsel
 no collective inside the loop, ONE all_gather of the outputs at the end of the run, outside the timed region and reported as
 gather_ms; --gpus must equal WORLD_SIZE).
 
-Instrumentation: inside the timed region HIP events bracket only the dominant kernel (`roofline`), on every other step; the per-class
-attribution (`conv3x3`, `roofline_hbm`, `other_matrix_kernels`, `operator_update`) is measured in two fully instrumented steps AFTER the
-timed region (`attribution_pass`) -- with ~430 event pairs per step in the timed region the step was 3 ms (2.8 %) slower.
+A plain run sets up, warms up, times --steps steps, writes the last timed step's outputs if --dump-outputs DIR is given and prints the
+line (metric / value / unit / ms_per_step / dtype / config, cold start, the multi-rank fields).  Everything else the benchmark measures
+is behind --full: the roofline and attribution figures, the measured peaks, the concurrent sub-batch region, the BASELINE.md section 3
+legs, the full run, the one-rank RCCL bring-up and the CPU baseline.
+
+Instrumentation (--full only): inside the timed region HIP events bracket only the dominant kernel (`roofline`), on every other step; the
+per-class attribution (`conv3x3`, `roofline_hbm`, `other_matrix_kernels`, `operator_update`) is measured in two fully instrumented steps
+AFTER the timed region (`attribution_pass`) -- with ~430 event pairs per step in the timed region the step was 3 ms (2.8 %) slower.
 """
 import argparse
 import ctypes as C
@@ -372,6 +377,28 @@ def conv_source_stamp():
     return h.hexdigest()[:12]
 
 
+DUMP_BYTES = 32 * 2 ** 20        # per array: two arrays stay within 64 MB
+
+
+def dump_outputs(path, arrays, dist, world, rank, coll_dev):
+    """--dump-outputs: every rank's rows (all_gather when ranks exist), written by rank 0 as float32 .npy.  An array above DUMP_BYTES is
+    replaced by a fixed sample of its flattened elements (seeded indices, ascending), the same for every run of the same arguments."""
+    for name, t in arrays.items():
+        t = t.detach().float().contiguous()
+        if dist is not None:
+            parts = [torch.empty_like(t, device=coll_dev) for _ in range(world)]
+            dist.all_gather(parts, t.to(coll_dev))
+            t = torch.cat(parts)
+        if rank != 0:
+            continue
+        v = t.cpu().numpy()
+        k = DUMP_BYTES // 4
+        if v.size > k:
+            v = v.reshape(-1)[np.sort(np.random.default_rng(0).choice(v.size, k, replace=False))]
+        os.makedirs(path, exist_ok=True)
+        np.save(os.path.join(path, name + ".npy"), v.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -400,6 +427,10 @@ def main():
                     "end-of-run gather through it: exercises communicator set-up and the collective on a 1-GPU box")
     ap.add_argument("--legs", default="auto", help="extra untimed-from-`value` legs (BASELINE.md section 3): comma list of informed,informed_b1,blind_b1,"
                     "forward_only,longform,full_run,shipped,gemm_modes,realclip or 'all' / 'none'; auto = all at N=1 with the default workload, full_run only otherwise")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: roofline / attribution / peaks, the concurrent region "
+                    "(--also-concurrent), the legs (--legs), the one-rank RCCL bring-up and the CPU baseline.  Off: none of them runs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed region write what its last step returned (x, x_den of every "
+                    "utterance, all ranks) as DIR/<name>.npy, float32; an array above 32 MB becomes a fixed seeded sample of its elements")
     a = ap.parse_args()
     if a.cpu_baseline_only:
         print(json.dumps(cpu_baseline(a.length, a.cpu_baseline_only, a.cpu_reps, a.cpu_utt, a.cpu_mode)))
@@ -535,7 +566,7 @@ def main():
     # so every layer shape is sampled equally --; the per-class attribution (convolution passes, GroupNorm groups, other GEMMs, operator update)
     # comes from a separate, untimed pass of ATTR_STEPS fully instrumented steps right after.
     log("timed region")
-    dom_level = int(os.environ.get("BUDDY_BENCH_PROF", "1"))
+    dom_level = int(os.environ.get("BUDDY_BENCH_PROF", "1")) if a.full else 0       # a plain run records no events at all
     t0 = time.perf_counter()
     sampled_steps = 0
     for i in range(a.steps):
@@ -547,8 +578,9 @@ def main():
     elapsed = time.perf_counter() - t0
     lib.buddy_prof_enable(0)
     log(f"timed region done: {elapsed:.3f} s")
-    dom_ms = (C.c_double * 3)(); dom_fl, dom_bi, dom_bo, dom_bg, dom_n = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_longlong()
-    _lib.check(lib.buddy_prof_collect_wino4(dom_ms, C.byref(dom_fl), C.byref(dom_bi), C.byref(dom_bo), C.byref(dom_bg), C.byref(dom_n)))
+    if a.dump_outputs:               # before anything else steps these runners
+        dump_outputs(a.dump_outputs, {"x": torch.cat([r.x for r in runs]), "x_den": torch.cat([r.x_den for r in runs])}, dist, world, rank, coll_dev)
+        log(f"outputs of the last timed step written to {a.dump_outputs}")
     el = torch.tensor([elapsed], device=coll_dev, dtype=torch.float64)
     per_rank_ms = [elapsed / a.steps * 1e3]
     if dist is not None:
@@ -560,29 +592,32 @@ def main():
 
     weight_store_main = net0[0].weight_bytes()       # before the legs: the other arithmetics' legs add their own operand forms to the shared store
     ATTR_STEPS = 2
-    log(f"attribution pass: {ATTR_STEPS} fully instrumented steps (untimed)")
-    lib.buddy_prof_enable(2)
-    for r in runs:
-        r.op_events = []
-    t0 = time.perf_counter()
-    for _ in range(ATTR_STEPS):
-        run.step()
-    barrier()
-    attr_elapsed = time.perf_counter() - t0
-    lib.buddy_prof_enable(0)
-    op_ms = sum(e0.elapsed_time(e1) for r in runs for e0, e1 in r.op_events)
-    for r in runs:
-        r.op_events = None
-    ms = (C.c_double * 2)(); fl = (C.c_double * 2)(); ln = (C.c_longlong * 2)(); by = (C.c_double * 2)(); xf = (C.c_double * 2)()
-    _lib.check(lib.buddy_prof_collect(ms, fl, ln, by, xf))
-    w4_ms = (C.c_double * 3)(); w4_fl, w4_bi, w4_bo, w4_bg, w4_n = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_longlong()
-    _lib.check(lib.buddy_prof_collect_wino4(w4_ms, C.byref(w4_fl), C.byref(w4_bi), C.byref(w4_bo), C.byref(w4_bg), C.byref(w4_n)))
-    hb_ms, hb_by, hb_n = C.c_double(), C.c_double(), C.c_longlong()
-    _lib.check(lib.buddy_prof_collect_hbm(C.byref(hb_ms), C.byref(hb_by), C.byref(hb_n)))
+    if a.full:
+        dom_ms = (C.c_double * 3)(); dom_fl, dom_bi, dom_bo, dom_bg, dom_n = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_longlong()
+        _lib.check(lib.buddy_prof_collect_wino4(dom_ms, C.byref(dom_fl), C.byref(dom_bi), C.byref(dom_bo), C.byref(dom_bg), C.byref(dom_n)))
+        log(f"attribution pass: {ATTR_STEPS} fully instrumented steps (untimed)")
+        lib.buddy_prof_enable(2)
+        for r in runs:
+            r.op_events = []
+        t0 = time.perf_counter()
+        for _ in range(ATTR_STEPS):
+            run.step()
+        barrier()
+        attr_elapsed = time.perf_counter() - t0
+        lib.buddy_prof_enable(0)
+        op_ms = sum(e0.elapsed_time(e1) for r in runs for e0, e1 in r.op_events)
+        for r in runs:
+            r.op_events = None
+        ms = (C.c_double * 2)(); fl = (C.c_double * 2)(); ln = (C.c_longlong * 2)(); by = (C.c_double * 2)(); xf = (C.c_double * 2)()
+        _lib.check(lib.buddy_prof_collect(ms, fl, ln, by, xf))
+        w4_ms = (C.c_double * 3)(); w4_fl, w4_bi, w4_bo, w4_bg, w4_n = C.c_double(), C.c_double(), C.c_double(), C.c_double(), C.c_longlong()
+        _lib.check(lib.buddy_prof_collect_wino4(w4_ms, C.byref(w4_fl), C.byref(w4_bi), C.byref(w4_bo), C.byref(w4_bg), C.byref(w4_n)))
+        hb_ms, hb_by, hb_n = C.c_double(), C.c_double(), C.c_longlong()
+        _lib.check(lib.buddy_prof_collect_hbm(C.byref(hb_ms), C.byref(hb_by), C.byref(hb_n)))
 
     # second region: the same workload as concurrent sub-batches (identical per-utterance results, better occupancy; not used for the rooflines)
     conc = None
-    S2 = a.also_concurrent
+    S2 = a.also_concurrent if a.full else 0
     if S2 > 1 and S == 1 and B % S2 == 0:
         log(f"second region: {S2} concurrent sub-batches")
         runs2, streams2 = make_runners(S2)
@@ -609,7 +644,9 @@ def main():
     default_workload = (B == 8 and a.length == 64000)
     ALL_LEGS = {"informed", "informed_b1", "blind_b1", "forward_only", "longform", "full_run", "shipped", "gemm_modes", "realclip"}
     gemm_mode_now = {0: "fp32", 1: "bf16x3", 2: "f16x2"}[int(net0[0].get_option("gemm"))]
-    if a.legs == "auto":
+    if not a.full:
+        want = set()
+    elif a.legs == "auto":
         want = set(ALL_LEGS) if (world == 1 and default_workload) else {"full_run"}
     elif a.legs == "all":
         want = set(ALL_LEGS)
@@ -772,7 +809,7 @@ def main():
         rows = bdist.gather_ragged([out[i] for i in range(out.shape[0])], world * out.shape[0], rank, world, device=device)
         assert len(rows) == world * out.shape[0] and all(torch.equal(rows[rank + world * i].to(out.device), out[i]) for i in range(out.shape[0]))
     rccl_selftest = None
-    if dist is None and world == 1 and not a.no_rccl_selftest:
+    if a.full and dist is None and world == 1 and not a.no_rccl_selftest:
         # N=1 default run: bring RCCL up once anyway (one rank, this GPU) after everything that is timed, so that communicator set-up, the
         # IPC-mode setting and the nccl side of buddy_amd/dist.py have run on this box before an 8-GPU node appears.  Failure is reported, not fatal.
         rccl_selftest = {"ok": False}
@@ -804,29 +841,7 @@ def main():
     if rank == 0:
         n_utt_steps = world * B * a.steps
         step_s = elapsed / a.steps                                                           # wall time of one step in the timed region
-        attr_step_s = attr_elapsed / ATTR_STEPS                                              # ... in the fully instrumented pass (slower: event bubbles)
-        n36 = max(1, int(dom_n.value))
-        gemm_tf = dom_fl.value / (dom_ms[1] * 1e-3) / 1e12 if dom_ms[1] > 0 else 0.0         # executed FLOPs of the 36 batched GEMMs / their time
-        gemm_ms_per_step = dom_ms[1] / max(1, sampled_steps)
-        conv_alg_tf = fl[0] / (ms[0] * 1e-3) / 1e12 if ms[0] > 0 else 0.0                    # direct-convolution FLOPs / three-launch group time
-        exec_step_tf = (xf[0] + xf[1]) / ATTR_STEPS / step_s / 1e12                          # every matrix-core FLOP executed per step / wall time of a step
-        a36 = max(1, int(w4_n.value))
-        # HBM bytes of the dominant kernel: separate rocprofv3 --pmc passes of this same command (counters cannot be read in-process),
-        # summarised by tools/pmc_summary.py; quoted only if measured on the kernels that are running now (source stamp)
         gemm_mode = {0: "fp32", 1: "bf16x3", 2: "f16x2"}[int(net0[0].get_option("gemm"))]      # what the handle ran with (--gemm, BUDDY_GEMM, or the library default)
-        traffic, traffic_group, traffic_src = None, None, "no PMC summary for the current kernel sources (tools/pmc_summary.py writes profiles/conv_traffic_pmc.json)"
-        tp = os.path.join(ROOT, "profiles", "conv_traffic_pmc.json")
-        stamp = conv_source_stamp()
-        if os.path.exists(tp) and B == 8 and a.length == 64000:
-            pj = json.load(open(tp))
-            if pj.get("source_stamp") == stamp:
-                k36 = [v for k, v in pj["per_kernel_bytes_per_convolution"].items() if "GEMM" in k or "36>" in k][0]
-                traffic = k36["fetch"] + k36["write"]
-                traffic_group = pj.get("hbm_bytes_per_launch")
-                traffic_src = f"profiles/conv_traffic_pmc.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, FETCH x2 gfx950 correction; source stamp {stamp})"
-            else:
-                traffic_src = f"profiles/conv_traffic_pmc.json is stale (stamp {pj.get('source_stamp')} != {stamp} of the current igemm.hip / wino4.hip): not quoted"
-        peaks = measure_peaks(lib, device)
         res = {
             "metric": f"diffusion steps/sec ({a.length / 16000:g} s@16 kHz utterance, blind Euler-Heun DPS, order 1, 10 operator updates/step)",
             "value": n_utt_steps / elapsed, "unit": "utterance-steps/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -853,80 +868,105 @@ def main():
             "gather_ms": gather_ms, "gather_first_call_ms": gather_first_ms, "gather_bytes_per_rank": int(out.numel() * 4),
             "gather_backend": (a.backend if dist is not None else None), "per_rank_ms_per_step": per_rank_ms,
             "per_rank_placement": placements if world > 1 else None, "rccl_env": rccl_env,
-            # dominant kernel: the batched Winograd-domain GEMMs of the 3x3 convolutions.  bf16x3 (default): every fp32 multiply-add is SIX bf16 MFMA
-            # multiply-adds -> achieved = 6 x the fp32-equivalent rate, against the bf16 matrix peak; the fp32-equivalent rate against the fp32 matrix
-            # peak is beside it (the kernel replaces v_mfma_f32_32x32x2_f32 at equal accuracy; --gemm fp32 is the reference run)
-            "roofline": (f16x2_roofline(gemm_tf, dom_bg.value, dom_ms[1], peaks) if gemm_mode == "f16x2" else
-                         {"bound": "mfma", "kernel": "wgemm_bf16x3_kernel -- the batched GEMMs M[pos] = V[pos] U[pos]^T of the three-pass Winograd 3x3 convolutions "
-                                                     "(64 positions, F(6x6,3x3), on the large layers; 36, F(4x4,3x3), on the small ones; 94 % of the network's "
-                                                     "algorithmic FLOPs) in bf16x3 arithmetic: exact three-way bf16 split of both fp32 operands, six "
-                                                     "v_mfma_f32_32x32x16_bf16 products per 16 k, fp32 accumulate",
-                          "achieved": 6.0 * gemm_tf, "peak": PEAK_BF16_MFMA, "unit": "TFLOP/s", "frac": 6.0 * gemm_tf / PEAK_BF16_MFMA,
-                          "achieved_note": "EXECUTED bf16 MFMA FLOPs per launch (6 x 2 * positions * tiles * Cin * Cout) / average launch duration, HIP events on the "
-                                           "launch stream inside the timed region (every launch of every other step)",
-                          "peak_measured_on_box": peaks.get("bf16_mfma_tflops"),
-                          "frac_of_measured_peak": (6.0 * gemm_tf / peaks["bf16_mfma_tflops"]) if peaks.get("bf16_mfma_tflops") else None,
-                          "peak_measured_note": "a pure v_mfma_f32_32x32x16_bf16 loop on random operand bits (no memory traffic) on this box: the chip clocks "
-                                                "to its power budget, so this -- not 2.5 PFLOP/s -- is what the matrix pipe sustains here",
-                          "fp32_equivalent_tflops": gemm_tf, "frac_of_fp32_matrix_peak": gemm_tf / PEAK_FP32_MFMA,
-                          "fp32_equivalent_note": "the same launches counted as the fp32 multiply-adds they replace (2 * positions * tiles * Cin * Cout) against the "
-                                                  "157.3 TFLOP/s fp32 matrix peak: what an exact-fp32 GEMM could reach at most on v_mfma_f32_32x32x2_f32",
-                          "hbm_side": {"achieved_GBps": dom_bg.value / (dom_ms[1] * 1e-3) / 1e9 if dom_ms[1] > 0 else 0.0, "peak_GBps": PEAK_HBM_GBS,
-                                       "frac": (dom_bg.value / (dom_ms[1] * 1e-3) / 1e9 / PEAK_HBM_GBS) if dom_ms[1] > 0 else 0.0,
-                                       "note": "algorithmic bytes (V read once, M written once, weights once) / time: the K = 128 layers of level 0 sit nearer this roofline "
-                                               "than the matrix one (192 bf16 FLOP per byte)"}}
-                         if gemm_mode == "bf16x3" else
-                         {"bound": "mfma", "kernel": "igemm_kernel<1,false,false,2,2,36> -- the batched GEMMs M[pos] = V[pos] U[pos]^T of the three-pass "
-                                                     "Winograd 3x3 convolutions on v_mfma_f32_32x32x2_f32 (--gemm fp32: the reference run)",
-                          "achieved": gemm_tf, "peak": PEAK_FP32_MFMA, "unit": "TFLOP/s", "frac": gemm_tf / PEAK_FP32_MFMA,
-                          "achieved_note": "EXECUTED FLOPs per launch (2 * positions * tiles * Cin * Cout) / average launch duration, HIP events on the launch stream inside "
-                                           "the timed region (every launch of every other step: an event pair costs a ~7 us dispatch bubble); <= 1 by construction",
-                          "peak_measured_on_box": peaks.get("fp32_mfma_tflops"),
-                          "frac_of_measured_peak": (gemm_tf / peaks["fp32_mfma_tflops"]) if peaks.get("fp32_mfma_tflops") else None}),
-            # the whole 3x3 convolution (three launches) and the whole step, for context
-            "conv3x3": {"algorithmic_tflops": conv_alg_tf, "algorithmic_speedup": (fl[0] / xf[0]) if xf[0] > 0 else None,
-                        "note": "direct-convolution FLOPs (2*M*N*9*Cin) / time of the three-launch group; the Winograd forms execute 64/(36*9) "
-                                "(F(6x6,3x3), plus tile overhang) or 1/4 (F(4x4,3x3)) of them -- algorithmic_speedup = direct / executed FLOPs over all "
-                                "convolutions -- so this is NOT a roofline fraction: the matrix-pipe utilisation is roofline.frac",
-                        "avg_conv_ms": ms[0] / max(1, ln[0]), "convolutions": int(ln[0]), "share_of_step": ms[0] * 1e-3 / attr_elapsed,
-                        "transform_passes": {"input_GBps": w4_bi.value / (w4_ms[0] * 1e-3) / 1e9 if w4_ms[0] > 0 else 0.0,
-                                             "output_GBps": w4_bo.value / (w4_ms[2] * 1e-3) / 1e9 if w4_ms[2] > 0 else 0.0,
-                                             "peak_GBps": PEAK_HBM_GBS, "copy_GBps_on_this_box": peaks.get("hbm_copy_GBps"), "copy_GBps_guide": GUIDE_COPY_GBS,
-                                             "share_of_step": (w4_ms[0] + w4_ms[2]) * 1e-3 / attr_elapsed,
-                                             "note": "HBM-bound: input read once + 64/36 (F(6x6,3x3)) or 36/16 (F(4x4,3x3)) transformed values written; the same read + output (and residual) once"},
-                        "fused_form_bytes_per_conv": by[0] / max(1, ln[0]),
-                        "three_pass_bytes_per_conv": (w4_bi.value + w4_bg.value + w4_bo.value) / a36},
-            "step_executed": {"tflops": exec_step_tf, "frac": exec_step_tf / PEAK_FP32_MFMA,
-                              "note": "all matrix-core FLOPs executed per step (Winograd-domain GEMMs, 1x1 / attention / DFT GEMMs; counted in the attribution "
-                                      "pass) / wall time of a step of the timed region / fp32 matrix peak"},
-            "other_matrix_kernels": {"tflops": fl[1] / (ms[1] * 1e-3) / 1e12 if ms[1] > 0 else 0.0, "ms_per_step": ms[1] / ATTR_STEPS, "launches": int(ln[1])},
-            # second roofline SURVEY 8(d) asks for: the HBM-bound GroupNorm(+SiLU, +2x resample) kernels and their backward
-            "roofline_hbm": {"bound": "hbm", "kernel": "GroupNorm statistics / apply(+SiLU,+resample) / backward (chan_reduce, gn_apply, gn_bwd_apply)",
-                             "achieved": hb_by.value / (hb_ms.value * 1e-3) / 1e9 if hb_ms.value > 0 else 0.0, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                             "frac": (hb_by.value / (hb_ms.value * 1e-3) / 1e9 / PEAK_HBM_GBS) if hb_ms.value > 0 else 0.0,
-                             "frac_of_measured_copy": (hb_by.value / (hb_ms.value * 1e-3) / 1e9 / peaks["hbm_copy_GBps"]) if (hb_ms.value > 0 and peaks.get("hbm_copy_GBps")) else None,
-                             "frac_of_guide_copy": (hb_by.value / (hb_ms.value * 1e-3) / 1e9 / GUIDE_COPY_GBS) if hb_ms.value > 0 else None,
-                             "peak_measured_on_box": {k: v for k, v in peaks.items() if k.startswith("hbm_")},
-                             "launch_groups": int(hb_n.value), "kernel_time_share_of_step": hb_ms.value * 1e-3 / attr_elapsed,
-                             "note": "algorithmic bytes (every pass reads its inputs and writes its output once) / HIP-event time"},
-            "operator_update": {"ms_per_step": op_ms / ATTR_STEPS, "share_of_step": op_ms * 1e-3 / attr_elapsed,
-                                "what": "optimize_op: 10 x (design filter, min-phase projection, subband FIR, loss, analytic backward, Adam, clamps) per step, "
-                                        "HIP events on the launch stream (rank 0)"},
-            "attribution_pass": {"steps": ATTR_STEPS, "ms_per_step": attr_step_s * 1e3,
-                                 "note": "conv3x3 / step_executed FLOP counts / other_matrix_kernels / roofline_hbm / operator_update come from these fully instrumented "
-                                         "steps run right after the timed region (shares are of THIS pass's time); value, ms_per_step and roofline from the timed region"},
-            "peaks": {"nominal": {"fp32_mfma_tflops": PEAK_FP32_MFMA, "bf16_mfma_tflops": PEAK_BF16_MFMA, "hbm_GBps": PEAK_HBM_GBS}, "measured_on_this_box": peaks},
         }
-        res["roofline"].update({"avg_launch_ms": dom_ms[1] / n36, "launches": n36, "sampled_steps": sampled_steps, "share_of_step": gemm_ms_per_step * 1e-3 / step_s,
-                                "flops_per_launch_fp32_equivalent": dom_fl.value / n36, "algorithmic_bytes_per_launch": dom_bg.value / n36,
-                                "traffic": traffic, "traffic_source": traffic_src,
-                                # the whole three-launch convolution against the bytes a fused form would move: what the three-pass structure costs
-                                "traffic_conv_group": traffic_group, "fused_form_bytes_per_conv": by[0] / max(1, ln[0]),
-                                "traffic_conv_group_over_fused_form": (traffic_group / (by[0] / max(1, ln[0]))) if (traffic_group and ln[0]) else None})
+        if a.full:
+            attr_step_s = attr_elapsed / ATTR_STEPS                                              # ... in the fully instrumented pass (slower: event bubbles)
+            n36 = max(1, int(dom_n.value))
+            gemm_tf = dom_fl.value / (dom_ms[1] * 1e-3) / 1e12 if dom_ms[1] > 0 else 0.0         # executed FLOPs of the 36 batched GEMMs / their time
+            gemm_ms_per_step = dom_ms[1] / max(1, sampled_steps)
+            conv_alg_tf = fl[0] / (ms[0] * 1e-3) / 1e12 if ms[0] > 0 else 0.0                    # direct-convolution FLOPs / three-launch group time
+            exec_step_tf = (xf[0] + xf[1]) / ATTR_STEPS / step_s / 1e12                          # every matrix-core FLOP executed per step / wall time of a step
+            a36 = max(1, int(w4_n.value))
+            # HBM bytes of the dominant kernel: separate rocprofv3 --pmc passes of this same command (counters cannot be read in-process),
+            # summarised by tools/pmc_summary.py; quoted only if measured on the kernels that are running now (source stamp)
+            traffic, traffic_group, traffic_src = None, None, "no PMC summary for the current kernel sources (tools/pmc_summary.py writes profiles/conv_traffic_pmc.json)"
+            tp = os.path.join(ROOT, "profiles", "conv_traffic_pmc.json")
+            stamp = conv_source_stamp()
+            if os.path.exists(tp) and B == 8 and a.length == 64000:
+                pj = json.load(open(tp))
+                if pj.get("source_stamp") == stamp:
+                    k36 = [v for k, v in pj["per_kernel_bytes_per_convolution"].items() if "GEMM" in k or "36>" in k][0]
+                    traffic = k36["fetch"] + k36["write"]
+                    traffic_group = pj.get("hbm_bytes_per_launch")
+                    traffic_src = f"profiles/conv_traffic_pmc.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes, FETCH x2 gfx950 correction; source stamp {stamp})"
+                else:
+                    traffic_src = f"profiles/conv_traffic_pmc.json is stale (stamp {pj.get('source_stamp')} != {stamp} of the current igemm.hip / wino4.hip): not quoted"
+            peaks = measure_peaks(lib, device)
+            res.update({
+                # dominant kernel: the batched Winograd-domain GEMMs of the 3x3 convolutions.  bf16x3 (default): every fp32 multiply-add is SIX bf16 MFMA
+                # multiply-adds -> achieved = 6 x the fp32-equivalent rate, against the bf16 matrix peak; the fp32-equivalent rate against the fp32 matrix
+                # peak is beside it (the kernel replaces v_mfma_f32_32x32x2_f32 at equal accuracy; --gemm fp32 is the reference run)
+                "roofline": (f16x2_roofline(gemm_tf, dom_bg.value, dom_ms[1], peaks) if gemm_mode == "f16x2" else
+                             {"bound": "mfma", "kernel": "wgemm_bf16x3_kernel -- the batched GEMMs M[pos] = V[pos] U[pos]^T of the three-pass Winograd 3x3 convolutions "
+                                                         "(64 positions, F(6x6,3x3), on the large layers; 36, F(4x4,3x3), on the small ones; 94 % of the network's "
+                                                         "algorithmic FLOPs) in bf16x3 arithmetic: exact three-way bf16 split of both fp32 operands, six "
+                                                         "v_mfma_f32_32x32x16_bf16 products per 16 k, fp32 accumulate",
+                              "achieved": 6.0 * gemm_tf, "peak": PEAK_BF16_MFMA, "unit": "TFLOP/s", "frac": 6.0 * gemm_tf / PEAK_BF16_MFMA,
+                              "achieved_note": "EXECUTED bf16 MFMA FLOPs per launch (6 x 2 * positions * tiles * Cin * Cout) / average launch duration, HIP events on the "
+                                               "launch stream inside the timed region (every launch of every other step)",
+                              "peak_measured_on_box": peaks.get("bf16_mfma_tflops"),
+                              "frac_of_measured_peak": (6.0 * gemm_tf / peaks["bf16_mfma_tflops"]) if peaks.get("bf16_mfma_tflops") else None,
+                              "peak_measured_note": "a pure v_mfma_f32_32x32x16_bf16 loop on random operand bits (no memory traffic) on this box: the chip clocks "
+                                                    "to its power budget, so this -- not 2.5 PFLOP/s -- is what the matrix pipe sustains here",
+                              "fp32_equivalent_tflops": gemm_tf, "frac_of_fp32_matrix_peak": gemm_tf / PEAK_FP32_MFMA,
+                              "fp32_equivalent_note": "the same launches counted as the fp32 multiply-adds they replace (2 * positions * tiles * Cin * Cout) against the "
+                                                      "157.3 TFLOP/s fp32 matrix peak: what an exact-fp32 GEMM could reach at most on v_mfma_f32_32x32x2_f32",
+                              "hbm_side": {"achieved_GBps": dom_bg.value / (dom_ms[1] * 1e-3) / 1e9 if dom_ms[1] > 0 else 0.0, "peak_GBps": PEAK_HBM_GBS,
+                                           "frac": (dom_bg.value / (dom_ms[1] * 1e-3) / 1e9 / PEAK_HBM_GBS) if dom_ms[1] > 0 else 0.0,
+                                           "note": "algorithmic bytes (V read once, M written once, weights once) / time: the K = 128 layers of level 0 sit nearer this roofline "
+                                                   "than the matrix one (192 bf16 FLOP per byte)"}}
+                             if gemm_mode == "bf16x3" else
+                             {"bound": "mfma", "kernel": "igemm_kernel<1,false,false,2,2,36> -- the batched GEMMs M[pos] = V[pos] U[pos]^T of the three-pass "
+                                                         "Winograd 3x3 convolutions on v_mfma_f32_32x32x2_f32 (--gemm fp32: the reference run)",
+                              "achieved": gemm_tf, "peak": PEAK_FP32_MFMA, "unit": "TFLOP/s", "frac": gemm_tf / PEAK_FP32_MFMA,
+                              "achieved_note": "EXECUTED FLOPs per launch (2 * positions * tiles * Cin * Cout) / average launch duration, HIP events on the launch stream inside "
+                                               "the timed region (every launch of every other step: an event pair costs a ~7 us dispatch bubble); <= 1 by construction",
+                              "peak_measured_on_box": peaks.get("fp32_mfma_tflops"),
+                              "frac_of_measured_peak": (gemm_tf / peaks["fp32_mfma_tflops"]) if peaks.get("fp32_mfma_tflops") else None}),
+                # the whole 3x3 convolution (three launches) and the whole step, for context
+                "conv3x3": {"algorithmic_tflops": conv_alg_tf, "algorithmic_speedup": (fl[0] / xf[0]) if xf[0] > 0 else None,
+                            "note": "direct-convolution FLOPs (2*M*N*9*Cin) / time of the three-launch group; the Winograd forms execute 64/(36*9) "
+                                    "(F(6x6,3x3), plus tile overhang) or 1/4 (F(4x4,3x3)) of them -- algorithmic_speedup = direct / executed FLOPs over all "
+                                    "convolutions -- so this is NOT a roofline fraction: the matrix-pipe utilisation is roofline.frac",
+                            "avg_conv_ms": ms[0] / max(1, ln[0]), "convolutions": int(ln[0]), "share_of_step": ms[0] * 1e-3 / attr_elapsed,
+                            "transform_passes": {"input_GBps": w4_bi.value / (w4_ms[0] * 1e-3) / 1e9 if w4_ms[0] > 0 else 0.0,
+                                                 "output_GBps": w4_bo.value / (w4_ms[2] * 1e-3) / 1e9 if w4_ms[2] > 0 else 0.0,
+                                                 "peak_GBps": PEAK_HBM_GBS, "copy_GBps_on_this_box": peaks.get("hbm_copy_GBps"), "copy_GBps_guide": GUIDE_COPY_GBS,
+                                                 "share_of_step": (w4_ms[0] + w4_ms[2]) * 1e-3 / attr_elapsed,
+                                                 "note": "HBM-bound: input read once + 64/36 (F(6x6,3x3)) or 36/16 (F(4x4,3x3)) transformed values written; the same read + output (and residual) once"},
+                            "fused_form_bytes_per_conv": by[0] / max(1, ln[0]),
+                            "three_pass_bytes_per_conv": (w4_bi.value + w4_bg.value + w4_bo.value) / a36},
+                "step_executed": {"tflops": exec_step_tf, "frac": exec_step_tf / PEAK_FP32_MFMA,
+                                  "note": "all matrix-core FLOPs executed per step (Winograd-domain GEMMs, 1x1 / attention / DFT GEMMs; counted in the attribution "
+                                          "pass) / wall time of a step of the timed region / fp32 matrix peak"},
+                "other_matrix_kernels": {"tflops": fl[1] / (ms[1] * 1e-3) / 1e12 if ms[1] > 0 else 0.0, "ms_per_step": ms[1] / ATTR_STEPS, "launches": int(ln[1])},
+                # second roofline SURVEY 8(d) asks for: the HBM-bound GroupNorm(+SiLU, +2x resample) kernels and their backward
+                "roofline_hbm": {"bound": "hbm", "kernel": "GroupNorm statistics / apply(+SiLU,+resample) / backward (chan_reduce, gn_apply, gn_bwd_apply)",
+                                 "achieved": hb_by.value / (hb_ms.value * 1e-3) / 1e9 if hb_ms.value > 0 else 0.0, "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                                 "frac": (hb_by.value / (hb_ms.value * 1e-3) / 1e9 / PEAK_HBM_GBS) if hb_ms.value > 0 else 0.0,
+                                 "frac_of_measured_copy": (hb_by.value / (hb_ms.value * 1e-3) / 1e9 / peaks["hbm_copy_GBps"]) if (hb_ms.value > 0 and peaks.get("hbm_copy_GBps")) else None,
+                                 "frac_of_guide_copy": (hb_by.value / (hb_ms.value * 1e-3) / 1e9 / GUIDE_COPY_GBS) if hb_ms.value > 0 else None,
+                                 "peak_measured_on_box": {k: v for k, v in peaks.items() if k.startswith("hbm_")},
+                                 "launch_groups": int(hb_n.value), "kernel_time_share_of_step": hb_ms.value * 1e-3 / attr_elapsed,
+                                 "note": "algorithmic bytes (every pass reads its inputs and writes its output once) / HIP-event time"},
+                "operator_update": {"ms_per_step": op_ms / ATTR_STEPS, "share_of_step": op_ms * 1e-3 / attr_elapsed,
+                                    "what": "optimize_op: 10 x (design filter, min-phase projection, subband FIR, loss, analytic backward, Adam, clamps) per step, "
+                                            "HIP events on the launch stream (rank 0)"},
+                "attribution_pass": {"steps": ATTR_STEPS, "ms_per_step": attr_step_s * 1e3,
+                                     "note": "conv3x3 / step_executed FLOP counts / other_matrix_kernels / roofline_hbm / operator_update come from these fully instrumented "
+                                             "steps run right after the timed region (shares are of THIS pass's time); value, ms_per_step and roofline from the timed region"},
+                "peaks": {"nominal": {"fp32_mfma_tflops": PEAK_FP32_MFMA, "bf16_mfma_tflops": PEAK_BF16_MFMA, "hbm_GBps": PEAK_HBM_GBS}, "measured_on_this_box": peaks},
+            })
+            res["roofline"].update({"avg_launch_ms": dom_ms[1] / n36, "launches": n36, "sampled_steps": sampled_steps, "share_of_step": gemm_ms_per_step * 1e-3 / step_s,
+                                    "flops_per_launch_fp32_equivalent": dom_fl.value / n36, "algorithmic_bytes_per_launch": dom_bg.value / n36,
+                                    "traffic": traffic, "traffic_source": traffic_src,
+                                    # the whole three-launch convolution against the bytes a fused form would move: what the three-pass structure costs
+                                    "traffic_conv_group": traffic_group, "fused_form_bytes_per_conv": by[0] / max(1, ln[0]),
+                                    "traffic_conv_group_over_fused_form": (traffic_group / (by[0] / max(1, ln[0]))) if (traffic_group and ln[0]) else None})
         res["config"]["gemm"] = gemm_mode
         if conc is not None:
             res["concurrent_sub_batches"] = conc
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             log("cpu baseline (oracle on host cores)")
             res["cpu_baseline"] = run_cpu_baseline(a.length)
         C.CDLL(None).fflush(None)          # anything buffered by C stdio (the RCCL banner) leaves through stderr before the line is written

@@ -151,7 +151,7 @@ def test_longform_chunked_blind_keeps_the_level_profile():
 
 
 def test_bench_line_contract():
-    """The ONE JSON line `python bench.py` prints (driver contract): metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better /
+    """The ONE JSON line `python bench.py --full` prints (driver contract): metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better /
     scaling / vs_baseline / dtype / data / config.workload naming BASELINE.json configs[1], and the `roofline` object of the dominant kernel with
     bound / achieved / peak / unit / frac / traffic; value consistent with ms_per_step."""
     import json
@@ -159,7 +159,7 @@ def test_bench_line_contract():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--also-concurrent", "0", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--also-concurrent", "0", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -216,6 +216,34 @@ def test_bench_line_contract():
     assert fr["T"] == 50 and fr["batch_per_gpu"] == 8 and 1.0 < fr["wall_s"] < 30.0 and abs(fr["utterance_steps_per_s"] - 400 / fr["wall_s"]) < 1e-6 * 400
     rs = j["rccl_selftest"]
     assert rs["ok"] is True and rs["backend"] == "nccl" and rs["init_ms"] > 0 and rs["gather_first_call_ms"] > 0, rs
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) does only what the headline needs: the same headline fields, --steps timed steps, no roofline / legs /
+    full run / RCCL bring-up / CPU baseline; --dump-outputs writes the last timed step's x and x_den of every utterance as float32 .npy."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    d = str(tmp_path / "out")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", d],
+                       capture_output=True, text=True, timeout=900, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config"):
+        assert k in j, k
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["unit"] == "utterance-steps/s" and "configs[1]" in j["config"]["workload"]
+    assert abs(j["value"] - 8 * 3 / (j["ms_per_step"] * 3e-3)) < 1e-6 * j["value"]
+    for k in ("roofline", "peaks", "attribution_pass", "concurrent_sub_batches", "cpu_baseline"):
+        assert k not in j, k
+    assert j["legs"] == {} and j["full_run"] is None and j["rccl_selftest"] is None
+    assert "attribution pass" not in r.stderr and "leg " not in r.stderr
+    for name in ("x", "x_den"):
+        v = np.load(os.path.join(d, name + ".npy"))
+        assert v.dtype == np.float32 and v.shape[0] == 8 and v.size == 8 * 64000 and np.isfinite(v).all() and np.abs(v).max() > 0, name
 
 
 def test_bench_force_dist_one_rank_rccl():

@@ -2,7 +2,7 @@
 # A/B of one environment switch on one box: alternating bench runs (main region only), ms/step of each.
 # usage: bash tools/ab_env.sh VAR A_VALUE B_VALUE [rounds] [extra bench flags]
 VAR=$1; A=$2; B=$3; R=${4:-2}; shift 4
-FLAGS="--steps 10 --warmup 3 --no-cpu-baseline --also-concurrent 0 --legs none --no-rccl-selftest $@"
+FLAGS="--full --steps 10 --warmup 3 --no-cpu-baseline --also-concurrent 0 --legs none --no-rccl-selftest $@"
 for i in $(seq $R); do
   for v in $A $B; do
     env $VAR=$v python bench.py $FLAGS 2>/dev/null | python -c "

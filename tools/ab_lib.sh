@@ -4,7 +4,7 @@
 cd $(dirname $0)/..
 for v in A B A B; do
   cp buddy_amd/libbuddy_hip_$v.so buddy_amd/libbuddy_hip.so
-  python bench.py --steps 10 --warmup 3 --legs none --no-cpu-baseline --also-concurrent 0 --no-rccl-selftest "$@" 2>/dev/null | python -c "
+  python bench.py --full --steps 10 --warmup 3 --legs none --no-cpu-baseline --also-concurrent 0 --no-rccl-selftest "$@" 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.readline())
 tp=j['conv3x3']['transform_passes']

@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU-busy share of the B = 1 blind step: rocprofv3 kernel stats of `bench.py --batch 1` against its own ms_per_step.  usage: tools/b1_busy.sh <tag>
 TAG=${1:-b1}; R=$(pwd); OUT=$R/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o $TAG -- python $R/bench.py --batch 1 --steps 10 --warmup 2 --no-cpu-baseline --also-concurrent 0 --legs none --no-rccl-selftest > $OUT/${TAG}_b1.json 2> /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o $TAG -- python $R/bench.py --full --batch 1 --steps 10 --warmup 2 --no-cpu-baseline --also-concurrent 0 --legs none --no-rccl-selftest > $OUT/${TAG}_b1.json 2> /dev/null
 cd $R
 find $OUT/prof_$TAG -name "*kernel_stats.csv" -exec cp {} $OUT/${TAG}_b1_kernel_stats.csv \;
 python - <<PY

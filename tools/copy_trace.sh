@@ -1,7 +1,7 @@
 #!/bin/bash
 # who issues the device-to-device copies of a step?  kernel trace of a short bench run; every __amd_rocclr_copyBuffer with its duration and neighbours.
 TAG=${1:-cp}; R=$(pwd); OUT=$R/gpurun_out; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT/tr_$TAG -o t -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --also-concurrent 0 --legs none --no-rccl-selftest > /dev/null 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT/tr_$TAG -o t -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --also-concurrent 0 --legs none --no-rccl-selftest > /dev/null 2>&1
 cd $R
 python - <<PY
 import csv, glob, collections

@@ -4,7 +4,7 @@
 KV=$1; PAT=$2; shift 2
 R=$(pwd); OUT=/tmp/prof_env_$$; export TMPDIR=/tmp
 cd /tmp
-env $KV rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o p -- python $R/bench.py --steps 4 --warmup 2 --no-cpu-baseline --also-concurrent 0 --legs none --no-rccl-selftest $@ > /dev/null 2>&1
+env $KV rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o p -- python $R/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --also-concurrent 0 --legs none --no-rccl-selftest $@ > /dev/null 2>&1
 cd $R
 python - "$(find $OUT -name '*kernel_stats.csv')" "$PAT" <<'PY'
 import csv, re, sys

@@ -2,6 +2,7 @@
 # per-(kernel, grid) table of EVERY kernel of one bench run (kernel trace), written to gpurun_out/<tag>_by_grid.txt.
 # usage: [BENCH_FLAGS="--batch 1"] tools/trace_all.sh <tag>
 TAG=${1:-trace}
+BENCH_FLAGS="--full $BENCH_FLAGS"        # the table counts the attribution steps too
 export TMPDIR=/tmp; R=$(pwd); mkdir -p $R/gpurun_out; cd /tmp
 rocprofv3 --kernel-trace --output-format csv -d $R/gpurun_out/tr_$TAG -o tr -- python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --also-concurrent 0 --legs none --no-rccl-selftest $BENCH_FLAGS > $R/gpurun_out/${TAG}_trace_bench.json 2> $R/gpurun_out/${TAG}_trace.err
 cd $R
