@@ -55,6 +55,10 @@ _SIGS = {
     "buddy_wgemm_f16x2_packed_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     "buddy_wgemm_f16x2_pack_weights": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "buddy_gemm_winograd_domain_f16x2": (C.c_int, [_f32p, C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "buddy_wgemm_f16_packed_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    "buddy_wgemm_f16_pack_weights": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "buddy_gemm_winograd_domain_f16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "buddy_conv3x3_winograd6_f16": (C.c_int, [_f32p, C.c_void_p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "buddy_abs_max_bits": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
     "buddy_gemm_bf16x3": (C.c_int, [_f32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_void_p, _f32p, C.c_int, C.c_longlong, C.c_int, C.c_int, _f32p, C.c_float,
                                     C.c_int, C.c_void_p]),
@@ -66,6 +70,8 @@ _SIGS = {
     "buddy_conv3x3_winograd6": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "buddy_gn_conv3x3_winograd6": (C.c_int, [_f32p, _f32p, C.c_int, _f32p, _f32p, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_void_p,
                                              C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "buddy_gn_conv3x3_winograd6_f16": (C.c_int, [_f32p, _f32p, C.c_int, _f32p, _f32p, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_void_p,
+                                                 C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "buddy_conv3x3_winograd6_gn_bwd_sums": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int,
                                                       C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "buddy_gemm_bf16x3_gn_bwd": (C.c_int, [_f32p, C.c_int, C.c_void_p, _f32p, _f32p, C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_float,
@@ -76,10 +82,16 @@ _SIGS = {
                                            _f32p, _f32p, C.c_int, C.c_int, C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "buddy_gn_upconv3x3_winograd6": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_void_p, C.c_void_p,
                                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "buddy_gn_upconv3x3_winograd6_f16": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_void_p, C.c_void_p,
+                                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "buddy_gnbwd_upconv3x3_winograd6": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_void_p, _f32p,
                                                   C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "buddy_gnbwd_upconv3x3_winograd6_f16": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_void_p, _f32p,
+                                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "buddy_gnbwd_conv3x3_winograd6": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_void_p, _f32p,
                                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "buddy_gnbwd_conv3x3_winograd6_f16": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_void_p, _f32p,
+                                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "buddy_gn_conv3x3_winograd4": (C.c_int, [_f32p, _f32p, C.c_int, _f32p, _f32p, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_void_p,
                                              C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "buddy_conv3x3_winograd": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -197,6 +197,21 @@ int buddy_gemm_winograd_domain_f16x2(const float* V, const void* U2, float* Mo, 
   launch_wgemm_f16x2(V, U2, Mo, tiles, Cout, Cin, positions, vmax, tiles_per_utt, (hipStream_t)stream);
   return finish();
 }
+long long buddy_wgemm_f16_packed_bytes(int positions, int Cout, int Cin) {
+  return (positions < 1 || positions > 64 || !wgemm_f16_supported(Cout, Cin)) ? 0 : (long long)wgemm_f16_packed_bytes(positions, Cout, Cin);
+}
+int buddy_wgemm_f16_pack_weights(const float* U, void* U1, int positions, int Cout, int Cin, void* stream) {
+  if (!U || !U1 || positions < 1 || positions > 64 || !wgemm_f16_supported(Cout, Cin)) { set_error("bad arguments (positions <= 64, Cout % 128, Cin % 32)"); return BUDDY_ERR_ARG; }
+  wgemm_f16_pack_weights(U, U1, positions, Cout, Cin, (hipStream_t)stream);
+  return finish();
+}
+int buddy_gemm_winograd_domain_f16(const void* V16, const signed char* vexp, const void* U1, float* Mo, int tiles, int Cout, int Cin, int positions, void* stream) {
+  if (!V16 || !vexp || !U1 || !Mo || tiles < 1 || positions < 1 || positions > 64 || !wgemm_f16_supported(Cout, Cin)) {
+    set_error("bad arguments (positions <= 64, Cout % 128, Cin % 32)"); return BUDDY_ERR_ARG;
+  }
+  launch_wgemm_f16(V16, vexp, U1, Mo, tiles, Cout, Cin, positions, (hipStream_t)stream);
+  return finish();
+}
 int buddy_abs_max_bits(const float* x, int groups, int segments, long long seg_len, unsigned* out, void* stream) {
   if (!x || !out || groups < 1 || segments < 1 || seg_len < 1) { set_error("bad arguments"); return BUDDY_ERR_ARG; }
   launch_abs_max_bits(x, groups, segments, seg_len, out, (hipStream_t)stream);
@@ -315,11 +330,24 @@ int buddy_conv3x3_winograd6(const float* x, const float* U6, const float* bias, 
   return finish();
 }
 
+int buddy_conv3x3_winograd6_f16(const float* x, const void* U1, const float* bias, float* y, float* scratch, int B, int H, int W, int Cin, int Cout,
+                                void* stream) {
+  if (!x || !U1 || !y || !scratch) { set_error("null argument"); return BUDDY_ERR_ARG; }
+  IgemmParams p; std::memset(&p, 0, sizeof(p));
+  p.A0 = x; p.ldA0 = Cin; p.Cin = Cin; p.H = H; p.W = W; p.M = B * H * W; p.N = Cout; p.C = y; p.ldC = Cout;
+  p.bias_n = bias; p.alpha = 1.f; p.out_scale = 1.f; p.rows_per_batch = H * W;
+  if (!wino6_supported(p) || !wgemm_f16_supported(Cout, Cin)) { set_error("shape not supported by the f16 F(6x6,3x3) path (H, W >= 6; Cout % 128, Cin % 32)"); return BUDDY_ERR_ARG; }
+  long long vf = 0, mf = 0; wino6_scratch(p, &vf, &mf);
+  launch_wino6(p, nullptr, scratch, scratch + vf, (hipStream_t)stream, nullptr, nullptr, nullptr, U1, 0, 3);
+  return finish();
+}
+
+// U1 != nullptr (F(6x6,3x3) only): the GEMM pass in f16 on that image (gemm = "f16"), U4 unused
 static int gn_conv3x3_winograd(bool f6, const float* x0, const float* x1, int C0, const float* gamma, const float* beta, int G, int silu, const float* U4,
                                const float* bias, float* y, float* scratch, float* stats, double* stat_scratch, double* csum, int B, int H, int W,
-                               int Cin, int Cout, void* stream) {
-  if (!x0 || !gamma || !beta || !U4 || !y || !scratch || !stats || !stat_scratch || G < 1 || Cin % 4 || (Cin / G) % 4 || Cin > 1024 ||
-      (x1 && (C0 % 4 || C0 < 4 || C0 >= Cin))) { set_error("bad arguments"); return BUDDY_ERR_ARG; }
+                               int Cin, int Cout, void* stream, const void* U1 = nullptr) {
+  if (!x0 || !gamma || !beta || !(U4 || U1) || !y || !scratch || !stats || !stat_scratch || G < 1 || Cin % 4 || (Cin / G) % 4 || Cin > 1024 ||
+      (x1 && (C0 % 4 || C0 < 4 || C0 >= Cin)) || (U1 && !wgemm_f16_supported(Cout, Cin))) { set_error("bad arguments"); return BUDDY_ERR_ARG; }
   hipStream_t st = (hipStream_t)stream;
   IgemmParams p; std::memset(&p, 0, sizeof(p));
   p.ldA0 = Cin; p.Cin = Cin; p.H = H; p.W = W; p.M = B * H * W; p.N = Cout; p.C = y; p.ldC = Cout;
@@ -332,7 +360,7 @@ static int gn_conv3x3_winograd(bool f6, const float* x0, const float* x1, int C0
   gn.stats = stats; gn.gamma = gamma; gn.beta = beta; gn.G = G; gn.silu = silu;
   launch_gn_stats(gn.x, B, H * W, Cin, G, 1e-6f, stat_scratch, stats, st);
   long long vf = 0, mf = 0;
-  if (f6) { wino6_scratch(p, &vf, &mf); launch_wino6(p, U4, scratch, scratch + vf, st, &gn, csum ? stat_scratch : nullptr); }
+  if (f6) { wino6_scratch(p, &vf, &mf); launch_wino6(p, U4, scratch, scratch + vf, st, &gn, csum ? stat_scratch : nullptr, nullptr, U1, 0, U1 ? 3 : 1); }
   else { wino4_scratch(p, &vf, &mf); launch_wino4(p, U4, scratch, scratch + vf, st, &gn, csum ? stat_scratch : nullptr); }
   if (csum) launch_csum_collapse(stat_scratch, sc, B, Cout, csum, st);
   return finish();
@@ -346,6 +374,13 @@ int buddy_gn_conv3x3_winograd6(const float* x0, const float* x1, int C0, const f
                                const float* bias, float* y, float* scratch, float* stats, double* stat_scratch, double* csum, int B, int H, int W,
                                int Cin, int Cout, void* stream) {
   return gn_conv3x3_winograd(true, x0, x1, C0, gamma, beta, G, silu, U6, bias, y, scratch, stats, stat_scratch, csum, B, H, W, Cin, Cout, stream);
+}
+
+int buddy_gn_conv3x3_winograd6_f16(const float* x0, const float* x1, int C0, const float* gamma, const float* beta, int G, int silu, const void* U1,
+                                   const float* bias, float* y, float* scratch, float* stats, double* stat_scratch, double* csum, int B, int H, int W,
+                                   int Cin, int Cout, void* stream) {
+  if (!U1) { set_error("null argument"); return BUDDY_ERR_ARG; }
+  return gn_conv3x3_winograd(true, x0, x1, C0, gamma, beta, G, silu, nullptr, bias, y, scratch, stats, stat_scratch, csum, B, H, W, Cin, Cout, stream, U1);
 }
 
 int buddy_conv3x3_winograd6_gn_bwd_sums(const float* g, const float* U6, float* da, float* scratch, const float* x0, const float* x1, int C0,
@@ -369,10 +404,12 @@ int buddy_conv3x3_winograd6_gn_bwd_sums(const float* g, const float* U6, float* 
   return finish();
 }
 
-int buddy_gnbwd_conv3x3_winograd6(const float* x, const float* gamma, const float* beta, const float* stats, const float* da, int G, int silu,
-                                  const float* U6, float* y, float* scratch, double* stat_scratch, float* red, int B, int H, int W, int C, int Cout,
-                                  void* stream) {
-  if (!x || !gamma || !beta || !stats || !da || !U6 || !y || !scratch || !stat_scratch || !red || G < 1 || C % 4 || (C / G) % 4 || C > 1024) {
+// up = 0 / 2: conv3x3 / the sub-pixel up data-gradient of the GroupNorm backward of da; U1 != nullptr: the GEMM pass in f16 on that image (U6 unused)
+static int gnbwd_conv3x3_winograd6(int up, const float* x, const float* gamma, const float* beta, const float* stats, const float* da, int G, int silu,
+                                   const float* U6, const void* U1, float* y, float* scratch, double* stat_scratch, float* red, int B, int H, int W, int C,
+                                   int Cout, void* stream) {
+  if (!x || !gamma || !beta || !stats || !da || !(U6 || U1) || !y || !scratch || !stat_scratch || !red || G < 1 || C % 4 || (C / G) % 4 || C > 1024 ||
+      (up && Cout % 4) || (U1 && !wgemm_f16_supported(Cout, up ? 4 * C : C))) {
     set_error("bad arguments"); return BUDDY_ERR_ARG;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -383,15 +420,28 @@ int buddy_gnbwd_conv3x3_winograd6(const float* x, const float* gamma, const floa
   W4Gn gn;
   gn.x.p0 = x; gn.x.p1 = nullptr; gn.x.C0 = C; gn.x.ld0 = C; gn.x.ld1 = 0;
   gn.stats = stats; gn.gamma = gamma; gn.beta = beta; gn.G = G; gn.silu = silu; gn.da = da; gn.ldda = C; gn.red = red;
-  launch_gn_bwd_sums(gn.x, stats, gamma, beta, da, B, H, W, C, G, 0, silu, stat_scratch, red, st);
-  long long vf = 0, mf = 0; wino6_scratch(p, &vf, &mf);
-  launch_wino6(p, U6, scratch, scratch + vf, st, &gn);
+  launch_gn_bwd_sums(gn.x, stats, gamma, beta, da, B, up ? 2 * H : H, up ? 2 * W : W, C, G, 0, silu, stat_scratch, red, st);
+  long long vf = 0, mf = 0; wino6_scratch(p, &vf, &mf, up);
+  launch_wino6(p, U6, scratch, scratch + vf, st, &gn, nullptr, nullptr, U1, up, U1 ? 3 : 1);
   return finish();
 }
+int buddy_gnbwd_conv3x3_winograd6(const float* x, const float* gamma, const float* beta, const float* stats, const float* da, int G, int silu,
+                                  const float* U6, float* y, float* scratch, double* stat_scratch, float* red, int B, int H, int W, int C, int Cout,
+                                  void* stream) {
+  return gnbwd_conv3x3_winograd6(0, x, gamma, beta, stats, da, G, silu, U6, nullptr, y, scratch, stat_scratch, red, B, H, W, C, Cout, stream);
+}
+int buddy_gnbwd_conv3x3_winograd6_f16(const float* x, const float* gamma, const float* beta, const float* stats, const float* da, int G, int silu,
+                                      const void* U1, float* y, float* scratch, double* stat_scratch, float* red, int B, int H, int W, int C, int Cout,
+                                      void* stream) {
+  if (!U1) { set_error("null argument"); return BUDDY_ERR_ARG; }
+  return gnbwd_conv3x3_winograd6(0, x, gamma, beta, stats, da, G, silu, nullptr, U1, y, scratch, stat_scratch, red, B, H, W, C, Cout, stream);
+}
 
-int buddy_gn_upconv3x3_winograd6(const float* x, const float* gamma, const float* beta, int G, int silu, const float* U6up, const float* bias, float* y,
-                                 float* scratch, float* stats, double* stat_scratch, double* csum, int B, int H, int W, int Cin, int Cout, void* stream) {
-  if (!x || !gamma || !beta || !U6up || !y || !scratch || !stats || !stat_scratch || G < 1 || Cin % 4 || (Cin / G) % 4 || Cin > 1024 || Cout % 4) {
+// U1 != nullptr: the GEMM pass in f16 on that image (U6up unused)
+static int gn_upconv3x3_winograd6(const float* x, const float* gamma, const float* beta, int G, int silu, const float* U6up, const void* U1, const float* bias,
+                                  float* y, float* scratch, float* stats, double* stat_scratch, double* csum, int B, int H, int W, int Cin, int Cout, void* stream) {
+  if (!x || !gamma || !beta || !(U6up || U1) || !y || !scratch || !stats || !stat_scratch || G < 1 || Cin % 4 || (Cin / G) % 4 || Cin > 1024 || Cout % 4 ||
+      (U1 && !wgemm_f16_supported(4 * Cout, Cin))) {
     set_error("bad arguments"); return BUDDY_ERR_ARG;
   }
   hipStream_t st = (hipStream_t)stream;
@@ -406,28 +456,31 @@ int buddy_gn_upconv3x3_winograd6(const float* x, const float* gamma, const float
   gn.stats = stats; gn.gamma = gamma; gn.beta = beta; gn.G = G; gn.silu = silu;
   launch_gn_stats(gn.x, B, H * W, Cin, G, 1e-6f, stat_scratch, stats, st);
   long long vf = 0, mf = 0; wino6_scratch(p, &vf, &mf, 1);
-  launch_wino6(p, U6up, scratch, scratch + vf, st, &gn, csum ? stat_scratch : nullptr, nullptr, nullptr, 1);
+  launch_wino6(p, U6up, scratch, scratch + vf, st, &gn, csum ? stat_scratch : nullptr, nullptr, U1, 1, U1 ? 3 : 1);
   if (csum) launch_csum_collapse(stat_scratch, sc, B, Cout, csum, st);
   return finish();
+}
+
+int buddy_gn_upconv3x3_winograd6(const float* x, const float* gamma, const float* beta, int G, int silu, const float* U6up, const float* bias, float* y,
+                                 float* scratch, float* stats, double* stat_scratch, double* csum, int B, int H, int W, int Cin, int Cout, void* stream) {
+  return gn_upconv3x3_winograd6(x, gamma, beta, G, silu, U6up, nullptr, bias, y, scratch, stats, stat_scratch, csum, B, H, W, Cin, Cout, stream);
+}
+int buddy_gn_upconv3x3_winograd6_f16(const float* x, const float* gamma, const float* beta, int G, int silu, const void* U1up, const float* bias, float* y,
+                                     float* scratch, float* stats, double* stat_scratch, double* csum, int B, int H, int W, int Cin, int Cout, void* stream) {
+  if (!U1up) { set_error("null argument"); return BUDDY_ERR_ARG; }
+  return gn_upconv3x3_winograd6(x, gamma, beta, G, silu, nullptr, U1up, bias, y, scratch, stats, stat_scratch, csum, B, H, W, Cin, Cout, stream);
 }
 
 int buddy_gnbwd_upconv3x3_winograd6(const float* h, const float* gamma, const float* beta, const float* stats, const float* da, int G, int silu,
                                     const float* U6upT, float* y, float* scratch, double* stat_scratch, float* red, int B, int H, int W, int C,
                                     int Cout, void* stream) {
-  if (!h || !gamma || !beta || !stats || !da || !U6upT || !y || !scratch || !stat_scratch || !red || G < 1 || C % 4 || (C / G) % 4 || C > 1024 ||
-      Cout % 4) { set_error("bad arguments"); return BUDDY_ERR_ARG; }
-  hipStream_t st = (hipStream_t)stream;
-  IgemmParams p; std::memset(&p, 0, sizeof(p));
-  p.ldA0 = C; p.Cin = C; p.H = H; p.W = W; p.M = B * H * W; p.N = Cout; p.C = y; p.ldC = Cout;
-  p.alpha = 1.f; p.out_scale = 1.f; p.rows_per_batch = H * W;
-  if (!wino6_supported(p)) { set_error("shape not supported by the F(6x6,3x3) path (H, W >= 6; channels multiples of 4)"); return BUDDY_ERR_ARG; }
-  W4Gn gn;
-  gn.x.p0 = h; gn.x.p1 = nullptr; gn.x.C0 = C; gn.x.ld0 = C; gn.x.ld1 = 0;
-  gn.stats = stats; gn.gamma = gamma; gn.beta = beta; gn.G = G; gn.silu = silu; gn.da = da; gn.ldda = C; gn.red = red;
-  launch_gn_bwd_sums(gn.x, stats, gamma, beta, da, B, 2 * H, 2 * W, C, G, 0, silu, stat_scratch, red, st);
-  long long vf = 0, mf = 0; wino6_scratch(p, &vf, &mf, 2);
-  launch_wino6(p, U6upT, scratch, scratch + vf, st, &gn, nullptr, nullptr, nullptr, 2);
-  return finish();
+  return gnbwd_conv3x3_winograd6(2, h, gamma, beta, stats, da, G, silu, U6upT, nullptr, y, scratch, stat_scratch, red, B, H, W, C, Cout, stream);
+}
+int buddy_gnbwd_upconv3x3_winograd6_f16(const float* h, const float* gamma, const float* beta, const float* stats, const float* da, int G, int silu,
+                                        const void* U1upT, float* y, float* scratch, double* stat_scratch, float* red, int B, int H, int W, int C,
+                                        int Cout, void* stream) {
+  if (!U1upT) { set_error("null argument"); return BUDDY_ERR_ARG; }
+  return gnbwd_conv3x3_winograd6(2, h, gamma, beta, stats, da, G, silu, nullptr, U1upT, y, scratch, stat_scratch, red, B, H, W, C, Cout, stream);
 }
 
 int buddy_groupnorm_act(const float* x, const float* gamma, const float* beta, float* y, float* stats, void* scratch, int B, int H, int W, int C,

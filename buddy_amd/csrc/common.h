@@ -17,7 +17,7 @@ namespace buddy {
 // ---- launcher options (options.hip): per handle, defaults from the validated BUDDY_* environment ----------------------
 struct Options {
   int conv;            // 3x3 convolution form: 0 by shape (F(6x6) / F(4x4) three-pass, fused F(2x2), direct), 1 direct, 2 wino2, 3 wino4
-  int gemm;            // Winograd-domain GEMM arithmetic: 2 f16x2 (default: two-term f16 splits, 2^-22), 1 bf16x3 (exact split), 0 fp32 MFMA
+  int gemm;            // Winograd-domain GEMM arithmetic: 2 f16x2 (default: two-term f16 splits, 2^-22), 1 bf16x3 (exact split), 0 fp32 MFMA, 3 f16 (opt-in fast mode)
   int attn;            // attention core 0 .. 4 (net.hip)
   int gn_fuse, gn_fuse_bwdin, gn_fuse_bwd, upconv, c2_fuse, attn_tr;                 // fusions of the network graph (A/B switches, default 1)
   int attn_split, attn_nw;                                                           // fp32 attention: forced loop-split count / forward tile height (0 = by shape)
@@ -65,6 +65,11 @@ void wgemm_f16x2_pack_weights(const float* U_dev, void* U2_dev, int P, int Cout,
 constexpr int VMAX_SUB = 64, VMAX_STRIDE = 32;
 void launch_abs_max_bits(const float* x, int groups, int segments, long long seg_len, unsigned* out, hipStream_t st);
 void launch_wgemm_f16x2(const float* V, const void* U2, float* M, long long Mt, int Cout, int Cin, int P, const unsigned* vmax, int tiles_per_utt, hipStream_t st);
+// f16 form (wgemm16.hip; gemm = "f16"): V16 = f16_rn(V 2^e[tile]) with vexp[tile] = e (int8), U1 = f16_rn(U 2^eu[p]) packed with u_inv[p] = 2^-eu[p]; one f16 MFMA per 16 k
+bool wgemm_f16_supported(int Cout, int Cin);                  // Cout % 128, Cin % 32
+size_t wgemm_f16_packed_bytes(int P, int Cout, int Cin);
+void wgemm_f16_pack_weights(const float* U_dev, void* U1_dev, int P, int Cout, int Cin, hipStream_t st);
+void launch_wgemm_f16(const void* V16, const signed char* vexp, const void* U1, float* M, long long Mt, int Cout, int Cin, int P, hipStream_t st);
 bool wgemm_general_supported(int N, int K, int C0, int ldA0, int ldA1, int ldC, const void* A0, const void* A1, const void* C, const void* bias);
 void launch_wgemm_bf16x3_general(const float* A0, int ldA0, const float* A1, int ldA1, int C0, const void* W3, float* C, int ldC, long long M, int N, int K,
                                  const float* bias_n, float alpha, int accumulate, hipStream_t st);
@@ -107,7 +112,8 @@ int wino6_stat_chunks(const IgemmParams& p, int up = 0);
 double wino6_exec_ratio(const IgemmParams& p, int up = 0);
 //   bwd_gn (with stat) -- data-gradient convolutions: the output is the gradient w.r.t. act(GroupNorm(bwd_gn->x)); the partials are the two sums
 //           of that GroupNorm's backward, (dxhat, dxhat * xhat), instead of (sum, sum of squares)
-//   U6x, xform, vmax -- the GEMM pass on the stage image U6x: xform 1 bf16x3, 2 f16x2 (vmax: B zeroed slots for the abs-max of V per utterance)
+//   U6x, xform, vmax -- the GEMM pass on the stage image U6x: xform 1 bf16x3, 2 f16x2 (vmax: B zeroed slots for the abs-max of V per utterance),
+//           3 f16 (U6x = wgemm_f16_pack_weights image; f16 V with per-tile exponents in the V buffer)
 //   up -- sub-pixel forms of conv3x3(nearest-upsample x2) (1) and of its data-gradient (2); p describes the LOW resolution (wino6.hip)
 void launch_wino6(const IgemmParams& p, const float* U6, float* V, float* Mb, hipStream_t st, const W4Gn* gn = nullptr, double* stat = nullptr,
                   const W4Gn* bwd_gn = nullptr, const void* U6x = nullptr, int up = 0, int xform = 1, unsigned* vmax = nullptr);

@@ -109,7 +109,7 @@ struct Arena {
 };
 
 // One prepared operand form of a 3x3 convolution's weights: u = fp32 (direct / Winograd-domain), x = the bf16x3 stage image of u (wgemm.hip)
-struct WVar { float* u = nullptr; void* x = nullptr; void* x2 = nullptr; };   // fp32 form, bf16x3 stage image, f16x2 stage image
+struct WVar { float* u = nullptr; void* x = nullptr; void* x2 = nullptr; void* x1 = nullptr; };   // fp32 form, bf16x3 / f16x2 / f16 (gemm = f16) stage image
 // raw: the torch OIHW tensor on the device.  3x3 convolutions of the ResBlocks get their operand forms LAZILY (conv_weights below): one
 // (direction, kernel variant, arithmetic) per layer is ever built for a given workload, on the GPU (wprep.hip).  wf / wb: forms prepared at
 // creation (the small 2-channel convolutions, 1x1 convolutions)
@@ -476,7 +476,7 @@ int net_set_option(Net* N, const char* key, int value) {
 }
 int net_get_option(Net* N, const char* key, int* value) { return option_get(N->opt, key, value); }
 int net_set_attention(Net* N, int mode) { if (mode < 0 || mode > 4) { set_error("attention mode must be 0..4"); return BUDDY_ERR_ARG; } return net_set_option(N, "attention", mode); }
-int net_set_gemm(Net* N, int mode) { if (mode < 0 || mode > 2) { set_error("gemm mode must be 0 (fp32 MFMA), 1 (bf16x3) or 2 (f16x2)"); return BUDDY_ERR_ARG; } return net_set_option(N, "gemm", mode); }
+int net_set_gemm(Net* N, int mode) { if (mode < 0 || mode > 3) { set_error("gemm mode must be 0 (fp32 MFMA), 1 (bf16x3), 2 (f16x2) or 3 (f16)"); return BUDDY_ERR_ARG; } return net_set_option(N, "gemm", mode); }
 int net_set_fir(Net* N, int fir) { N->fir = fir != 0; N->rsv_vjp = -1; N->tape.clear(); N->have_tape = false; return BUDDY_OK; }
 void net_destroy(Net* N) {
   if (!N) return;
@@ -489,14 +489,14 @@ void net_destroy(Net* N) {
 
 // The operand form `kind` (0 direct, 2 / 4 / 6 = Winograd F(kind x kind, 3x3), 61 = F(6x6,3x3) of the sub-pixel up form) of a 3x3 convolution for one direction, built on first use on
 // the GPU from the raw OIHW tensor (wprep.hip) and cached in the shared store.  want_x: 1 the bf16x3 / 2 the f16x2 stage image (the fp32 form is then only a
-// staging buffer, reused for the next layer); 0: the fp32 form itself is kept.  The preparing stream is drained before the pointer is
+// staging buffer, reused for the next layer); 3: the f16 stage image (wgemm16.hip, gemm = f16); 0: the fp32 form itself is kept.  The preparing stream is drained before the pointer is
 // published, so a replica on another stream may use it at once.
 static const WVar* conv_weights(Net* N, const ConvW& c, bool dgrad, int kind, int want_x) {
   Weights* Wt = N->W.get();
   const int ki = kind == 0 ? 0 : kind == 2 ? 1 : kind == 4 ? 2 : kind == 6 ? 3 : 4;
   WVar& v = c.var[dgrad ? 1 : 0][ki];
   std::lock_guard<std::mutex> lk(Wt->mu);
-  if (want_x == 2 ? v.x2 != nullptr : want_x ? v.x != nullptr : v.u != nullptr) return &v;
+  if (want_x == 3 ? v.x1 != nullptr : want_x == 2 ? v.x2 != nullptr : want_x ? v.x != nullptr : v.u != nullptr) return &v;
   const int ph = kind == 61 ? 4 : 1;                          // sub-pixel up form: four phase kernels per output channel (wprep.hip)
   const int Co = dgrad ? c.cin : ph * c.cout, Ci = dgrad ? ph * c.cout : c.cin;
   const size_t nfl = (size_t)conv3_weight_floats(c.cout, c.cin, kind);
@@ -520,14 +520,15 @@ static const WVar* conv_weights(Net* N, const ConvW& c, bool dgrad, int kind, in
   void* x = nullptr;
   if (want_x) {
     const int P = kind == 4 ? 36 : 64;
-    const size_t bytes = want_x == 2 ? wgemm_f16x2_packed_bytes(P, Co, Ci) : wgemm_packed_bytes(P, Co, Ci);
+    const size_t bytes = want_x == 3 ? wgemm_f16_packed_bytes(P, Co, Ci) : want_x == 2 ? wgemm_f16x2_packed_bytes(P, Co, Ci) : wgemm_packed_bytes(P, Co, Ci);
     if (hipMalloc(&x, bytes) != hipSuccess) { N->prep_failed = true; set_error("out of memory preparing convolution weights"); return nullptr; }
     Wt->lazy_allocs.push_back(x); Wt->lazy_bytes += bytes;
-    if (want_x == 2) wgemm_f16x2_pack_weights(u, x, P, Co, Ci, st);
+    if (want_x == 3) wgemm_f16_pack_weights(u, x, P, Co, Ci, st);
+    else if (want_x == 2) wgemm_f16x2_pack_weights(u, x, P, Co, Ci, st);
     else wgemm_pack_weights(u, x, P, Co, Ci, st);
   }
   (void)hipStreamSynchronize(st);
-  if (want_x == 2) v.x2 = x; else if (want_x) v.x = x; else v.u = u;
+  if (want_x == 3) v.x1 = x; else if (want_x == 2) v.x2 = x; else if (want_x) v.x = x; else v.u = u;
   ++Wt->lazy_count;
   return &v;
 }
@@ -609,7 +610,7 @@ static int conv3(Net* N, const Conv3& c) {
     }
     if (use_wino6 && wino_ok && H >= 6 && W >= 6) {
       const size_t th = c.up == 1 ? H / 7 + 1 : c.up == 2 ? (H + 6) / 7 : (H + 5) / 6, tw = c.up == 1 ? W / 7 + 1 : c.up == 2 ? (W + 6) / 7 : (W + 5) / 6;
-      const size_t need = (size_t)64 * ((size_t)B * th * tw) * (size_t)((c.up == 2 ? 4 : 1) * Cin + (c.up == 1 ? 4 : 1) * Cout);
+      const size_t need = (size_t)64 * ((size_t)B * th * tw) * (size_t)((c.up == 2 ? 4 : 1) * Cin + (c.up == 1 ? 4 : 1) * Cout);   // gemm = f16: V16 + exponents fit in V's part
       if (need > N->w4_need) N->w4_need = need;
     }
     return 0;
@@ -618,7 +619,8 @@ static int conv3(Net* N, const Conv3& c) {
     IgemmParams p = ig_base();
     p.A0 = a; p.ldA0 = Cin; p.Cin = Cin; p.H = H; p.W = W; p.M = B * H * W; p.N = Cout; p.C = c.out; p.ldC = Cout;
     p.bias_n = c.bias; p.bias_bn = c.bias_bn; p.ld_bias_bn = c.ld_bn; p.rows_per_batch = H * W; p.alpha = c.alpha; p.out_scale = c.out_scale;
-    int x3 = wgemm_supported((c.up == 1 ? 4 : 1) * Cout, (c.up == 2 ? 4 : 1) * Cin) ? N->opt.gemm : 0;     // 1 bf16x3, 2 f16x2
+    int x3 = wgemm_supported((c.up == 1 ? 4 : 1) * Cout, (c.up == 2 ? 4 : 1) * Cin) ? N->opt.gemm : 0;     // 1 bf16x3, 2 f16x2, 3 f16
+    if (x3 == 3 && !wgemm_f16_supported((c.up == 1 ? 4 : 1) * Cout, (c.up == 2 ? 4 : 1) * Cin)) x3 = 2;       // what mode 2 runs
     if (x3 == 2 && !wgemm_f16x2_supported((c.up == 1 ? 4 : 1) * Cout, (c.up == 2 ? 4 : 1) * Cin)) x3 = 1;
     const WVar* wv = conv_weights(N, *c.w, c.dgrad, 61, x3);
     unsigned* vm = x3 == 2 ? vmax_slot(N, B) : nullptr;
@@ -632,7 +634,7 @@ static int conv3(Net* N, const Conv3& c) {
     const double xr = wino6_exec_ratio(p, c.up);
     igemm_prof_record(pr, 9, 1, N->st, true, xr);
     launch_wino6(p, wv->u, N->w4_scratch, N->w4_scratch + vf, N->st, gn, stat ? N->partial : nullptr, (stat && want_bwd) ? bwd_gn : nullptr,
-                 x3 == 2 ? wv->x2 : x3 ? wv->x : nullptr, c.up, x3, vm);
+                 x3 == 3 ? wv->x1 : x3 == 2 ? wv->x2 : x3 ? wv->x : nullptr, c.up, x3, vm);
     igemm_prof_record(pr, 9, 1, N->st, false, xr);
     if (stat && (want_bwd || direct)) return sc;
     if (stat && stat_out) { launch_csum_collapse(N->partial, sc, B, Cout, stat_out->csum, N->st); stat_out->has_csum = true; }
@@ -658,12 +660,14 @@ static int conv3(Net* N, const Conv3& c) {
   }
   const bool x3 = N->opt.gemm >= 1 && wgemm_supported(Cout, Cin);     // the batched GEMM pass in split arithmetic: only the stage image is needed
   if (w6) {
-    const int xf = !x3 ? 0 : (N->opt.gemm == 2 && !wgemm_f16x2_supported(Cout, Cin)) ? 1 : N->opt.gemm;     // 1 bf16x3, 2 f16x2
+    int xf = !x3 ? 0 : N->opt.gemm;                                                                        // 1 bf16x3, 2 f16x2, 3 f16
+    if (xf == 3 && !wgemm_f16_supported(Cout, Cin)) xf = 2;                                                // what mode 2 runs
+    if (xf == 2 && !wgemm_f16x2_supported(Cout, Cin)) xf = 1;
     const WVar* wv = conv_weights(N, *c.w, c.dgrad, 6, xf);
     if (!wv) return -1;
     unsigned* vm = xf == 2 ? vmax_slot(N, B) : nullptr;
     if (xf == 2 && !vm) return -1;
-    const float* U6 = wv->u; const void* U6x = xf == 2 ? wv->x2 : xf ? wv->x : nullptr;
+    const float* U6 = wv->u; const void* U6x = xf == 3 ? wv->x1 : xf == 2 ? wv->x2 : xf ? wv->x : nullptr;
     long long vf = 0, mf = 0; wino6_scratch(p, &vf, &mf);
     const bool fuse_bwd = N->opt.gn_fuse_bwd != 0;
     const bool want_bwd = bwd_gn != nullptr && fuse_gn && fuse_bwd;
@@ -700,13 +704,13 @@ static int conv3(Net* N, const Conv3& c) {
   }
   return 0;
 }
-// The general GEMMs in f16x2 arithmetic (round 6; only with gemm = f16x2): option gen_f16x2 = 1 every shape (DEFAULT), 0 never (the exact bf16x3 split),
+// The general GEMMs in f16x2 arithmetic (round 6; with gemm = f16x2, and with gemm = f16, which changes only the batched Winograd-domain GEMMs): option gen_f16x2 = 1 every shape (DEFAULT), 0 never (the exact bf16x3 split),
 // 2 the smaller launches only.  The first version took each row's power of two in a pre-pass that re-read A from beyond L2 and measured equal to bf16x3
 // (331.8 vs 328.4 us, 129.0 vs 128.8 us per launch); with the scale found on the way (wgemm_f16x2_gen_kernel) every 1x1 / NIN / skip-path shape of the
 // network is faster, 6.83 -> 5.98 ms over one forward + VJP at B = 8 (tools/gemm_shapes.py, profiles/README.md round 6) and 1.2 - 1.5x per launch in
 // isolation (tools/gen_gemm_one.py).
 static bool gen_f16x2_on(const Net* N, long long M) {
-  if (N->opt.gemm != 2 || N->opt.gen_f16x2 == 0) return false;
+  if ((N->opt.gemm != 2 && N->opt.gemm != 3) || N->opt.gen_f16x2 == 0) return false;
   return N->opt.gen_f16x2 == 1 || M <= 600000;
 }
 // a plain row-major GEMM against a registered [N][K] weight (1x1 convolution, NIN) in bf16x3 arithmetic when the handle's mode asks for it
@@ -1282,7 +1286,8 @@ int net_reserve(Net* N, int B, int L, int with_vjp, long long* bytes) {
     N->arena.cap = need;
   }
   N->vslots = conv_slots;
-  if (N->opt.gemm == 2 && N->vmax_cap < (size_t)conv_slots * B * VMAX_SUB * VMAX_STRIDE) {
+  // gemm = f16 keeps the slots: a shape its GEMM refuses runs what gemm = f16x2 runs
+  if (N->opt.gemm >= 2 && N->vmax_cap < (size_t)conv_slots * B * VMAX_SUB * VMAX_STRIDE) {
     if (N->vmax) (void)hipFree(N->vmax);
     N->vmax = nullptr; N->vmax_cap = 0;
     HIPCHK(hipMalloc(&N->vmax, (size_t)conv_slots * B * VMAX_SUB * VMAX_STRIDE * 4));
@@ -1306,7 +1311,7 @@ int net_forward(Net* N, const float* x, const float* cnoise, const float* cin_b,
   if (rc) return rc;
   N->st = st;
   N->arena.dry = false; N->arena.overflow = false;
-  if (N->opt.gemm == 2) { HIPCHK(hipMemsetAsync(N->vmax, 0, (size_t)(N->vslot_need[0] ? N->vslot_need[0] : N->vslots) * B * VMAX_SUB * VMAX_STRIDE * 4, st)); N->vslot = 0; }
+  if (N->opt.gemm >= 2) { HIPCHK(hipMemsetAsync(N->vmax, 0, (size_t)(N->vslot_need[0] ? N->vslot_need[0] : N->vslots) * B * VMAX_SUB * VMAX_STRIDE * 4, st)); N->vslot = 0; }
   run_forward(N, x, cnoise, cin_b, cskip_b, cout_b, y, B, L, save != 0);
   N->vslot_need[0] = N->vslot;
   if (N->arena.overflow) { set_error("arena overflow"); return BUDDY_ERR_STATE; }
@@ -1319,7 +1324,7 @@ int net_vjp(Net* N, const float* cot, float* gx, hipStream_t st) {
   if (!N->have_tape) { set_error("vjp without a saved forward"); return BUDDY_ERR_STATE; }
   OptScope scope(&N->opt);
   N->st = st;
-  if (N->opt.gemm == 2) { HIPCHK(hipMemsetAsync(N->vmax, 0, (size_t)(N->vslot_need[1] ? N->vslot_need[1] : N->vslots) * N->rsv_B * VMAX_SUB * VMAX_STRIDE * 4, st)); N->vslot = 0; }
+  if (N->opt.gemm >= 2) { HIPCHK(hipMemsetAsync(N->vmax, 0, (size_t)(N->vslot_need[1] ? N->vslot_need[1] : N->vslots) * N->rsv_B * VMAX_SUB * VMAX_STRIDE * 4, st)); N->vslot = 0; }
   run_vjp(N, cot, gx);
   N->vslot_need[1] = N->vslot;
   if (N->arena.overflow) { set_error("arena overflow"); return BUDDY_ERR_STATE; }

@@ -78,83 +78,93 @@ struct W6Geo { int B, H, W, TH, TW, QC, TPB; long long Mt; int xcd; int Cl; };  
 // S2D (sub-pixel form of the data-gradient of conv3x3(nearest-upsample x2), launch_wino6 up = 2; TS = 7): the input is a (2H, 2W, Cl) tensor read as
 //       its space-to-depth image (H, W, 4 Cl): channel c' = ph * Cl + c, ph = 2 py + px, is pixel (2 y + py, 2 x + px) of channel c; the patch of phase
 //       (py, px) starts at (7 ty - py, 7 tx - px) (the even phase reads rows i, i + 1 of its image, the odd one i - 1, i).  Single source.
+// phase 1 of the input transform for one (tile, channel quad c, patch column col): the column's eight inputs (GroupNorm forms applied, zero padding)
+// through B^T.  Shared by w6_input_kernel and its f16 form.
+template <int GN, bool S2D, int TS>
+__device__ __forceinline__ void w6_in_column(const float* __restrict__ x, int ldX, const W4Gn& gn, int Cin, const W6Geo& geo, int c, int b, int ty, int tx,
+                                             int col, float4 (&t)[8]) {
+  const int H = geo.H, W = geo.W;
+  float mean = 0.f, rstd = 0.f, m1 = 0.f, m2 = 0.f;
+  float4 gm = make_float4(0.f, 0.f, 0.f, 0.f), bt = gm;
+  const float* da = nullptr;
+  const int ph = S2D ? c / geo.Cl : 0, cl = S2D ? c - ph * geo.Cl : c, py = ph >> 1, px = ph & 1;   // cl: channel of the source tensor
+  if (GN) {
+    const int g = cl / ((S2D ? geo.Cl : Cin) / gn.G);
+    mean = gn.stats[((long long)b * gn.G + g) * 2]; rstd = gn.stats[((long long)b * gn.G + g) * 2 + 1];
+    if (GN == 2) { m1 = gn.red[((long long)b * gn.G + g) * 2]; m2 = gn.red[((long long)b * gn.G + g) * 2 + 1]; da = gn.da + cl; }
+    gm = ld4(gn.gamma + cl); bt = ld4(gn.beta + cl);
+    const bool second = !S2D && gn.x.p1 != nullptr && c >= gn.x.C0;
+    x = second ? gn.x.p1 + (c - gn.x.C0) : gn.x.p0 + cl;
+    ldX = second ? gn.x.ld1 : gn.x.ld0;
+  } else {
+    x += cl;
+  }
+  const int gx = TS * tx - (S2D ? px : 1) + col, gy0 = TS * ty - (S2D ? py : 1);
+  float4 d[8];
+  // All loads of the column first, UNCONDITIONAL, from coordinates clamped into the image; the zero padding is applied to the value afterwards.
+  // With the load inside `if (inside)` next to the GroupNorm arithmetic the compiler kept every row's load -> wait -> SiLU chain to itself (10
+  // loads, 18 vmcnt waits in the GN 1 instantiation against 8 / 1 in the plain one): eight load latencies one after the other per thread.
+  const bool okx = (unsigned)gx < (unsigned)W;
+  const int cx = min(max(gx, 0), W - 1);
+  float4 g4[GN == 2 ? 8 : 1];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const int cy = min(max(gy0 + r, 0), H - 1);
+    const long long pix = S2D ? ((long long)b * (2 * H) + 2 * cy + py) * (2 * W) + 2 * cx + px : ((long long)b * H + cy) * W + cx;
+    d[r] = ld4(x + pix * ldX);
+    if (GN == 2) g4[r] = ld4(da + pix * gn.ldda);
+  }
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const bool ok = okx && (unsigned)(gy0 + r) < (unsigned)H;
+    float4 v = d[r];
+    if (GN == 1) {
+      v = make_float4((v.x - mean) * rstd * gm.x + bt.x, (v.y - mean) * rstd * gm.y + bt.y, (v.z - mean) * rstd * gm.z + bt.z,
+                      (v.w - mean) * rstd * gm.w + bt.w);
+      if (gn.silu) v = make_float4(silu_f(v.x), silu_f(v.y), silu_f(v.z), silu_f(v.w));
+    }
+    if (GN == 2) {
+      const float xv[4] = {v.x, v.y, v.z, v.w}, dv[4] = {g4[r].x, g4[r].y, g4[r].z, g4[r].w};
+      const float gv[4] = {gm.x, gm.y, gm.z, gm.w}, bv[4] = {bt.x, bt.y, bt.z, bt.w};
+      float o[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float xh = (xv[j] - mean) * rstd;
+        const float dxh = dv[j] * (gn.silu ? dsilu_f(xh * gv[j] + bv[j]) : 1.f) * gv[j];
+        o[j] = rstd * (dxh - m1 - xh * m2);
+      }
+      v = make_float4(o[0], o[1], o[2], o[3]);
+    }
+    d[r] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  bt8(d, t);                                                 // column: t[:, col] = B^T d[:, col]
+}
+// XCD-aware tile order: the hardware deals consecutive workgroups round-robin to the 8 XCDs (own L2 each), which puts the two tiles that share
+// two of their eight patch columns -- and the tile row below, which shares two rows -- on different L2s: the 1.78x patch overlap was fetched
+// from the fabric almost in full (PMC r03: 2.09x the input instead of ~1.1x).  Each XCD gets a contiguous range of tiles instead.
+__device__ __forceinline__ void w6_xcd_order(int& bx, int& by) {
+  const int n = gridDim.x * gridDim.y, lin = blockIdx.y * gridDim.x + blockIdx.x;
+  const int q8 = n >> 3, r8 = n & 7, xcd = lin & 7, k = lin >> 3;
+  const int nl = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + k;
+  bx = nl % gridDim.x; by = nl / gridDim.x;
+}
+
 template <int GN, bool S2D = false, int TS = 6>
 __global__ __launch_bounds__(256) void w6_input_kernel(const float* __restrict__ x, int ldX, const W4Gn gn, float* __restrict__ V, int Cin,
                                                        const W6Geo geo, unsigned* __restrict__ vmax) {
   __shared__ float4 lds[32 * 64];
   const int tid = threadIdx.x, QC = geo.QC;
   const int ql = tid % QC, col = (tid / QC) & 7, tl = tid / (QC * 8);
-  // XCD-aware tile order: the hardware deals consecutive workgroups round-robin to the 8 XCDs (own L2 each), which puts the two tiles that share
-  // two of their eight patch columns -- and the tile row below, which shares two rows -- on different L2s: the 1.78x patch overlap was fetched
-  // from the fabric almost in full (PMC r03: 2.09x the input instead of ~1.1x).  Each XCD gets a contiguous range of tiles instead.
   int bx = blockIdx.x, by = blockIdx.y;
-  if (geo.xcd) {
-    const int n = gridDim.x * gridDim.y, lin = blockIdx.y * gridDim.x + blockIdx.x;
-    const int q8 = n >> 3, r8 = n & 7, xcd = lin & 7, k = lin >> 3;
-    const int nl = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + k;
-    bx = nl % gridDim.x; by = nl / gridDim.x;
-  }
+  if (geo.xcd) w6_xcd_order(bx, by);
   const int quad = by * QC + ql, c = quad * 4;
   const long long tile = (long long)bx * geo.TPB + tl;
   const bool live = tile < geo.Mt && c < Cin;
-  const int H = geo.H, W = geo.W;
   int b = 0, ty = 0, tx = 0;
   if (live) { tx = (int)(tile % geo.TW); ty = (int)((tile / geo.TW) % geo.TH); b = (int)(tile / ((long long)geo.TW * geo.TH)); }
   if (live) {
-    float mean = 0.f, rstd = 0.f, m1 = 0.f, m2 = 0.f;
-    float4 gm = make_float4(0.f, 0.f, 0.f, 0.f), bt = gm;
-    const float* da = nullptr;
-    const int ph = S2D ? c / geo.Cl : 0, cl = S2D ? c - ph * geo.Cl : c, py = ph >> 1, px = ph & 1;   // cl: channel of the source tensor
-    if (GN) {
-      const int g = cl / ((S2D ? geo.Cl : Cin) / gn.G);
-      mean = gn.stats[((long long)b * gn.G + g) * 2]; rstd = gn.stats[((long long)b * gn.G + g) * 2 + 1];
-      if (GN == 2) { m1 = gn.red[((long long)b * gn.G + g) * 2]; m2 = gn.red[((long long)b * gn.G + g) * 2 + 1]; da = gn.da + cl; }
-      gm = ld4(gn.gamma + cl); bt = ld4(gn.beta + cl);
-      const bool second = !S2D && gn.x.p1 != nullptr && c >= gn.x.C0;
-      x = second ? gn.x.p1 + (c - gn.x.C0) : gn.x.p0 + cl;
-      ldX = second ? gn.x.ld1 : gn.x.ld0;
-    } else {
-      x += cl;
-    }
-    const int gx = TS * tx - (S2D ? px : 1) + col, gy0 = TS * ty - (S2D ? py : 1);
-    float4 d[8], t[8];
-    // All loads of the column first, UNCONDITIONAL, from coordinates clamped into the image; the zero padding is applied to the value afterwards.
-    // With the load inside `if (inside)` next to the GroupNorm arithmetic the compiler kept every row's load -> wait -> SiLU chain to itself (10
-    // loads, 18 vmcnt waits in the GN 1 instantiation against 8 / 1 in the plain one): eight load latencies one after the other per thread.
-    const bool okx = (unsigned)gx < (unsigned)W;
-    const int cx = min(max(gx, 0), W - 1);
-    float4 g4[GN == 2 ? 8 : 1];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const int cy = min(max(gy0 + r, 0), H - 1);
-      const long long pix = S2D ? ((long long)b * (2 * H) + 2 * cy + py) * (2 * W) + 2 * cx + px : ((long long)b * H + cy) * W + cx;
-      d[r] = ld4(x + pix * ldX);
-      if (GN == 2) g4[r] = ld4(da + pix * gn.ldda);
-    }
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const bool ok = okx && (unsigned)(gy0 + r) < (unsigned)H;
-      float4 v = d[r];
-      if (GN == 1) {
-        v = make_float4((v.x - mean) * rstd * gm.x + bt.x, (v.y - mean) * rstd * gm.y + bt.y, (v.z - mean) * rstd * gm.z + bt.z,
-                        (v.w - mean) * rstd * gm.w + bt.w);
-        if (gn.silu) v = make_float4(silu_f(v.x), silu_f(v.y), silu_f(v.z), silu_f(v.w));
-      }
-      if (GN == 2) {
-        const float xv[4] = {v.x, v.y, v.z, v.w}, dv[4] = {g4[r].x, g4[r].y, g4[r].z, g4[r].w};
-        const float gv[4] = {gm.x, gm.y, gm.z, gm.w}, bv[4] = {bt.x, bt.y, bt.z, bt.w};
-        float o[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float xh = (xv[j] - mean) * rstd;
-          const float dxh = dv[j] * (gn.silu ? dsilu_f(xh * gv[j] + bv[j]) : 1.f) * gv[j];
-          o[j] = rstd * (dxh - m1 - xh * m2);
-        }
-        v = make_float4(o[0], o[1], o[2], o[3]);
-      }
-      d[r] = ok ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    bt8(d, t);                                               // column: t[:, col] = B^T d[:, col]
+    float4 t[8];
+    w6_in_column<GN, S2D, TS>(x, ldX, gn, Cin, geo, c, b, ty, tx, col, t);
 #pragma unroll
     for (int r = 0; r < 8; ++r) lds[(tl * 64 + r * 8 + col) * QC + ql] = t[r];
   }
@@ -193,6 +203,99 @@ __global__ __launch_bounds__(256) void w6_input_kernel(const float* __restrict__
         const int bw = (int)(tw / ((long long)geo.TW * geo.TH)), sub = (int)((tw + 13 * by) & (VMAX_SUB - 1));
         atomicMax(vmax + ((long long)bw * VMAX_SUB + sub) * VMAX_STRIDE, __float_as_uint(m));
       }
+    }
+  }
+}
+
+// f16 form (network option gemm = "f16"; wgemm16.hip): the same transform arithmetic in fp32, then ONE rounding to f16 of V . 2^e, with one power of two
+// e per TILE chosen over that tile's values at all 64 positions and all Cin channels so that its abs-max . 2^e lies in [2^14, 2^15) (exponent field of
+// the abs-max clamped to [15, 253]: e = 141 - field, in [-112, 126]; an all-zero tile gets e = 126).  V16[(pos * Mt + tile) * Cin + c] (f16),
+// vexp[tile] (int8).  The scale depends on the tile's data alone: no atomics, bit-for-bit reproducible, independent of the batch.
+// A workgroup therefore sees ALL channels of its tiles: grid ceil(Mt / TPB) (1-D), and it walks the ceil(Cin / 4 / QC) channel blocks of the fp32 form's
+// decomposition (same thread layout, same LDS image) twice: the first walk finds the abs-max, the second stores.  The transformed values of the first
+// KEEP blocks stay in registers between the walks (2, the GroupNorm-backward form 1); blocks beyond (Cin > 4 QC KEEP) are transformed again from their
+// (cache-resident) inputs.
+template <int GN, bool S2D = false, int TS = 6>
+__global__ __launch_bounds__(256) void w6_input_f16_kernel(const float* __restrict__ x, int ldX, const W4Gn gn, _Float16* __restrict__ V,
+                                                           signed char* __restrict__ vexp, int Cin, const W6Geo geo) {
+  constexpr int KEEP = GN == 2 ? 1 : 2;                     // GN 2 reads x and da: a second kept block costs the occupancy
+  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+  __shared__ float4 lds[32 * 64];
+  __shared__ float wmx[256];
+  const int tid = threadIdx.x, QC = geo.QC;
+  const int ql = tid % QC, col = (tid / QC) & 7, tl = tid / (QC * 8);
+  int bx = blockIdx.x, by = 0;
+  if (geo.xcd) w6_xcd_order(bx, by);
+  const long long tile = (long long)bx * geo.TPB + tl;
+  const bool tile_live = tile < geo.Mt;
+  int b = 0, ty = 0, tx = 0;
+  if (tile_live) { tx = (int)(tile % geo.TW); ty = (int)((tile / geo.TW) % geo.TH); b = (int)(tile / ((long long)geo.TW * geo.TH)); }
+  const int nblk = (Cin / 4 + QC - 1) / QC;
+  // channel block k: both phases of the transform; v = this thread's row r = col of the tile's 8 x 8 image (positions 8 r + j) for channels c .. c + 3.
+  // Every thread of the workgroup calls it (two barriers).
+  auto xform = [&](int k, float4 (&v)[8]) -> bool {
+    const int c = (k * QC + ql) * 4;
+    const bool live = tile_live && c < Cin;
+    if (live) {
+      float4 t[8];
+      w6_in_column<GN, S2D, TS>(x, ldX, gn, Cin, geo, c, b, ty, tx, col, t);
+#pragma unroll
+      for (int r = 0; r < 8; ++r) lds[(tl * 64 + r * 8 + col) * QC + ql] = t[r];
+    }
+    __syncthreads();
+    if (live) {
+      float4 d[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) d[j] = lds[(tl * 64 + col * 8 + j) * QC + ql];
+      bt8(d, v);                                             // row: v[r, :] = t[r, :] B
+    }
+    __syncthreads();
+    return live;
+  };
+  float4 keep[KEEP][8];
+  float vm = 0.f;
+  for (int k = 0; k < nblk; ++k) {
+    float4 v[8];
+    if (xform(k, v)) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) vm = fmaxf(fmaxf(vm, fmaxf(fabsf(v[j].x), fabsf(v[j].y))), fmaxf(fabsf(v[j].z), fabsf(v[j].w)));
+#pragma unroll
+      for (int q = 0; q < KEEP; ++q)
+        if (k == q)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) keep[q][j] = v[j];
+    }
+  }
+  for (int o = QC >> 1; o > 0; o >>= 1) vm = fmaxf(vm, __shfl_xor(vm, o));
+  if (ql == 0) wmx[tl * 8 + col] = vm;
+  __syncthreads();
+  float m = wmx[tl * 8];
+#pragma unroll
+  for (int j = 1; j < 8; ++j) m = fmaxf(m, wmx[tl * 8 + j]);
+  int ef = (int)((__float_as_uint(m) >> 23) & 0xFF);
+  ef = ef < 15 ? 15 : (ef > 253 ? 253 : ef);
+  const float s = __uint_as_float((unsigned)(268 - ef) << 23);   // 2^(141 - ef)
+  if (tile_live && ql == 0 && col == 0) vexp[tile] = (signed char)(141 - ef);
+  const long long ps = geo.Mt * Cin;
+  for (int k = 0; k < nblk; ++k) {
+    float4 v[8];
+    bool live;
+    if (k < KEEP) {
+      live = tile_live && (k * QC + ql) * 4 < Cin;
+#pragma unroll
+      for (int q = 0; q < KEEP; ++q)
+        if (k == q)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) v[j] = keep[q][j];
+    } else {
+      live = xform(k, v);
+    }
+    if (live) {
+      _Float16* out = V + tile * Cin + (k * QC + ql) * 4;
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        *reinterpret_cast<f16x4*>(out + (long long)(col * 8 + j) * ps) =
+            f16x4{(_Float16)(v[j].x * s), (_Float16)(v[j].y * s), (_Float16)(v[j].z * s), (_Float16)(v[j].w * s)};
     }
   }
 }
@@ -392,7 +495,8 @@ double wino6_exec_ratio(const IgemmParams& p, int up) {       // executed / dire
 // p.H, p.W, p.M describe the LOW resolution in both.
 void launch_wino6(const IgemmParams& p, const float* U6, float* V, float* Mb, hipStream_t st, const W4Gn* gn, double* stat, const W4Gn* bwd_gn,
                   const void* U6x, int up, int xform, unsigned* vmax) {
-  // xform: the arithmetic of the stage image U6x: 1 = bf16x3, 2 = f16x2 (then vmax: one zeroed slot per utterance for this launch's abs-max of V)
+  // xform: the arithmetic of the stage image U6x: 1 = bf16x3, 2 = f16x2 (then vmax: one zeroed slot per utterance for this launch's abs-max of V), 3 = f16
+  // (U6x: the wgemm16.hip image; the caller checks wgemm_f16_supported)
   if (xform != 2) vmax = nullptr;
   const int CinG = up == 2 ? 4 * p.Cin : p.Cin, NG = up == 1 ? 4 * p.N : p.N;       // K and N of the batched GEMM
   W6Geo gi = geometry(p, CinG, up), go = geometry(p, NG, up);
@@ -404,7 +508,19 @@ void launch_wino6(const IgemmParams& p, const float* U6, float* V, float* Mb, hi
   if (prof) { for (auto& e : ev) (void)hipEventCreate(&e); (void)hipEventRecord(ev[0], st); }
   if (prof_gemm) { (void)hipEventCreate(&ev[1]); (void)hipEventCreate(&ev[2]); }
   const dim3 grid_in((unsigned)((Mt + gi.TPB - 1) / gi.TPB), (unsigned)((CinG / 4 + gi.QC - 1) / gi.QC));
-  if (up == 2) {
+  // xform 3 (f16, wgemm16.hip): V16 (f16) and the tiles' exponents in the V buffer (2 + 1 / (64 Cin) of its 4 bytes per element)
+  _Float16* V16 = reinterpret_cast<_Float16*>(V);
+  signed char* vexp = reinterpret_cast<signed char*>(V16 + 64 * Mt * CinG);
+  const dim3 grid_in16((unsigned)((Mt + gi.TPB - 1) / gi.TPB));
+  if (xform == 3) {
+    if (up == 2 && gn && gn->da) hipLaunchKernelGGL((w6_input_f16_kernel<2, true, 7>), grid_in16, dim3(256), 0, st, (const float*)nullptr, 0, *gn, V16, vexp, CinG, gi);
+    else if (up == 2) hipLaunchKernelGGL((w6_input_f16_kernel<0, true, 7>), grid_in16, dim3(256), 0, st, p.A0, p.ldA0, W4Gn{}, V16, vexp, CinG, gi);
+    else if (up == 1 && gn) hipLaunchKernelGGL((w6_input_f16_kernel<1, false, 7>), grid_in16, dim3(256), 0, st, (const float*)nullptr, 0, *gn, V16, vexp, p.Cin, gi);
+    else if (up == 1) hipLaunchKernelGGL((w6_input_f16_kernel<0, false, 7>), grid_in16, dim3(256), 0, st, p.A0, p.ldA0, W4Gn{}, V16, vexp, p.Cin, gi);
+    else if (gn && gn->da) hipLaunchKernelGGL(w6_input_f16_kernel<2>, grid_in16, dim3(256), 0, st, (const float*)nullptr, 0, *gn, V16, vexp, p.Cin, gi);
+    else if (gn) hipLaunchKernelGGL(w6_input_f16_kernel<1>, grid_in16, dim3(256), 0, st, (const float*)nullptr, 0, *gn, V16, vexp, p.Cin, gi);
+    else hipLaunchKernelGGL(w6_input_f16_kernel<0>, grid_in16, dim3(256), 0, st, p.A0, p.ldA0, W4Gn{}, V16, vexp, p.Cin, gi);
+  } else if (up == 2) {
     if (gn && gn->da) hipLaunchKernelGGL((w6_input_kernel<2, true, 7>), grid_in, dim3(256), 0, st, (const float*)nullptr, 0, *gn, V, CinG, gi, vmax);
     else hipLaunchKernelGGL((w6_input_kernel<0, true, 7>), grid_in, dim3(256), 0, st, p.A0, p.ldA0, W4Gn{}, V, CinG, gi, vmax);
   } else if (up == 1) {
@@ -422,7 +538,8 @@ void launch_wino6(const IgemmParams& p, const float* U6, float* V, float* Mb, hi
   g.M = (int)Mt; g.N = NG; g.H = 1; g.W = 1; g.rows_per_batch = 1; g.alpha = 1.f; g.out_scale = 1.f;
   g.tag = 36;                                                 // the Winograd-domain batched GEMM instantiation (36 or 64 positions)
   igemm_prof_enable(0);
-  if (U6x != nullptr && xform == 2 && wgemm_supported(NG, CinG)) launch_wgemm_f16x2(V, U6x, Mb, Mt, NG, CinG, 64, vmax, gi.TH * gi.TW, st);
+  if (U6x != nullptr && xform == 3) launch_wgemm_f16(V16, vexp, U6x, Mb, Mt, NG, CinG, 64, st);
+  else if (U6x != nullptr && xform == 2 && wgemm_supported(NG, CinG)) launch_wgemm_f16x2(V, U6x, Mb, Mt, NG, CinG, 64, vmax, gi.TH * gi.TW, st);
   else if (U6x != nullptr && wgemm_supported(NG, CinG)) launch_wgemm_bf16x3(V, U6x, Mb, Mt, NG, CinG, 64, st);
   else launch_igemm(g, 1, false, false, 64, st);
   igemm_prof_enable(plevel);

@@ -65,7 +65,7 @@ class _NetFn(torch.autograd.Function):
 
 class NCSNppTime(nn.Module):
     ATTENTION_MODES = {"flash": 0, "bf16": 1, "f16": 2, "matrix": 3, "auto": 4}
-    GEMM_MODES = {"fp32": 0, "bf16x3": 1, "f16x2": 2}
+    GEMM_MODES = {"fp32": 0, "bf16x3": 1, "f16x2": 2, "f16": 3}       # "f16": opt-in fast mode (include/buddy_hip.h, buddy_ncsnpp_set_gemm)
 
     def __init__(self, stft=None, nonlinearity="swish", nf=128, ch_mult=(1, 2, 2, 2), num_res_blocks=1,
                  attn_resolutions=(0,), resamp_with_conv=True, time_conditional=True, fir=False,

@@ -126,6 +126,19 @@ long long buddy_wgemm_f16x2_packed_bytes(int positions, int Cout, int Cin);
 int buddy_wgemm_f16x2_pack_weights(const float* U, void* U2, int positions, int Cout, int Cin, void* stream);
 int buddy_gemm_winograd_domain_f16x2(const float* V, const void* U2, float* M, int tiles, int Cout, int Cin, int positions, const unsigned* vmax,
                                      int tiles_per_utt, void* stream);
+/* The same products in plain "f16" arithmetic (csrc/wgemm16.hip; network option gemm = "f16", the opt-in fast mode): ONE f16 term per operand element,
+ * one v_mfma_f32_32x32x16_f16 per 16 k, fp32 accumulation.  Operand format (positions <= 64, Cout % 128 == 0, Cin % 32 == 0, else 0 / an error):
+ *   V16  [positions][tiles][Cin] _Float16: V16[p][t][c] = f16_rn(V[p][t][c] * 2^vexp[t]), round to nearest even;
+ *   vexp [tiles] int8: one power of two per ROW (the F(6x6,3x3) tile, shared by all positions), in [-112, 126]; the convolutions choose it inside their
+ *        input transform from the tile's abs-max m over all positions and channels: vexp = 141 - clamp(exponent field of m, 15, 253), so m * 2^vexp lies
+ *        in [2^14, 2^15) (an all-zero tile: 126);
+ *   U1   = buddy_wgemm_f16_packed_bytes(...) bytes filled by buddy_wgemm_f16_pack_weights from U [positions][Cout][Cin] (device): per position
+ *        eu[p] = 141 - clamp(exponent field of max |U[p]|, 15, 253) and the elements f16_rn(U[p][n][c] * 2^eu[p]) in the kernel's stage order, then
+ *        positions floats u_inv[p] = 2^-eu[p];
+ *   M[p][t][n] = 2^-vexp[t] * u_inv[p] * sum_c V16[p][t][c] * f16_rn(U[p][n][c] * 2^eu[p])   (fp32 accumulation). */
+long long buddy_wgemm_f16_packed_bytes(int positions, int Cout, int Cin);
+int buddy_wgemm_f16_pack_weights(const float* U, void* U1, int positions, int Cout, int Cin, void* stream);
+int buddy_gemm_winograd_domain_f16(const void* V16, const signed char* vexp, const void* U1, float* M, int tiles, int Cout, int Cin, int positions, void* stream);
 /* out [segments][64][32]: partial maxima (bit patterns, word 0 of each 128-byte line) of |x| over segment u of every one of `groups` equally spaced blocks:
  * x is [groups][segments][seg_len] floats (V: groups = positions, segments = utterances, seg_len = tiles_per_utt * Cin); out is overwritten. */
 int buddy_abs_max_bits(const float* x, int groups, int segments, long long seg_len, unsigned* out, void* stream);
@@ -171,6 +184,26 @@ int buddy_conv3x3_winograd4(const float* x, const float* U4, const float* bias, 
 int buddy_winograd6_transform_weights(const float* wt_host, int Cout, int Cin, float* U6_host);
 int buddy_conv3x3_winograd6(const float* x, const float* U6, const float* bias, float* y, float* scratch, int B, int H, int W, int Cin, int Cout,
                             void* stream);
+/* the same convolution with the Winograd-domain GEMM in plain f16 (network option gemm = "f16"): U1 = buddy_wgemm_f16_pack_weights of U6 (positions 64),
+ * Cout % 128 == 0, Cin % 32 == 0; scratch as above.  On return the first 64 * tiles * Cin * 2 bytes of scratch hold V16 and the next `tiles` bytes vexp
+ * (format of buddy_gemm_winograd_domain_f16; tiles = B * ceil(H/6) * ceil(W/6)). */
+int buddy_conv3x3_winograd6_f16(const float* x, const void* U1, const float* bias, float* y, float* scratch, int B, int H, int W, int Cin, int Cout,
+                                void* stream);
+/* The three GroupNorm-fused forms and the sub-pixel data-gradient below with the GEMM in plain f16: the same arguments with the f16 image U1 (positions 64,
+ * buddy_wgemm_f16_pack_weights of the fp32 form: [64][Cout][Cin], kind 61 [64][4 Cout][Cin] for the up form, [64][Cout][4 C] for its data-gradient) in
+ * place of U6; the GEMM's Cout % 128 == 0 and K % 32 == 0.  V16 and vexp in scratch as for buddy_conv3x3_winograd6_f16 (K = 4 C channels in the
+ * data-gradient of the up form; tiles of the sub-pixel forms: B * (H / 7 + 1) * (W / 7 + 1) forward, B * ceil(H / 7) * ceil(W / 7) data-gradient). */
+int buddy_gn_conv3x3_winograd6_f16(const float* x0, const float* x1, int C0, const float* gamma, const float* beta, int G, int silu, const void* U1,
+                                   const float* bias, float* y, float* scratch, float* stats, double* stat_scratch, double* csum, int B, int H, int W,
+                                   int Cin, int Cout, void* stream);
+int buddy_gnbwd_conv3x3_winograd6_f16(const float* x, const float* gamma, const float* beta, const float* stats, const float* da, int G, int silu,
+                                      const void* U1, float* y, float* scratch, double* stat_scratch, float* red, int B, int H, int W, int C, int Cout,
+                                      void* stream);
+int buddy_gn_upconv3x3_winograd6_f16(const float* x, const float* gamma, const float* beta, int G, int silu, const void* U1up, const float* bias, float* y,
+                                     float* scratch, float* stats, double* stat_scratch, double* csum, int B, int H, int W, int Cin, int Cout, void* stream);
+int buddy_gnbwd_upconv3x3_winograd6_f16(const float* h, const float* gamma, const float* beta, const float* stats, const float* da, int G, int silu,
+                                        const void* U1upT, float* y, float* scratch, double* stat_scratch, float* red, int B, int H, int W, int C,
+                                        int Cout, void* stream);
 /* act(GroupNorm(cat[x0, x1])) -> conv3x3 as ONE three-pass convolution: the normalisation and SiLU are applied inside the input transform
  * (the activated tensor never reaches HBM) and, with csum != NULL, the output transform leaves the per-(utterance, channel) sum and sum of
  * squares of y (csum[B][Cout][2], float64) -- the statistics the NEXT GroupNorm needs (layerspp.py:243-245, 257-259).  x1 may be NULL (single
@@ -245,8 +278,16 @@ int buddy_ncsnpp_set_attention(void* handle, int mode);
  *       fp32's 24), three f16 MFMA products, fp32 accumulation; measured against float64 it is as close as the exact forms (one denoiser evaluation +
  *       VJP 117.2 / 113.0 dB), but it is NOT bit-for-bit the fp32 product;
  *   1 = "bf16x3": every fp32 operand split EXACTLY into three bf16 terms, six bf16 MFMA products, fp32 accumulation: the fp32 kernel's accuracy;
- *   0 = v_mfma_f32_32x32x2_f32 (bit-exact fp32 FMA chains; the reference run).
- * The 1x1 / NIN / DFT GEMMs run in bf16x3 in modes 1 and 2.  Env BUDDY_GEMM=fp32|bf16x3|f16x2 sets the process default. */
+ *   0 = v_mfma_f32_32x32x2_f32 (bit-exact fp32 FMA chains; the reference run);
+ *   3 = "f16", the OPT-IN FAST MODE (not the default, never the headline): the batched F(6x6,3x3) / sub-pixel GEMMs and their input transforms in plain f16
+ *       -- V stored as ONE f16 term with a power of two per tile, U as one f16 term per position scale, one f16 MFMA per 16 k (buddy_gemm_winograd_domain_f16);
+ *       everything else as mode 2, and shapes the f16 GEMM refuses run what mode 2 runs.  11 operand bits instead of 22: one denoiser evaluation + VJP
+ *       against float64 55.3 / 51.6 dB at sigma 0.5 and 67.5 / 63.3 dB at sigma 0.02 (mode 2: 117 / 113 dB); one F(6x6,3x3) convolution 0.7-1.8e-2 of the
+ *       abs-max by form; against mode 2 on the same noise streams |delta SI-SDR to clean| <= 0.0022 dB over informed T = 50 chains and a median of 0.50 dB
+ *       over the blind T = 50 headline batch (two float64 runs of that chaotic chain: 0.74 dB).
+ * The general GEMMs (1x1 / NIN / skip path / DFT) run in bf16x3 in mode 1 and in f16x2 in modes 2 and 3 where their shape allows (bf16x3 with option
+ * gen_f16x2 = 0).
+ * Env BUDDY_GEMM=fp32|bf16x3|f16x2|f16 sets the process default. */
 int buddy_ncsnpp_set_gemm(void* handle, int mode);
 
 /* single-head attention over T tokens without the T x T matrix (online softmax, fp32 MFMA), token-major q, k, v, O [B][T][C], C in {64,128,256}:
