@@ -395,6 +395,130 @@ __global__ void loss_finalize_kernel(const double* partial, int nblk, float kapp
   loss[u] = accumulate ? loss[u] + v : v;
 }
 
+// ---- the rest of the reference's loss family (utils/losses.py:26-93).  The compressed-spectrum members without a frequency weighting keep the two
+// kernels above (the default configuration runs exactly those); every other spectral loss goes through spec_loss_kernel, the time-domain ones through
+// td_loss_kernel.  Same LossJobs-style two-job layout, grid and deterministic per-block double partials + loss_finalize_kernel.
+enum LossKind { LK_COMP_SUMMEAN = 0, LK_COMP_SUM = 1, LK_COMP_MEAN = 2, LK_STFT_SUM = 3, LK_STFT_MAG_SUM = 4, LK_STFT_LOGMAG_SUM = 5,
+                LK_LOG_STFT_SUM = 6, LK_L2_SUM = 7, LK_L2_MEAN = 8, LK_NONE = 9 };
+// phi(X), the representation a spectral loss compares: loss = kappa * sum |phi(w_f X_hat) - phi(w_f Y)|^2 (magnitude kinds: real, in .x)
+template <int K> __device__ __forceinline__ float2 spec_phi(float2 x, float p) {
+  if (K == LK_STFT_SUM) return x;
+  const float r = sqrtf(x.x * x.x + x.y * x.y);
+  if (K == LK_STFT_MAG_SUM) return make_float2(r, 0.f);
+  if (K == LK_STFT_LOGMAG_SUM) return make_float2(log10f(r + 1e-8f), 0.f);
+  if (K == LK_LOG_STFT_SUM) {                                 // log(1 + |X|) exp(j angle X); angle(0) = 0
+    if (r == 0.f) return make_float2(0.f, 0.f);
+    const float s = logf(1.f + r) / r;
+    return make_float2(x.x * s, x.y * s);
+  }
+  return compress(x, p);
+}
+// d |phi(X) - R|^2 / dX (as dRe + j dIm) with D = phi(X) - R = (dr, di); abs and angle have zero gradient at X = 0 (torch autograd)
+template <int K> __device__ __forceinline__ float2 spec_grad(float2 x, float dr, float di, float p) {
+  if (K == LK_STFT_SUM) return make_float2(2.f * dr, 2.f * di);
+  const float r = sqrtf(x.x * x.x + x.y * x.y);
+  if (r == 0.f) return make_float2(0.f, 0.f);
+  const float ir = 1.f / r, cr = x.x * ir, ci = x.y * ir;     // e^{j theta}
+  if (K == LK_STFT_MAG_SUM) return make_float2(2.f * dr * cr, 2.f * dr * ci);
+  if (K == LK_STFT_LOGMAG_SUM) { const float gr = 2.f * dr / ((r + 1e-8f) * 2.302585093f); return make_float2(gr * cr, gr * ci); }
+  float rho, drho;                                            // phi = rho(r) e^{j theta}
+  if (K == LK_LOG_STFT_SUM) { rho = logf(1.f + r); drho = 1.f / (1.f + r); }
+  else { const float re = r + 1e-8f; rho = powf(re, p); drho = p * (rho / re); }
+  const float a = dr * cr + di * ci;                          // Re(conj(D) e^{j theta})
+  const float b = dr * ci - di * cr;                          // Im(conj(D) e^{j theta})
+  const float gr = 2.f * a * drho, gt = -2.f * rho * b * ir;  // dL/dr, (1/r) dL/dtheta
+  return make_float2(gr * cr - gt * ci, gr * ci + gt * cr);
+}
+// R: cached target phi(w_f Y), or nullptr: the target is phi(w_f * what G holds on entry) (the regulariser's detached STFT(rir + t n)).
+// w: per-bin weight table (513 floats), nullptr = no weighting.
+struct SpecJob { const float* R; const float* Xh; float* G; double* partial; const float* w; int T; float kappa; float p; int kind; int blocks; };
+struct SpecJobs { SpecJob j[2]; };
+template <int K> __device__ double spec_loss_rows(const SpecJob& jb, int u, int bx, const float* wl) {
+  const long long total = (long long)jb.T * FB;
+  double acc = 0.0;
+  for (long long i = (long long)bx * 256 + threadIdx.x; i < total; i += (long long)jb.blocks * 256) {
+    const long long t = i / FB; const int f = (int)(i % FB);
+    const long long row = ((long long)u * jb.T + t) * LDSP;
+    const float wf = wl ? wl[f] : 1.f;
+    float2 x = reinterpret_cast<const float2*>(jb.Xh + row)[f];
+    float2 rc;
+    if (jb.R) rc = reinterpret_cast<const float2*>(jb.R + row)[f];
+    else { float2 gy = reinterpret_cast<const float2*>(jb.G + row)[f]; if (wl) { gy.x *= wf; gy.y *= wf; } rc = spec_phi<K>(gy, jb.p); }
+    if (wl) { x.x *= wf; x.y *= wf; }
+    const float2 ph = spec_phi<K>(x, jb.p);
+    const float dr = ph.x - rc.x, di = ph.y - rc.y;
+    acc += (double)(dr * dr + di * di);
+    if (jb.G) {
+      const float2 g = spec_grad<K>(x, dr, di, jb.p);
+      const float s = jb.kappa * wf;                          // d(w x)/dx = w (real)
+      reinterpret_cast<float2*>(jb.G + row)[f] = make_float2(s * g.x, s * g.y);
+    }
+  }
+  return acc;
+}
+__global__ __launch_bounds__(256) void spec_loss_kernel(SpecJobs jobs) {
+  __shared__ double red[256];
+  __shared__ float wl[FB];
+  const bool second = (int)blockIdx.x >= jobs.j[0].blocks;
+  const SpecJob& jb = jobs.j[second ? 1 : 0];
+  const int bx = (int)blockIdx.x - (second ? jobs.j[0].blocks : 0), u = blockIdx.y;
+  if (jb.w) for (int f = threadIdx.x; f < FB; f += 256) wl[f] = jb.w[f];
+  __syncthreads();
+  const float* wp = jb.w ? wl : nullptr;
+  double acc;
+  switch (jb.kind) {                                          // one kind per job: uniform per block
+    case LK_STFT_SUM: acc = spec_loss_rows<LK_STFT_SUM>(jb, u, bx, wp); break;
+    case LK_STFT_MAG_SUM: acc = spec_loss_rows<LK_STFT_MAG_SUM>(jb, u, bx, wp); break;
+    case LK_STFT_LOGMAG_SUM: acc = spec_loss_rows<LK_STFT_LOGMAG_SUM>(jb, u, bx, wp); break;
+    case LK_LOG_STFT_SUM: acc = spec_loss_rows<LK_LOG_STFT_SUM>(jb, u, bx, wp); break;
+    default: acc = spec_loss_rows<LK_COMP_SUMMEAN>(jb, u, bx, wp); break;
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) { if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off]; __syncthreads(); }
+  if (threadIdx.x == 0) jb.partial[(long long)u * jb.blocks + bx] = red[0];
+}
+// R = phi(w_f X) over rows of FB bins (the cached target of a spectral loss; compress_kernel's counterpart for the other kinds / weighted ones)
+template <int K> __device__ __forceinline__ void spec_target_row(const float* X, float* R, long long i, const float* w, float p) {
+  const long long r = i / FB; const int f = (int)(i % FB);
+  float2 x = reinterpret_cast<const float2*>(X + r * LDSP)[f];
+  if (w) { x.x *= w[f]; x.y *= w[f]; }
+  reinterpret_cast<float2*>(R + r * LDSP)[f] = spec_phi<K>(x, p);
+}
+__global__ __launch_bounds__(256) void spec_target_kernel(const float* X, float* R, long long rows, int kind, const float* w, float p) {
+  const long long total = rows * FB;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+    switch (kind) {
+      case LK_STFT_SUM: spec_target_row<LK_STFT_SUM>(X, R, i, w, p); break;
+      case LK_STFT_MAG_SUM: spec_target_row<LK_STFT_MAG_SUM>(X, R, i, w, p); break;
+      case LK_STFT_LOGMAG_SUM: spec_target_row<LK_STFT_LOGMAG_SUM>(X, R, i, w, p); break;
+      case LK_LOG_STFT_SUM: spec_target_row<LK_LOG_STFT_SUM>(X, R, i, w, p); break;
+      default: spec_target_row<LK_COMP_SUMMEAN>(X, R, i, w, p); break;
+    }
+  }
+}
+// time-domain l2_sum / l2_mean: loss_u = kappa * sum_s (yh - y)^2, g = 2 kappa (yh - y).  y == nullptr: the target is yh + t * noise (the
+// regulariser's detached rir + t n; t read from t_dev when given, the captured loop's scalar).
+struct TdJob { const float* y; const float* yh; float* g; double* partial; const float* noise; const float* t_dev; float t; int len; float kappa; int blocks; };
+__global__ __launch_bounds__(256) void td_loss_kernel(TdJob jb) {
+  __shared__ double red[256];
+  const int u = blockIdx.y, bx = blockIdx.x;
+  const float t = jb.t_dev ? *jb.t_dev : jb.t;
+  const long long base = (long long)u * jb.len;
+  double acc = 0.0;
+  for (long long i = (long long)bx * 256 + threadIdx.x; i < jb.len; i += (long long)jb.blocks * 256) {
+    const float yh = jb.yh[base + i];
+    const float y = jb.y ? jb.y[base + i] : yh + t * jb.noise[base + i];
+    const float d = yh - y;
+    acc += (double)(d * d);
+    if (jb.g) jb.g[base + i] = 2.f * jb.kappa * d;
+  }
+  red[threadIdx.x] = acc;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) { if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off]; __syncthreads(); }
+  if (threadIdx.x == 0) jb.partial[(long long)u * jb.blocks + bx] = red[0];
+}
+
 // ---- filter design (reference :212-251) ----
 struct DesignTabs { const int* idx; const float* frac; const float* corr; const float* dpm; const int* fge; };   // per-bin knot index / fraction; OLA corr[Nf]; dpm[Nf][FB]
 // dm[u][n][j], j = 0..K-1 knots (rows 0 and K-1 are zero): sum_e w[e][j-1] * exp(decay[e][j-1])^(-n)
@@ -1151,7 +1275,13 @@ struct BlindOp {
   float *frames = nullptr, *X1 = nullptr, *X2 = nullptr, *X3 = nullptr, *Ybuf = nullptr, *sig1 = nullptr, *sig2 = nullptr;
   // second scratch set: the RIR-regulariser chain of an iteration shares every launch with the reconstruction chain (param_grads)
   float *frames_b = nullptr, *X2_b = nullptr, *X3_b = nullptr, *Ybuf_b = nullptr; double* partial_b = nullptr;
-  int loss_norm = 0;                 // 0 l2_comp_stft_summean (default), 1 l2_comp_stft_sum, 2 l2_comp_stft_mean
+  // one loss descriptor per term: 0 likelihood (rec_loss_grad / fir_loss_grad), 1 operator fit (rec_loss_params), 2 RIR-noise regulariser,
+  // 3 the callable buddy_blindop_stft_loss.  kind: LossKind; fw: frequency weighting 0 none, 1 sqrt, 2 exp, 3 log, 4 linear; comp: compression.
+  struct LossDesc { int kind; int fw; float comp; };
+  static constexpr int NSLOT = 4, NFW = 5;
+  LossDesc slot[NSLOT] = {{0, 0, 0.667f}, {0, 0, 0.667f}, {0, 0, 0.667f}, {0, 0, 0.667f}};
+  float* wtab = nullptr; unsigned wtab_set = 1u;   // NFW x FB weight tables uploaded by the caller (bit k: row k present; row 0 = no weighting)
+  float *Ytd = nullptr, *Yc1 = nullptr;            // time-domain target (y itself) / slot 1's spectral target when it differs from slot 0's
   bool fused_loop = false;           // inside the captured optimisation loop: step counter in design_dm, no loss finalisation, one Adam launch
   bool big_lds = false;              // fir_sb_lds_kernel may take > 64 KB of dynamic LDS (set once at creation, outside any stream capture)
   float *A = nullptr, *Apre = nullptr, *logdm = nullptr, *dmv = nullptr, *gdm = nullptr, *Fin = nullptr, *GFin = nullptr, *GH = nullptr;
@@ -1310,34 +1440,80 @@ struct BlindOp {
     else
       hipLaunchKernelGGL(fir_gradh_kernel, dim3(U * ((Nf + FT - 1) / FT) * ((FB + GH_F - 1) / GH_F)), dim3(256), 0, st, X, xs, GY, GH, U, Tn, Nf, accumulate);
   }
-  // loss_u (+)= kappa * sum |Rc - comp(Xh)|^2, G optional; a second term (Rc1 == nullptr: target = compress(G1 on entry)) may share the launch
+  // ---- loss slots ----
+  static bool is_td(const LossDesc& d) { return d.kind == LK_L2_SUM || d.kind == LK_L2_MEAN; }
+  static bool is_spec(const LossDesc& d) { return d.kind >= LK_COMP_SUMMEAN && d.kind <= LK_LOG_STFT_SUM; }
+  static bool is_comp(const LossDesc& d) { return d.kind <= LK_COMP_MEAN; }
+  static bool legacy(const LossDesc& d) { return is_comp(d) && d.fw == 0; }      // the kernels the default configuration runs
+  // the two slots compare against the same cached target (phi(w_f STFT(y)), or y itself)
+  static bool same_target(const LossDesc& a, const LossDesc& b) {
+    if (is_td(a) || is_td(b)) return is_td(a) && is_td(b);
+    if (!is_spec(a) || !is_spec(b) || a.fw != b.fw) return false;
+    if (is_comp(a) || is_comp(b)) return is_comp(a) && is_comp(b) && a.comp == b.comp;
+    return a.kind == b.kind;
+  }
+  const float* wrow(const LossDesc& d) const { return d.fw ? wtab + (size_t)d.fw * FB : nullptr; }
+  const float* target(int s) const { return is_td(slot[s]) ? Ytd : (s == 1 && !same_target(slot[0], slot[1]) ? Yc1 : Yc); }
+  // R = phi(w_f X) for slot s (rows of FB bins)
+  void spec_target(int s, const float* X, float* R, long long rows) {
+    const LossDesc& d = slot[s];
+    if (legacy(d)) hipLaunchKernelGGL(compress_kernel, dim3(gridf(rows * FB)), dim3(256), 0, st, X, R, rows, d.comp);
+    else hipLaunchKernelGGL(spec_target_kernel, dim3(gridf(rows * FB)), dim3(256), 0, st, X, R, rows, d.kind, wrow(d), d.comp);
+  }
+  // loss_u (+)= kappa * sum |Rc - phi(Xh)|^2, G optional; a second term (Rc1 == nullptr: target = phi(G1 on entry)) may share the launch.
+  // Slots s0 / s1 say which loss each term evaluates; two compressed-spectrum terms without weighting keep comp_loss_kernel.
   static constexpr int LOSS_BLK = 64, LOSS_BLK_B = 32;
-  void comp_loss2(const float* Rc0, const float* Xh0, float* G0, int T0, float w0, float* out0, const float* Rc1, const float* Xh1, float* G1, int T1, float w1,
-                  float* out1, bool two) {
-    LossJobs jobs; std::memset(&jobs, 0, sizeof(jobs));
-    // normalisation of the loss family (utils/losses.py:46-64): summean = mean over frames of the sum over bins (the shipped one), sum, mean over both
-    auto kap = [&](float w, int Tn) { return loss_norm == 0 ? w / (float)Tn : (loss_norm == 1 ? w : w / ((float)Tn * (float)FB)); };
-    const float k0 = kap(w0, T0), k1 = two ? kap(w1, T1) : 0.f;
-    jobs.j[0] = LossJob{Rc0, Xh0, G0, partial, T0, k0, LOSS_BLK};
-    if (two) jobs.j[1] = LossJob{Rc1, Xh1, G1, partial_b, T1, k1, LOSS_BLK_B};
-    hipLaunchKernelGGL(comp_loss_kernel, dim3(LOSS_BLK + (two ? LOSS_BLK_B : 0), U), dim3(256), 0, st, jobs, c.comp);
+  void comp_loss2(int s0, const float* Rc0, const float* Xh0, float* G0, int T0, float w0, float* out0, int s1, const float* Rc1, const float* Xh1, float* G1,
+                  int T1, float w1, float* out1, bool two) {
+    const LossDesc& d0 = slot[s0];
+    const LossDesc& d1 = slot[two ? s1 : s0];
+    // normalisation of the loss family (utils/losses.py:26-64): summean = mean over frames of the sum over bins (the shipped one), mean over both; the rest are sums
+    auto kap = [&](const LossDesc& d, float w, int Tn) { return d.kind == LK_COMP_SUMMEAN ? w / (float)Tn : (d.kind == LK_COMP_MEAN ? w / ((float)Tn * (float)FB) : w); };
+    const float k0 = kap(d0, w0, T0), k1 = two ? kap(d1, w1, T1) : 0.f;
+    const unsigned grid = LOSS_BLK + (two ? LOSS_BLK_B : 0);
+    if (legacy(d0) && (!two || (legacy(d1) && d1.comp == d0.comp))) {
+      LossJobs jobs; std::memset(&jobs, 0, sizeof(jobs));
+      jobs.j[0] = LossJob{Rc0, Xh0, G0, partial, T0, k0, LOSS_BLK};
+      if (two) jobs.j[1] = LossJob{Rc1, Xh1, G1, partial_b, T1, k1, LOSS_BLK_B};
+      hipLaunchKernelGGL(comp_loss_kernel, dim3(grid, U), dim3(256), 0, st, jobs, d0.comp);
+    } else {
+      SpecJobs jobs; std::memset(&jobs, 0, sizeof(jobs));
+      jobs.j[0] = SpecJob{Rc0, Xh0, G0, partial, wrow(d0), T0, k0, d0.comp, d0.kind, LOSS_BLK};
+      if (two) jobs.j[1] = SpecJob{Rc1, Xh1, G1, partial_b, wrow(d1), T1, k1, d1.comp, d1.kind, LOSS_BLK_B};
+      hipLaunchKernelGGL(spec_loss_kernel, dim3(grid, U), dim3(256), 0, st, jobs);
+    }
     if (!fused_loop) {       // the loop only needs the gradient; the loss VALUES are read through buddy_blindop_param_grads / rec_loss_grad
       hipLaunchKernelGGL(loss_finalize_kernel, dim3(U), dim3(32), 0, st, (const double*)partial, LOSS_BLK, k0, out0, 0);
       if (two) hipLaunchKernelGGL(loss_finalize_kernel, dim3(U), dim3(32), 0, st, (const double*)partial_b, LOSS_BLK_B, k1, out1, 0);
     }
   }
-  void comp_loss(const float* Rcx, const float* Xh, float* G, int Tn, float weight, float* out, int accumulate) {
-    (void)accumulate;
-    comp_loss2(Rcx, Xh, G, Tn, weight, out, nullptr, nullptr, nullptr, 0, 0.f, nullptr, false);
+  void comp_loss(int s, const float* Rcx, const float* Xh, float* G, int Tn, float weight, float* out) {
+    comp_loss2(s, Rcx, Xh, G, Tn, weight, out, s, nullptr, nullptr, nullptr, 0, 0.f, nullptr, false);
+  }
+  // time-domain loss of slot s on (U, len) signals: loss_u = kappa * sum (yh - y)^2, g = d loss / d yh (optional); y == nullptr: y = yh + t n
+  void td_loss(int s, const float* y, const float* yh, float* g, int len, float weight, float* out, double* part, const float* noise = nullptr,
+               float t = 0.f, const float* t_dev = nullptr) {
+    const float k = slot[s].kind == LK_L2_MEAN ? weight / (float)len : weight;
+    const TdJob jb{y, yh, g, part, noise, t_dev, t, len, k, LOSS_BLK};
+    hipLaunchKernelGGL(td_loss_kernel, dim3(LOSS_BLK, U), dim3(256), 0, st, jb);
+    if (!fused_loop) hipLaunchKernelGGL(loss_finalize_kernel, dim3(U), dim3(32), 0, st, (const double*)part, LOSS_BLK, k, out, 0);
   }
   // RIR-noise regulariser (reference :94-100): loss(rir, (rir + t n).detach()), gradient w.r.t. the subband filter's output left in X2
   void reg_chain(const float* noise, float t_op, const float* t_op_dev, float w_reg) {
+    const int Q = WIN + WIN / 2;
+    if (is_td(slot[2])) {                                                                           // on the time RIR itself
+      time_rir(rir);
+      td_loss(2, nullptr, rir, sig2, Lr, w_reg, losses + U, partial_b, noise, t_op, t_op_dev);
+      istft_adj(sig2, Td, Q, env_d, Lr, norm, X2);
+      return;
+    }
     fir(Xdelta, 0, Td, Ybuf);                                                                       // rir = istft(FIR(Xdelta, H)), never materialised:
-    istft_stft(Ybuf, Td, WIN + WIN / 2, env_d, Lr, norm, WIN, Td, 1.f / norm, X3, noise, t_op, t_op_dev);   // STFT(rir + t n)
-    hipLaunchKernelGGL(compress_kernel, dim3(gridf((long long)U * Td * FB)), dim3(256), 0, st, (const float*)X3, Rc, (long long)U * Td, c.comp);
-    stft_of_frames(Td, WIN + WIN / 2, env_d, Lr, WIN, Td, 1.f / norm, X2);                           // STFT(rir) from the same frames
-    comp_loss(Rc, X2, X3, Td, w_reg, losses + U, 0);
-    stft_adj_istft_adj(X3, Lr, WIN, Td, 1.f / norm, Td, WIN + WIN / 2, env_d, norm, X2);
+    istft_stft(Ybuf, Td, Q, env_d, Lr, norm, WIN, Td, 1.f / norm, X3, noise, t_op, t_op_dev);       // STFT(rir + t n)
+    const bool leg = legacy(slot[2]);
+    if (leg) hipLaunchKernelGGL(compress_kernel, dim3(gridf((long long)U * Td * FB)), dim3(256), 0, st, (const float*)X3, Rc, (long long)U * Td, slot[2].comp);
+    stft_of_frames(Td, Q, env_d, Lr, WIN, Td, 1.f / norm, X2);                                      // STFT(rir) from the same frames
+    comp_loss(2, leg ? Rc : nullptr, X2, X3, Td, w_reg, losses + U);                                // other kinds: target phi(w_f X3) formed in the loss kernel
+    stft_adj_istft_adj(X3, Lr, WIN, Td, 1.f / norm, Td, Q, env_d, norm, X2);
   }
   void degrade(const float* x, float* y) {
     stft(x, L, WIN, T, 1.f / norm, X1);
@@ -1370,7 +1546,8 @@ int blindop_create(const BlindOpCfg& cfg, int U, int L, BlindOp** out) {
   if (cfg.n_fft != NFFT || cfg.win != WIN || cfg.hop != HOP) { set_error("operator STFT must be 1024/512/128"); return BUDDY_ERR_ARG; }
   if (cfg.num_knots < 3 || cfg.num_knots > 64 || cfg.Nf < 4 || cfg.E < 1) { set_error("bad operator config"); return BUDDY_ERR_ARG; }
   BlindOp* o = new BlindOp();
-  o->c = cfg; o->U = U; o->L = L; o->Nf = cfg.Nf; o->E = cfg.E; o->K = cfg.num_knots; o->NB = cfg.num_knots - 2;
+  o->c = cfg; o->U = U; o->L = L;
+  for (auto& d : o->slot) d.comp = cfg.comp; o->Nf = cfg.Nf; o->E = cfg.E; o->K = cfg.num_knots; o->NB = cfg.num_knots - 2;
   o->T = 1 + (L + WIN) / HOP;
   o->Lh = HOP * cfg.Nf; o->Lm = o->Lh + HOP; o->Lr = o->Lh + 1024; o->Td = 1 + (o->Lr + WIN) / HOP;
   if (2 * o->Lm != N2) { set_error("Nf must be 100 (25856-point minimum-phase FFT)"); delete o; return BUDDY_ERR_ARG; }
@@ -1510,8 +1687,14 @@ int blindop_get_H(BlindOp* o, float* out, hipStream_t st) {
 }
 int blindop_set_y(BlindOp* o, const float* y, hipStream_t st) {
   o->st = st;
-  o->stft(y, o->L, WIN, o->T, 1.f / o->norm, o->X1);
-  hipLaunchKernelGGL(compress_kernel, dim3(gridf((long long)o->U * o->T * FB)), dim3(256), 0, st, (const float*)o->X1, o->Yc, (long long)o->U * o->T, o->c.comp);
+  const bool td0 = BlindOp::is_td(o->slot[0]), td1 = BlindOp::is_td(o->slot[1]);
+  const bool spec0 = BlindOp::is_spec(o->slot[0]), spec1 = BlindOp::is_spec(o->slot[1]);
+  if (td0 || td1) HIPCHK(hipMemcpyAsync(o->Ytd, y, (size_t)o->U * o->L * 4, hipMemcpyDeviceToDevice, st));     // time-domain kinds: y itself
+  if (spec0 || spec1) {
+    o->stft(y, o->L, WIN, o->T, 1.f / o->norm, o->X1);
+    if (spec0) o->spec_target(0, o->X1, o->Yc, (long long)o->U * o->T);                               // default: compress_kernel, as always
+    if (spec1 && !BlindOp::same_target(o->slot[0], o->slot[1])) o->spec_target(1, o->X1, o->Yc1, (long long)o->U * o->T);
+  }
   HIPCHK(hipGetLastError());
   return BUDDY_OK;
 }
@@ -1633,40 +1816,85 @@ int blindop_stft_len_adj(BlindOp* o, const float* G_ref, int len, float* g_x, hi
   HIPCHK(hipGetLastError());
   return BUDDY_OK;
 }
-// loss_u = weight * l2_comp_stft_summean(a_u, b_u) (utils/losses.py:59-64) of two signals of length len in {L, Lr}, with the gradient w.r.t. either
-// argument (NULL: not wanted).  The formula is symmetric in (a, b); each gradient is one pass of the loss kernel against the other side's compressed spectrum.
+// loss_u = weight * loss(a_u, b_u) (slot 3's kind, utils/losses.py:26-93) of two signals of length len in {L, Lr}, with the gradient w.r.t. either
+// argument (NULL: not wanted).  Every formula is symmetric in (a, b); each gradient is one pass of the loss kernel against the other side's target.
 int blindop_stft_loss(BlindOp* o, const float* a, const float* b, int len, float weight, float* loss, float* g_a, float* g_b, hipStream_t st) {
   o->st = st;
   const int U = o->U, Tn = frames_of(o, len);
   if (Tn < 0) { set_error("stft loss: signals of the handle's bound length or of its time-RIR length only"); return BUDDY_ERR_ARG; }
-  const dim3 gc(gridf((long long)U * Tn * FB));
+  if (BlindOp::is_td(o->slot[3])) {                 // l2_sum / l2_mean on the signals themselves
+    if (g_b || !g_a) o->td_loss(3, a, b, g_b, len, weight, loss, o->partial);
+    if (g_a) o->td_loss(3, b, a, g_a, len, weight, loss, o->partial);
+    HIPCHK(hipGetLastError());
+    return BUDDY_OK;
+  }
   o->stft(a, len, WIN, Tn, 1.f / o->norm, o->X1);
   o->stft(b, len, WIN, Tn, 1.f / o->norm, o->X2);
   if (g_b || !g_a) {
-    hipLaunchKernelGGL(compress_kernel, gc, dim3(256), 0, st, (const float*)o->X1, o->Ybuf, (long long)U * Tn, o->c.comp);
-    o->comp_loss(o->Ybuf, o->X2, g_b ? o->X3 : nullptr, Tn, weight, loss, 0);
+    o->spec_target(3, o->X1, o->Ybuf, (long long)U * Tn);
+    o->comp_loss(3, o->Ybuf, o->X2, g_b ? o->X3 : nullptr, Tn, weight, loss);
     if (g_b) o->stft_adj(o->X3, len, WIN, Tn, 1.f / o->norm, g_b);
   }
   if (g_a) {
-    hipLaunchKernelGGL(compress_kernel, gc, dim3(256), 0, st, (const float*)o->X2, o->Ybuf, (long long)U * Tn, o->c.comp);
-    o->comp_loss(o->Ybuf, o->X1, o->X3, Tn, weight, loss, 0);
+    o->spec_target(3, o->X2, o->Ybuf, (long long)U * Tn);
+    o->comp_loss(3, o->Ybuf, o->X1, o->X3, Tn, weight, loss);
     o->stft_adj(o->X3, len, WIN, Tn, 1.f / o->norm, g_a);
   }
   HIPCHK(hipGetLastError());
   return BUDDY_OK;
 }
-// the compression exponent of the spectral losses, (0, 1]; the cached compressed observation must be set again afterwards (buddy_blindop_set_y)
+// the compression exponent of the spectral losses, (0, 1], for every slot; the cached compressed observation must be set again afterwards (buddy_blindop_set_y)
 int blindop_set_compression(BlindOp* o, float comp) {
   if (!(comp > 0.f && comp <= 1.f)) { set_error("compression factor must be in (0, 1]"); return BUDDY_ERR_ARG; }
-  if (comp != o->c.comp && o->gexec) { (void)hipGraphExecDestroy(o->gexec); o->gexec = nullptr; }      // the captured loop holds the exponent as a kernel argument
+  bool changed = false;
+  for (int s = 0; s < BlindOp::NSLOT; ++s) { changed |= o->slot[s].comp != comp; o->slot[s].comp = comp; }
+  if (changed && o->gexec) { (void)hipGraphExecDestroy(o->gexec); o->gexec = nullptr; }      // the captured loop holds the exponent as a kernel argument
   o->c.comp = comp;
   return BUDDY_OK;
 }
-// which member of the l2_comp_stft family the loss entries evaluate: 0 summean (utils/losses.py:59-64), 1 sum (:46-50), 2 mean (:52-57)
+// which member of the l2_comp_stft family every slot evaluates, without weighting: 0 summean (utils/losses.py:59-64), 1 sum (:46-50), 2 mean (:52-57)
 int blindop_set_loss_norm(BlindOp* o, int mode) {
   if (mode < 0 || mode > 2) { set_error("loss normalisation: 0 summean, 1 sum, 2 mean"); return BUDDY_ERR_ARG; }
-  if (mode != o->loss_norm && o->gexec) { (void)hipGraphExecDestroy(o->gexec); o->gexec = nullptr; }      // kappa is a kernel argument of the captured loop
-  o->loss_norm = mode;
+  bool changed = false;
+  for (int s = 0; s < BlindOp::NSLOT; ++s) { changed |= o->slot[s].kind != mode || o->slot[s].fw != 0; o->slot[s].kind = mode; o->slot[s].fw = 0; }
+  if (changed && o->gexec) { (void)hipGraphExecDestroy(o->gexec); o->gexec = nullptr; }      // kappa is a kernel argument of the captured loop
+  return BUDDY_OK;
+}
+// the per-bin weight table (FB floats, host memory) of frequency weighting fw in 1..4; kept until the handle is destroyed
+int blindop_set_freq_weights(BlindOp* o, int fw, const float* w) {
+  if (fw < 1 || fw >= BlindOp::NFW) { set_error("frequency weighting: 1 sqrt, 2 exp, 3 log, 4 linear"); return BUDDY_ERR_ARG; }
+  if (!w) { set_error("weight table: null"); return BUDDY_ERR_ARG; }
+  for (int f = 0; f < FB; ++f)
+    if (!std::isfinite(w[f])) { set_error("weight table: non-finite entry"); return BUDDY_ERR_ARG; }
+  if (!o->wtab && o->dalloc(&o->wtab, (size_t)BlindOp::NFW * FB)) { set_error("hipMalloc failed"); return BUDDY_ERR_HIP; }
+  HIPCHK(hipMemcpy(o->wtab + (size_t)fw * FB, w, (size_t)FB * 4, hipMemcpyHostToDevice));
+  o->wtab_set |= 1u << fw;
+  if (o->gexec) { (void)hipGraphExecDestroy(o->gexec); o->gexec = nullptr; }
+  return BUDDY_OK;
+}
+// slot 0..3 := (kind, frequency weighting, compression); see include/buddy_hip.h for the tables.  Call buddy_blindop_set_y again afterwards when
+// slot 0 or 1 changed: the cached targets depend on them.
+int blindop_set_loss(BlindOp* o, int s, int kind, int fw, float comp) {
+  if (s < 0 || s >= BlindOp::NSLOT) { set_error("loss slot: 0 likelihood, 1 operator fit, 2 RIR-noise regulariser, 3 callable loss"); return BUDDY_ERR_ARG; }
+  if (kind < LK_COMP_SUMMEAN || kind > LK_NONE) { set_error("loss kind: 0..8, or 9 = none"); return BUDDY_ERR_ARG; }
+  if (kind == LK_NONE && s != 1) { set_error("loss kind none: slot 1 (operator fit) only"); return BUDDY_ERR_ARG; }
+  if (fw < 0 || fw >= BlindOp::NFW) { set_error("frequency weighting: 0 none, 1 sqrt, 2 exp, 3 log, 4 linear"); return BUDDY_ERR_ARG; }
+  const BlindOp::LossDesc d{kind, fw, comp};
+  if (fw != 0 && !BlindOp::is_spec(d)) { set_error("frequency weighting applies to the STFT losses only"); return BUDDY_ERR_ARG; }
+  if (fw != 0 && !((o->wtab_set >> fw) & 1u)) { set_error("frequency weighting: its table has not been uploaded (buddy_blindop_set_freq_weights)"); return BUDDY_ERR_ARG; }
+  if (BlindOp::is_comp(d) && !(comp > 0.f && comp <= 1.f)) { set_error("compression factor must be in (0, 1]"); return BUDDY_ERR_ARG; }
+  BlindOp::LossDesc nd = d;
+  if (!BlindOp::is_comp(d)) nd.comp = o->slot[s].comp;      // unused by the other kinds
+  // buffers the new configuration needs, allocated here (never inside the captured loop)
+  BlindOp::LossDesc next[2] = {o->slot[0], o->slot[1]};
+  if (s < 2) next[s] = nd;
+  if ((BlindOp::is_td(next[0]) || BlindOp::is_td(next[1])) && !o->Ytd && o->dalloc(&o->Ytd, (size_t)o->U * o->L)) { set_error("hipMalloc failed"); return BUDDY_ERR_HIP; }
+  if (BlindOp::is_spec(next[1]) && !BlindOp::same_target(next[0], next[1]) && !o->Yc1 && o->dalloc(&o->Yc1, (size_t)o->U * o->T * LDSP + 8)) {
+    set_error("hipMalloc failed"); return BUDDY_ERR_HIP;
+  }
+  const BlindOp::LossDesc& od = o->slot[s];
+  if ((od.kind != nd.kind || od.fw != nd.fw || od.comp != nd.comp) && s < 3 && o->gexec) { (void)hipGraphExecDestroy(o->gexec); o->gexec = nullptr; }
+  o->slot[s] = nd;
   return BUDDY_OK;
 }
 int blindop_lengths(BlindOp* o, int* L, int* Lr, int* T, int* Td) { if (L) *L = o->L; if (Lr) *Lr = o->Lr; if (T) *T = o->T; if (Td) *Td = o->Td; return BUDDY_OK; }
@@ -1677,10 +1905,16 @@ int blindop_rec_loss_grad(BlindOp* o, const float* x_den, float weight, float* l
   const int U = o->U, T = o->T, L = o->L;
   o->stft(x_den, L, WIN, T, 1.f / o->norm, o->X1);
   o->fir(o->X1, (long long)T * LDSP, T, o->Ybuf);
-  o->istft_stft(o->Ybuf, T, WIN + WIN / 2, o->env_T, L, o->norm, WIN, T, 1.f / o->norm, o->X2);
-  o->comp_loss(o->Yc, o->X2, g_x ? o->X3 : nullptr, T, weight, loss, 0);
+  if (BlindOp::is_td(o->slot[0])) {                  // loss on the degraded signal itself: FIR -> istft -> loss -> istft_adj -> fir_adjx -> stft_adj
+    o->istft(o->Ybuf, T, WIN + WIN / 2, o->env_T, L, o->norm, o->sig1);
+    o->td_loss(0, o->Ytd, o->sig1, g_x ? o->sig2 : nullptr, L, weight, loss, o->partial);
+    if (g_x) o->istft_adj(o->sig2, T, WIN + WIN / 2, o->env_T, L, o->norm, o->X2);
+  } else {
+    o->istft_stft(o->Ybuf, T, WIN + WIN / 2, o->env_T, L, o->norm, WIN, T, 1.f / o->norm, o->X2);
+    o->comp_loss(0, o->target(0), o->X2, g_x ? o->X3 : nullptr, T, weight, loss);
+    if (g_x) o->stft_adj_istft_adj(o->X3, L, WIN, T, 1.f / o->norm, T, WIN + WIN / 2, o->env_T, o->norm, o->X2);
+  }
   if (g_x) {
-    o->stft_adj_istft_adj(o->X3, L, WIN, T, 1.f / o->norm, T, WIN + WIN / 2, o->env_T, o->norm, o->X2);
     hipLaunchKernelGGL(fir_adjx_kernel, dim3(gridf((long long)U * T * FB)), dim3(256), 0, st, (const float*)o->X2, (const float*)o->H, o->X3, U, T, o->Nf);
     o->stft_adj(o->X3, L, WIN, T, 1.f / o->norm, g_x);
   }
@@ -1696,12 +1930,14 @@ int blindop_fir_loss_grad(BlindOp* o, const float* x_den, const float* rir, long
   o->st = st;
   const int U = o->U, T = o->T, L = o->L;
   launch_fir(x_den, rir, rir_stride, o->sig1, U, L, M, 0, st);
-  o->stft(o->sig1, L, WIN, T, 1.f / o->norm, o->X2);
-  o->comp_loss(o->Yc, o->X2, g_x ? o->X3 : nullptr, T, weight, loss, 0);
-  if (g_x) {
-    o->stft_adj(o->X3, L, WIN, T, 1.f / o->norm, o->sig2);
-    launch_fir(o->sig2, rir, rir_stride, g_x, U, L, M, 1, st);
+  if (BlindOp::is_td(o->slot[0])) {                  // loss on sig1 directly, then the FIR adjoint
+    o->td_loss(0, o->Ytd, o->sig1, g_x ? o->sig2 : nullptr, L, weight, loss, o->partial);
+  } else {
+    o->stft(o->sig1, L, WIN, T, 1.f / o->norm, o->X2);
+    o->comp_loss(0, o->target(0), o->X2, g_x ? o->X3 : nullptr, T, weight, loss);
+    if (g_x) o->stft_adj(o->X3, L, WIN, T, 1.f / o->norm, o->sig2);
   }
+  if (g_x) launch_fir(o->sig2, rir, rir_stride, g_x, U, L, M, 1, st);
   HIPCHK(hipGetLastError());
   return BUDDY_OK;
 }
@@ -1714,7 +1950,8 @@ static int param_grads(BlindOp* o, const float* x_den, const float* noise, float
   const float norm = o->norm;
   o->update_H();
   if (!have_Xd) o->stft(x_den, L, WIN, T, 1.f / norm, o->X1);          // X1 = STFT(x_den) stays valid across the iterations
-  if (noise && o->fir_lds_ok()) {
+  const bool rec_on = o->slot[1].kind != LK_NONE;
+  if (noise && o->fir_lds_ok() && BlindOp::is_spec(o->slot[1]) && BlindOp::is_spec(o->slot[2])) {
     // The reconstruction term and the RIR-noise regulariser (reference :94-100: loss(rir, (rir + t n).detach())) are the same chain
     //   FIR by H -> iSTFT -> STFT -> compressed-spectrum loss -> adjoints -> tap gradient
     // on two inputs (STFT(x_den), T frames; STFT(delta), Td frames): every kernel of the chain takes both as two jobs of ONE launch (7 launches
@@ -1729,7 +1966,7 @@ static int param_grads(BlindOp* o, const float* x_den, const float* noise, float
           {R2cSrc{nullptr, o->frames_b, o->Lr, WIN, Td, Q, o->env_d, nullptr, noise, t_op, t_op_dev}, Td, o->X3_b}};
       o->r2c_multi(rq, 3, 1.f / norm, 0);
     }
-    o->comp_loss2(o->Yc, o->X2, o->X3, T, w_rec, o->losses, nullptr, o->X2_b, o->X3_b, Td, w_reg, o->losses + U, true);
+    o->comp_loss2(1, o->target(1), o->X2, o->X3, T, w_rec, o->losses, 2, nullptr, o->X2_b, o->X3_b, Td, w_reg, o->losses + U, true);
     o->c2r2(o->X3, (long long)U * T, o->frames, o->X3_b, (long long)U * Td, o->frames_b, 1.f / norm, 0);
     {   // istft_adj(stft_adj(.)) of both
       const BlindOp::R2cReq rq[2] = {
@@ -1739,15 +1976,26 @@ static int param_grads(BlindOp* o, const float* x_den, const float* noise, float
     }
     o->gradh2(o->X1, (long long)T * LDSP, o->X2, T, o->Xdelta, 0LL, o->X2_b, Td, 0);
   } else {
-    // reconstruction term
-    o->fir(o->X1, (long long)T * LDSP, T, o->Ybuf);
-    o->istft_stft(o->Ybuf, T, WIN + WIN / 2, o->env_T, L, norm, WIN, T, 1.f / norm, o->X2);
-    o->comp_loss(o->Yc, o->X2, o->X3, T, w_rec, o->losses, 0);
-    o->stft_adj_istft_adj(o->X3, L, WIN, T, 1.f / norm, T, WIN + WIN / 2, o->env_T, norm, o->X2);
-    o->gradh(o->X1, (long long)T * LDSP, o->X2, T, 0);
+    // reconstruction term (slot 1: a time-domain kind compares the degraded signal itself; "none" drops the term)
+    if (BlindOp::is_td(o->slot[1])) {
+      o->fir(o->X1, (long long)T * LDSP, T, o->Ybuf);
+      o->istft(o->Ybuf, T, WIN + WIN / 2, o->env_T, L, norm, o->sig1);
+      o->td_loss(1, o->Ytd, o->sig1, o->sig2, L, w_rec, o->losses, o->partial);
+      o->istft_adj(o->sig2, T, WIN + WIN / 2, o->env_T, L, norm, o->X2);
+      o->gradh(o->X1, (long long)T * LDSP, o->X2, T, 0);
+    } else if (rec_on) {
+      o->fir(o->X1, (long long)T * LDSP, T, o->Ybuf);
+      o->istft_stft(o->Ybuf, T, WIN + WIN / 2, o->env_T, L, norm, WIN, T, 1.f / norm, o->X2);
+      o->comp_loss(1, o->target(1), o->X2, o->X3, T, w_rec, o->losses);
+      o->stft_adj_istft_adj(o->X3, L, WIN, T, 1.f / norm, T, WIN + WIN / 2, o->env_T, norm, o->X2);
+      o->gradh(o->X1, (long long)T * LDSP, o->X2, T, 0);
+    } else {
+      HIPCHK(hipMemsetAsync(o->losses, 0, (size_t)U * 4, st));
+      if (!noise) HIPCHK(hipMemsetAsync(o->GH, 0, (size_t)U * Nf * LDSP * 4, st));
+    }
     if (noise) {
       o->reg_chain(noise, t_op, t_op_dev, w_reg);
-      o->gradh(o->Xdelta, 0LL, o->X2, Td, 1);
+      o->gradh(o->Xdelta, 0LL, o->X2, Td, rec_on ? 1 : 0);
     }
   }
   o->cons_backward(o->GH);

@@ -150,7 +150,7 @@ class EulerHeunSamplerDPS(EulerHeunSampler):
             self.RIR_noise_regularization_loss = get_loss(ps.RIR_noise_regularization.loss, operator=operator)
         if operator.hip_bind(y, ps) is False:
             raise NotImplementedError("this observation / loss configuration is outside what the HIP likelihood kernels are built for "
-                                      "(2-D GPU tensor of >= 1024 samples, l2_comp_stft_summean @ 0.667, operator STFT 1024/512/128 hann)")
+                                      "(2-D GPU tensor of >= 1024 samples, a non-hybrid rec_loss of utils.losses.SUPPORTED, operator STFT 1024/512/128 hann)")
 
     def predict_conditional(self, y, operator, shape=None, blind=False, **kwargs):
         self.bind(y, operator, blind)

@@ -34,34 +34,37 @@ class RIROperator(Operator, OperatorSTFT):
 
     # ---- sampler fast path: likelihood loss + analytic gradient in the HIP library (buddy_blindop_fir_loss_grad) ----
     def hip_bind(self, y, ps):
-        """True if the HIP likelihood path is usable for this run (CUDA, shipped loss); caches comp(STFT(y)) in a library handle."""
-        from .subband_filtering import create_stft_loss_handle
+        """True if the HIP likelihood path is usable for this run (CUDA, operator STFT 1024/512/128 hann, a non-hybrid rec_loss); caches the loss
+        target of y in the library handle of y's shape (slot 0)."""
         from ... import _lib
+        from ...utils.losses import bind_slot, get_loss
         l, hp = ps.rec_loss, self.op_hp
-        from ...utils.losses import NORM_MODE
-        if not (y.is_cuda and y.dim() == 2 and not hasattr(l, "loss_1") and l.name in NORM_MODE and 0.0 < float(l.compression_factor) <= 1.0
+        if not (y.is_cuda and y.dim() == 2 and not hasattr(l, "loss_1") and l.name != "none"
                 and (hp.NFFT, hp.win_length, hp.hop, hp.window) == (1024, 512, 128, "hann") and y.shape[1] >= 1024):
             return False
-        h = self._loss_handle(int(y.shape[0]), int(y.shape[1]))
+        spec = get_loss(l)
+        key = (int(y.shape[0]), int(y.shape[1]))
+        h = self._loss_handle(*key)
         self._hip_w = float(l.get("weight", 1.0))
-        self._comp_created, self._loss_norm = float(l.compression_factor), NORM_MODE[l.name]
-        _lib.check(_lib.load().buddy_blindop_set_compression(h, self._comp_created))
-        _lib.check(_lib.load().buddy_blindop_set_loss_norm(h, self._loss_norm))
+        if not hasattr(self, "_fw_uploaded"):
+            self.__dict__["_fw_uploaded"] = set()
+        bind_slot(h, 0, spec, self._fw_uploaded)
         _lib.check(_lib.load().buddy_blindop_set_y(h, _lib.ptr(y.contiguous().float()), _lib.stream_ptr()))
+        self.__dict__["_hip_h"], self.__dict__["_hip_key"] = h, key        # the handle the likelihood calls use
         return True
 
     def _loss_handle(self, U, n):
-        """library handle (STFT-1024/512/128 + compressed-spectrum loss machinery) for (U, n) signals; one is kept, rebuilt when the shape changes"""
+        """library handle (STFT-1024/512/128 + loss machinery) for (U, n) signals, one per shape (the bound likelihood handle is never rebuilt
+        by a callable loss or apply_stft of another shape)"""
         from .subband_filtering import create_stft_loss_handle
         hp = self.op_hp
         if (hp.NFFT, hp.win_length, hp.hop, hp.window) != (1024, 512, 128, "hann") or n < 1024:
             raise NotImplementedError("the HIP STFT / loss kernels are built for the operator STFT 1024 / 512 / 128 (hann) and signals of >= 1024 samples")
         key = (int(U), int(n))
-        if getattr(self, "_hip_key", None) != key:
-            self._hip_release()
-            self._hip_h = create_stft_loss_handle(self.sample_rate, key[0], key[1])
-            self._hip_key = key
-        return self._hip_h
+        hs = self.__dict__.setdefault("_hip_handles", {})
+        if key not in hs:
+            hs[key] = create_stft_loss_handle(self.sample_rate, key[0], key[1])
+        return hs[key]
 
     def apply_stft(self, x):
         """reference reverb.py:54-72 -> (U, 513, frames) complex64, differentiable (its adjoint runs in the library): get_loss(...)(y, y_hat) of the
@@ -79,6 +82,9 @@ class RIROperator(Operator, OperatorSTFT):
     def hip_rec_loss_grad(self, x_den):
         """d (sum_u weight * rec_loss_u) / d x_den straight from the library (no autograd graph)"""
         from ... import _lib
+        key = getattr(self, "_hip_key", None)
+        if key is None or tuple(x_den.shape) != key:
+            raise ValueError(f"hip_rec_loss_grad: x_den of shape {tuple(x_den.shape)}, the likelihood was bound (hip_bind) for {key}")
         x = x_den.contiguous().float()
         rir = self.params.detach().contiguous().float()
         M = rir.shape[-1]
@@ -91,12 +97,12 @@ class RIROperator(Operator, OperatorSTFT):
 
     def _hip_release(self):
         try:
-            if getattr(self, "_hip_h", None) is not None:
-                from ... import _lib
-                _lib.load().buddy_blindop_destroy(self._hip_h)
+            from ... import _lib
+            for h in (self.__dict__.get("_hip_handles") or {}).values():
+                _lib.load().buddy_blindop_destroy(h)
         except Exception:
             pass
-        self.__dict__["_hip_h"] = None; self.__dict__["_hip_key"] = None     # not via nn.Module.__setattr__: also runs at interpreter shutdown
+        self.__dict__["_hip_handles"] = {}; self.__dict__["_hip_h"] = None; self.__dict__["_hip_key"] = None     # not via nn.Module.__setattr__: also runs at interpreter shutdown
 
     def __del__(self):
         try:

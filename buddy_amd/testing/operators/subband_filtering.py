@@ -33,7 +33,7 @@ class SubbandFiltering(Operator, OperatorSTFT):
 
 
 class _HipRecLoss(torch.autograd.Function):
-    """sum_u weight * l2_comp_stft_summean(y_u, degrade(x_den_u)) with the analytic gradient from the HIP operator."""
+    """sum_u weight * rec_loss(y_u, degrade(x_den_u)) (slot 0 of the handle) with the analytic gradient from the HIP operator."""
 
     @staticmethod
     def forward(ctx, x_den, op, weight):
@@ -148,7 +148,7 @@ class _StftFn(torch.autograd.Function):
 
 
 class _StftLossFn(torch.autograd.Function):
-    """sum_u weight * l2_comp_stft_summean(a_u, b_u) (reference utils/losses.py:59-64) in ONE library call, gradient w.r.t. whichever side needs it."""
+    """sum_u weight * loss(a_u, b_u) (slot 3 of the handle, reference utils/losses.py:26-93) in ONE library call, gradient w.r.t. whichever side needs it."""
 
     @staticmethod
     def forward(ctx, a, b, h, weight, sink):
@@ -174,7 +174,7 @@ class _StftLossFn(torch.autograd.Function):
 
 
 def create_stft_loss_handle(sample_rate, num_utts, length):
-    """Library handle used only for its STFT-1024/512/128 + compressed-spectrum-loss machinery (informed operator): the blind filter
+    """Library handle used only for its STFT-1024/512/128 + loss machinery (informed operator): the blind filter
     parameters of the handle are placeholders."""
     import ctypes as C
     lib = _lib.require_gpu()
@@ -186,11 +186,13 @@ def create_stft_loss_handle(sample_rate, num_utts, length):
 
 
 class _HipFirRecLoss(torch.autograd.Function):
-    """sum_u weight * l2_comp_stft_summean(y_u, x_den_u * rir_u) for the informed operator, analytic gradient from the library."""
+    """sum_u weight * rec_loss(y_u, x_den_u * rir_u) (slot 0) for the informed operator, analytic gradient from the library."""
 
     @staticmethod
     def forward(ctx, x_den, op, weight):
         lib = _lib.require_gpu()
+        if tuple(x_den.shape) != getattr(op, "_hip_key", None):
+            raise ValueError(f"hip_rec_loss: x_den of shape {tuple(x_den.shape)}, the likelihood was bound (hip_bind) for {getattr(op, '_hip_key', None)}")
         x = x_den.contiguous().float()
         rir = op.params.detach().contiguous().float()
         M = rir.shape[-1]
@@ -246,8 +248,7 @@ class BlindSubbandFiltering(SubbandFiltering):
                                             float(10 ** (self.Amax / 20)), int(bool(op_hp.clamp_decay)),
                                             int(bool(op_hp.enforce_long_decay_in_second_exponential)), C.byref(h)))
         self._h = h
-        self._comp_created = 0.667
-        self._loss_norm = 0           # member of the l2_comp_stft family the fused calls evaluate (hip_bind): 0 summean
+        self._comp_created = 0.667    # compression exponent of the likelihood slot (hip_bind / set_compression)
         self._h_epoch = 0             # bumped by every update_H: a saved autograd node of an older H refuses to run its backward
         self._Hr = None               # H of the last autograd-mode update_H (real view, carries the graph to the parameters)
         self._pt = None               # persistent parameter tensors (decay, weights, phases) once somebody asked for ``params`` (see there)
@@ -431,23 +432,28 @@ class BlindSubbandFiltering(SubbandFiltering):
 
     # ---- sampler fast paths ----
     def hip_bind(self, y, ps):
-        """cache comp(STFT(y)); read loss weights / compression from the posterior_sampling config"""
+        """cache the likelihood / operator-fit targets of y; one loss per term from the posterior_sampling config (slots 0..2 of the handle)"""
         # the regulariser is gated like the reference gates it (EulerHeunSamplerDPS.py:94,200): only loss.name == "none" turns it off;
         # RIR_noise_regularization.use is never read there
+        from ...utils.losses import bind_slot, get_loss
         reg_loss = ps.RIR_noise_regularization.loss
-        from ...utils.losses import NORM_MODE
-        used = (ps.rec_loss, ps.rec_loss_params) + (() if reg_loss.name == "none" else (reg_loss,))
-        if any(hasattr(l, "loss_1") or l.name not in NORM_MODE for l in used):
-            raise NotImplementedError(f"the HIP operator's fused calls evaluate one member of {sorted(NORM_MODE)} (hybrids: through get_loss(...)(x, x_hat))")
-        comps, names = {float(l.compression_factor) for l in used}, {l.name for l in used}
-        if len(comps) != 1 or len(names) != 1 or not (0.0 < min(comps) <= 1.0):
-            raise NotImplementedError("the HIP operator's fused calls take ONE loss name and ONE compression factor in (0, 1] for the reconstruction, "
-                                      "parameter and regulariser terms (the shipped configs: l2_comp_stft_summean @ 0.667 for all three)")
-        self._loss_norm = NORM_MODE[names.pop()]
-        _lib.check(_lib.load().buddy_blindop_set_loss_norm(self._h, self._loss_norm))
-        self.set_compression(comps.pop())
+        blocks = ((0, "rec_loss", ps.rec_loss), (1, "rec_loss_params", ps.rec_loss_params), (2, "RIR_noise_regularization.loss", reg_loss))
+        specs = {}
+        for slot, key, l in blocks:
+            if hasattr(l, "loss_1"):
+                raise NotImplementedError(f"{key}: the HIP operator's fused calls evaluate one loss per term (hybrids: through get_loss(...)(x, x_hat))")
+            specs[slot] = get_loss(l)
+        if specs[0] is None:
+            raise NotImplementedError("rec_loss.name: none -- the likelihood needs a loss")
+        if not hasattr(self, "_fw_uploaded"):
+            self._fw_uploaded = set()
+        bind_slot(self._h, 0, specs[0], self._fw_uploaded)
+        bind_slot(self._h, 1, specs[1], self._fw_uploaded)          # "none": the operator fit drops the term (reference :87-91)
+        if specs[2] is not None:
+            bind_slot(self._h, 2, specs[2], self._fw_uploaded)
+        self._comp_created = specs[0].compression_factor
         self.w_rec = float(ps.rec_loss.get("weight", 1.0))
-        self.w_rec_params = float(ps.rec_loss_params.get("weight", 1.0))
+        self.w_rec_params = 0.0 if specs[1] is None else float(ps.rec_loss_params.get("weight", 1.0))
         self.w_reg = None if reg_loss.name == "none" else float(reg_loss.get("weight", 1.0))
         self.reg = ps.RIR_noise_regularization
         self.hp = ps.blind_hp

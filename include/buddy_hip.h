@@ -400,6 +400,19 @@ int buddy_blindop_set_compression(void* handle, float compression_factor);
 /* which member of the reference's compressed-spectrum family every loss entry of the handle evaluates (utils/losses.py:46-64):
  * 0 = l2_comp_stft_summean (default, the shipped configs), 1 = l2_comp_stft_sum, 2 = l2_comp_stft_mean */
 int buddy_blindop_set_loss_norm(void* handle, int mode);
+/* which loss each term of the handle evaluates (utils/losses.py:26-93), one descriptor per slot.  set_compression / set_loss_norm above set all slots.
+ *   slot  0 likelihood (rec_loss_grad, fir_loss_grad)     1 operator fit (rec_loss_params; param_grads, optimize)
+ *         2 RIR-noise regulariser (param_grads, optimize)  3 the callable buddy_blindop_stft_loss
+ *   kind  0 l2_comp_stft_summean  1 l2_comp_stft_sum  2 l2_comp_stft_mean  3 l2_stft_sum  4 l2_stft_mag_sum  5 l2_stft_logmag_sum
+ *         6 l2_log_stft_sum  7 l2_sum  8 l2_mean (time domain: on the signals themselves)  9 none (slot 1 only: the term is dropped)
+ *   freq_weighting  0 none  1 sqrt  2 exp  3 log  4 linear (STFT kinds only; the table must have been uploaded with set_freq_weights)
+ *   compression     (0, 1], read by kinds 0..2 only
+ * Kinds 0..2 without weighting run the same kernels as before this entry existed.  Changing slot 0 or 1 requires buddy_blindop_set_y again (the cached
+ * targets phi(w_f STFT(y)) / y depend on them); changing slots 0..2 drops the captured optimize graph.  Invalid arguments: BUDDY_ERR_ARG. */
+int buddy_blindop_set_loss(void* handle, int slot, int kind, int freq_weighting, float compression);
+/* per-bin weight table w[513] (host memory, float32) of freq_weighting 1..4: the reference's get_frequency_weighting(linspace(0, 1, 513) + 1);
+ * copied into the handle (synchronously) and kept */
+int buddy_blindop_set_freq_weights(void* handle, int freq_weighting, const float* w);
 int buddy_blindop_lengths(void* handle, int* L, int* L_rir, int* frames, int* frames_rir);
 int buddy_blindop_project(void* handle, void* stream);
 int buddy_blindop_get_adam(void* handle, float* m_decay, float* v_decay, float* m_weights, float* v_weights, float* m_phases, float* v_phases,
