@@ -25,6 +25,9 @@ _SIGS = {
     "buddy_ncsnpp_param_count": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
     "buddy_ncsnpp_create": (C.c_int, [_f32p, C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.POINTER(C.c_void_p)]),
+    "buddy_ncsnpp_param_count_attn": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
+    "buddy_ncsnpp_create_attn": (C.c_int, [_f32p, C.c_longlong, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.POINTER(C.c_void_p)]),
     "buddy_ncsnpp_destroy": (C.c_int, [C.c_void_p]),
     "buddy_ncsnpp_replica": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "buddy_ncsnpp_weight_bytes": (C.c_int, [C.c_void_p, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),

@@ -1,7 +1,7 @@
 // Single-head self-attention over all H*W positions without materialising the T x T matrix (gfx950, fp32 MFMA 16x16x4, wave64).
 // Replaces the three einsum / softmax steps of reference AttnBlockpp.forward (networks/ncsnpp_utils/layerspp.py:82-86):
 //     w = einsum('bchw,bcij->bhwij', q, k) * C^-0.5 ; w = softmax(w over ij) ; h = einsum('bhwij,bcij->bchw', w, v)
-// and their gradients.  q, k, v, O and all gradients are token-major [B][T][C] (NHWC activations flattened), C in {64, 128, 256}.
+// and their gradients.  q, k, v, O and all gradients are token-major [B][T][C] (NHWC activations flattened), C in {32, 64, 128, 256} (C = 32: its own kernels, below the others).
 //
 // Forward  (flash_fwd_kernel): a workgroup owns 64 query rows (4 waves x 16 rows), walks the keys / values in blocks of 32 staged through
 //   LDS; per block: S = q K^T (MFMA, q fragments live in registers), online softmax with the running row max / row sum kept per lane and
@@ -357,9 +357,289 @@ __global__ __launch_bounds__(256) void flash_bwd_dkv_kernel(const float* __restr
   }
 }
 
+
+// ---- head width C = 32 (the level-0 attention sites of the nf = 32 networks) -------------------------------------------------------------------
+// Not an instantiation of the kernels above: at C = 32 a 32-row block is 256 float4 (fetch32 would hold 0 per thread with 8 waves), and S = q K^T
+// has a K-depth of only 32 -- eight MFMAs per 16 x 16 tile against a row max, a row sum, 16 exponentials and an LDS round trip of P per lane and
+// block, so the loop is bound by issue and LDS, not by the matrix pipe.  Shape: 2 waves x 32 rows (two 16-row groups per wave) = 64 rows per
+// workgroup (the grid the split rule of flash_attn_splits assumes), keys / queries walked in blocks of 64.  Every K / V fragment read from LDS
+// feeds two MFMAs (one per row group), and each online-softmax step, barrier pair and staging round covers 64 keys instead of 32.  The loop-split
+// ranges are the same 32-row-block ranges as above (split_range); a 64-block that runs past `hi` masks the keys of the next split.
+constexpr int BK32 = 64, LD32 = 32 + 4, PL32 = BK32 + 4;
+// rows [r0, r0 + 64) of a [T][32] matrix -> registers (512 float4 over 128 threads) -> LDS [64][LD32]
+__device__ __forceinline__ void fetch64_c32(const float* __restrict__ src, int r0, int T, float4 (&r)[4]) {
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    const int i = threadIdx.x + 128 * n, row = i >> 3, c = (i & 7) * 4;
+    r[n] = ld4_row(src, r0 + row, T, 32, c);
+  }
+}
+__device__ __forceinline__ void put64_c32(const float4 (&r)[4], float* dst) {
+#pragma unroll
+  for (int n = 0; n < 4; ++n) {
+    const int i = threadIdx.x + 128 * n, row = i >> 3, c = (i & 7) * 4;
+    *reinterpret_cast<float4*>(dst + row * LD32 + c) = r[n];
+  }
+}
+// a[rg][kk]: this lane's A-operand row 16 rg + i of the wave, channels 16 kk + 4 g .. + 3
+__device__ __forceinline__ void load_rows_c32(const float* __restrict__ src, int rw, int T, int i, int g, float4 (&a)[2][2]) {
+#pragma unroll
+  for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) a[rg][kk] = ld4_row(src, rw + 16 * rg + i, T, 32, 16 * kk + 4 * g);
+}
+// acc[rg][t] (16 x 16) = sum_k A_rg[row][k] Bs[16 t + col][k], k < 32, t < 4: each B fragment read once for both row groups
+__device__ __forceinline__ void tile_abt_c32(const float4 (&a)[2][2], const float* Bs, int i, int g, f32x4 (&acc)[2][4]) {
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    const float av[2][4] = {{a[0][kk].x, a[0][kk].y, a[0][kk].z, a[0][kk].w}, {a[1][kk].x, a[1][kk].y, a[1][kk].z, a[1][kk].w}};
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const float4 b = *reinterpret_cast<const float4*>(Bs + (16 * t + i) * LD32 + 16 * kk + 4 * g);
+      const float bv[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0][j], bv[j], acc[0][t], 0, 0, 0);
+        acc[1][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1][j], bv[j], acc[1][t], 0, 0, 0);
+      }
+    }
+  }
+}
+// o[rg][c] += Ps[16 rg + row][k] Bs[k][16 c + col], k < 64; Ps is the wave's 32 x 64 tile (row stride PL32)
+__device__ __forceinline__ void tile_pb_c32(const float* Ps, const float* Bs, int i, int g, f32x4 (&o)[2][2]) {
+#pragma unroll
+  for (int h = 0; h < 4; ++h) {
+    const float4 p0 = *reinterpret_cast<const float4*>(Ps + i * PL32 + 16 * h + 4 * g);
+    const float4 p1 = *reinterpret_cast<const float4*>(Ps + (16 + i) * PL32 + 16 * h + 4 * g);
+    const float pv[2][4] = {{p0.x, p0.y, p0.z, p0.w}, {p1.x, p1.y, p1.z, p1.w}};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float* brow = Bs + (16 * h + 4 * g + j) * LD32 + i;
+      const float b0 = brow[0], b1 = brow[16];
+#pragma unroll
+      for (int rg = 0; rg < 2; ++rg) {
+        o[rg][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv[rg][j], b0, o[rg][0], 0, 0, 0);
+        o[rg][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv[rg][j], b1, o[rg][1], 0, 0, 0);
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(128) void flash_fwd_c32_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                            float* __restrict__ O, float* __restrict__ Lse, int T, float scale) {
+  __shared__ __attribute__((aligned(16))) float Ks[BK32 * LD32];
+  __shared__ __attribute__((aligned(16))) float Vs[BK32 * LD32];
+  __shared__ __attribute__((aligned(16))) float Ps[2][32 * PL32];
+  int jlo, jhi; split_range(T, jlo, jhi);
+  O += (long long)blockIdx.z * gridDim.y * T * 32; Lse += (long long)blockIdx.z * gridDim.y * T;
+  const int b = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
+  const long long base = (long long)b * T * 32;
+  const int rw = blockIdx.x * 64 + 32 * w;                   // first of this wave's 32 query rows
+  float4 qa[2][2];
+  load_rows_c32(q + base, rw, T, i, g, qa);
+  f32x4 o[2][2];
+  float m[2][4], l[2][4];
+#pragma unroll
+  for (int rg = 0; rg < 2; ++rg) {
+    o[rg][0] = zero_acc(); o[rg][1] = zero_acc();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { m[rg][r] = -INFINITY; l[rg][r] = 0.f; }
+  }
+  float4 pk[4], pv[4];
+  fetch64_c32(k + base, jlo, T, pk);
+  fetch64_c32(v + base, jlo, T, pv);
+  for (int j0 = jlo; j0 < jhi; j0 += BK32) {
+    __syncthreads();
+    put64_c32(pk, Ks);
+    put64_c32(pv, Vs);
+    __syncthreads();
+    if (j0 + BK32 < jhi) { fetch64_c32(k + base, j0 + BK32, T, pk); fetch64_c32(v + base, j0 + BK32, T, pv); }
+    f32x4 s[2][4];
+#pragma unroll
+    for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) s[rg][t] = zero_acc();
+    tile_abt_c32(qa, Ks, i, g, s);
+#pragma unroll
+    for (int rg = 0; rg < 2; ++rg) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float sv[4], mx = -INFINITY;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) { sv[t] = (j0 + 16 * t + i < jhi) ? s[rg][t][r] * scale : -INFINITY; mx = fmaxf(mx, sv[t]); }
+        const float mn = fmaxf(m[rg][r], row_max16(mx));    // finite: key j0 < jhi of every block is valid
+        const float alpha = expf(m[rg][r] - mn);
+        float sum = 0.f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const float e = expf(sv[t] - mn);
+          sum += e;
+          Ps[w][(16 * rg + 4 * g + r) * PL32 + 16 * t + i] = e;
+        }
+        l[rg][r] = l[rg][r] * alpha + row_sum16(sum);
+        m[rg][r] = mn;
+        o[rg][0][r] *= alpha; o[rg][1][r] *= alpha;
+      }
+    }
+    __syncthreads();
+    tile_pb_c32(Ps[w], Vs, i, g, o);
+  }
+#pragma unroll
+  for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = rw + 16 * rg + 4 * g + r;
+      if (row >= T) continue;
+      const float inv = 1.f / l[rg][r];
+      O[base + (long long)row * 32 + i] = o[rg][0][r] * inv;
+      O[base + (long long)row * 32 + 16 + i] = o[rg][1][r] * inv;
+      if (i == 0) Lse[(long long)b * T + row] = m[rg][r] + logf(l[rg][r]);
+    }
+}
+
+__global__ __launch_bounds__(128) void flash_bwd_dq_c32_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                               const float* __restrict__ dO, const float* __restrict__ Lse, const float* __restrict__ D,
+                                                               float* __restrict__ dq, int T, float scale) {
+  __shared__ __attribute__((aligned(16))) float Ks[BK32 * LD32];
+  __shared__ __attribute__((aligned(16))) float Vs[BK32 * LD32];
+  __shared__ __attribute__((aligned(16))) float Ps[2][32 * PL32];
+  int jlo, jhi; split_range(T, jlo, jhi);
+  dq += (long long)blockIdx.z * gridDim.y * T * 32;
+  const int b = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
+  const long long base = (long long)b * T * 32;
+  const int rw = blockIdx.x * 64 + 32 * w;
+  float4 qa[2][2], da[2][2];
+  load_rows_c32(q + base, rw, T, i, g, qa);
+  load_rows_c32(dO + base, rw, T, i, g, da);
+  float lse[2][4], dl[2][4];
+  f32x4 acc[2][2];
+#pragma unroll
+  for (int rg = 0; rg < 2; ++rg) {
+    acc[rg][0] = zero_acc(); acc[rg][1] = zero_acc();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      lse[rg][r] = ld1_row(Lse + (long long)b * T, rw + 16 * rg + 4 * g + r, T);
+      dl[rg][r] = ld1_row(D + (long long)b * T, rw + 16 * rg + 4 * g + r, T);
+    }
+  }
+  float4 pk[4], pv[4];
+  fetch64_c32(k + base, jlo, T, pk);
+  fetch64_c32(v + base, jlo, T, pv);
+  for (int j0 = jlo; j0 < jhi; j0 += BK32) {
+    __syncthreads();
+    put64_c32(pk, Ks);
+    put64_c32(pv, Vs);
+    __syncthreads();
+    if (j0 + BK32 < jhi) { fetch64_c32(k + base, j0 + BK32, T, pk); fetch64_c32(v + base, j0 + BK32, T, pv); }
+    f32x4 s[2][4], dp[2][4];
+#pragma unroll
+    for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) { s[rg][t] = zero_acc(); dp[rg][t] = zero_acc(); }
+    tile_abt_c32(qa, Ks, i, g, s);
+    tile_abt_c32(da, Vs, i, g, dp);
+#pragma unroll
+    for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const bool rok = rw + 16 * rg + 4 * g + r < T;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const float p = (rok && j0 + 16 * t + i < jhi) ? expf(s[rg][t][r] * scale - lse[rg][r]) : 0.f;
+          Ps[w][(16 * rg + 4 * g + r) * PL32 + 16 * t + i] = p * (dp[rg][t][r] - dl[rg][r]) * scale;
+        }
+      }
+    __syncthreads();
+    tile_pb_c32(Ps[w], Ks, i, g, acc);
+  }
+#pragma unroll
+  for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = rw + 16 * rg + 4 * g + r;
+      if (row >= T) continue;
+      dq[base + (long long)row * 32 + i] = acc[rg][0][r];
+      dq[base + (long long)row * 32 + 16 + i] = acc[rg][1][r];
+    }
+}
+
+__global__ __launch_bounds__(128) void flash_bwd_dkv_c32_kernel(const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v,
+                                                                const float* __restrict__ dO, const float* __restrict__ Lse, const float* __restrict__ D,
+                                                                float* __restrict__ dk, float* __restrict__ dv, int T, float scale) {
+  __shared__ __attribute__((aligned(16))) float Qs[BK32 * LD32];
+  __shared__ __attribute__((aligned(16))) float Os[BK32 * LD32];        // dO rows of the current query block
+  __shared__ __attribute__((aligned(16))) float Ps[2][32 * PL32];       // P^T, then dS^T, of the wave's 32 key rows
+  int ilo, ihi; split_range(T, ilo, ihi);                                // gridDim.z > 1: dk / dv are partial buffers [split][B][T][32]
+  dk += (long long)blockIdx.z * gridDim.y * T * 32; dv += (long long)blockIdx.z * gridDim.y * T * 32;
+  const int b = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
+  const long long base = (long long)b * T * 32;
+  const int rw = blockIdx.x * 64 + 32 * w;                               // key / value rows
+  float4 ka[2][2], va[2][2];
+  load_rows_c32(k + base, rw, T, i, g, ka);
+  load_rows_c32(v + base, rw, T, i, g, va);
+  f32x4 gk[2][2], gv[2][2];
+#pragma unroll
+  for (int rg = 0; rg < 2; ++rg) { gk[rg][0] = zero_acc(); gk[rg][1] = zero_acc(); gv[rg][0] = zero_acc(); gv[rg][1] = zero_acc(); }
+  float4 pq[4], po[4];
+  fetch64_c32(q + base, ilo, T, pq);
+  fetch64_c32(dO + base, ilo, T, po);
+  for (int i0 = ilo; i0 < ihi; i0 += BK32) {
+    __syncthreads();
+    put64_c32(pq, Qs);
+    put64_c32(po, Os);
+    __syncthreads();
+    if (i0 + BK32 < ihi) { fetch64_c32(q + base, i0 + BK32, T, pq); fetch64_c32(dO + base, i0 + BK32, T, po); }
+    f32x4 s[2][4], dp[2][4];
+#pragma unroll
+    for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+      for (int t = 0; t < 4; ++t) { s[rg][t] = zero_acc(); dp[rg][t] = zero_acc(); }
+    tile_abt_c32(ka, Qs, i, g, s);             // S^T[key row][query col]
+    tile_abt_c32(va, Os, i, g, dp);            // dP^T
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int qc = i0 + 16 * t + i;          // this lane's query column
+      const bool qok = qc < ihi;
+      const float lse = ld1_row(Lse + (long long)b * T, qc, T), dl = ld1_row(D + (long long)b * T, qc, T);
+#pragma unroll
+      for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float p = (qok && rw + 16 * rg + 4 * g + r < T) ? expf(s[rg][t][r] * scale - lse) : 0.f;
+          Ps[w][(16 * rg + 4 * g + r) * PL32 + 16 * t + i] = p;
+          dp[rg][t][r] = p * (dp[rg][t][r] - dl) * scale;                // dS^T, kept in registers until P^T has been used
+        }
+    }
+    __syncthreads();
+    tile_pb_c32(Ps[w], Os, i, g, gv);
+    __syncthreads();
+#pragma unroll
+    for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Ps[w][(16 * rg + 4 * g + r) * PL32 + 16 * t + i] = dp[rg][t][r];
+    __syncthreads();
+    tile_pb_c32(Ps[w], Qs, i, g, gk);
+  }
+#pragma unroll
+  for (int rg = 0; rg < 2; ++rg)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int row = rw + 16 * rg + 4 * g + r;
+      if (row >= T) continue;
+      dk[base + (long long)row * 32 + i] = gk[rg][0][r];
+      dk[base + (long long)row * 32 + 16 + i] = gk[rg][1][r];
+      dv[base + (long long)row * 32 + i] = gv[rg][0][r];
+      dv[base + (long long)row * 32 + 16 + i] = gv[rg][1][r];
+    }
+}
+
 }  // namespace
 
-bool flash_attn_supported(int C) { return C == 64 || C == 128 || C == 256; }
+// fp32 kernels: C in {32, 64, 128, 256}.  The 16-bit-operand kernels (attn16.hip) have no C = 32 form: flash_attn16_supported
+bool flash_attn_supported(int C) { return C == 32 || C == 64 || C == 128 || C == 256; }
+bool flash_attn16_supported(int C) { return C == 64 || C == 128 || C == 256; }
 
 // Loop splits of the fp32 kernels: a function of T ALONE -- what fills the chip for ONE utterance (cdiv(T, 64) workgroups per split, up to 256 in
 // all; at least four 32-row blocks per split, every split non-empty).  The count fixes the summation order of every row, so it must not depend on
@@ -394,10 +674,14 @@ void launch_flash_attn_fwd(const float* q, const float* k, const float* v, float
 #define FA_FWDS(CC)                                                                                              \
     hipLaunchKernelGGL((flash_fwd_kernel<CC, 4>), gs, block, 0, st, q, k, v, Op, Lp, T, scale);                    \
     hipLaunchKernelGGL(flash_combine_kernel<CC>, gc, block, 0, st, Op, Lp, O, Lse, rows, splits);
-    if (C == 64) { FA_FWDS(64) } else if (C == 128) { FA_FWDS(128) } else { FA_FWDS(256) }
+    if (C == 32) {
+      hipLaunchKernelGGL(flash_fwd_c32_kernel, gs, dim3(128), 0, st, q, k, v, Op, Lp, T, scale);
+      hipLaunchKernelGGL(flash_combine_kernel<32>, gc, block, 0, st, Op, Lp, O, Lse, rows, splits);
+    } else if (C == 64) { FA_FWDS(64) } else if (C == 128) { FA_FWDS(128) } else { FA_FWDS(256) }
 #undef FA_FWDS
     return;
   }
+  if (C == 32) { hipLaunchKernelGGL(flash_fwd_c32_kernel, grid, dim3(128), 0, st, q, k, v, O, Lse, T, scale); return; }
   // fp32: 128-row workgroups (8 waves) once there are enough of them to fill the chip, 64-row ones otherwise (BUDDY_ATTN_NW=4|8 forces one)
   const int force_nw = cur_opt().attn_nw;
   const bool wide = force_nw ? force_nw == 8 : (long long)cdiv(T, 128) * B >= 256;
@@ -426,7 +710,14 @@ void launch_flash_attn_bwd(const float* q, const float* k, const float* v, const
     hipLaunchKernelGGL(flash_bwd_dkv_kernel<CC>, gs, block, 0, st, q, k, v, dO, Lse, Dc, P0, P1, T, scale);        \
     hipLaunchKernelGGL(sum_parts_kernel, gr, block, 0, st, P0, dk, n4, splits);                                    \
     hipLaunchKernelGGL(sum_parts_kernel, gr, block, 0, st, P1, dv, n4, splits);
-    if (C == 64) { FA_BWDS(64) } else if (C == 128) { FA_BWDS(128) } else { FA_BWDS(256) }
+    if (C == 32) {
+      hipLaunchKernelGGL(attn_delta_kernel<32>, gd, block, 0, st, dO, O, D, rows);
+      hipLaunchKernelGGL(flash_bwd_dq_c32_kernel, gs, dim3(128), 0, st, q, k, v, dO, Lse, Dc, P0, T, scale);
+      hipLaunchKernelGGL(sum_parts_kernel, gr, block, 0, st, P0, dq, n4, splits);
+      hipLaunchKernelGGL(flash_bwd_dkv_c32_kernel, gs, dim3(128), 0, st, q, k, v, dO, Lse, Dc, P0, P1, T, scale);
+      hipLaunchKernelGGL(sum_parts_kernel, gr, block, 0, st, P0, dk, n4, splits);
+      hipLaunchKernelGGL(sum_parts_kernel, gr, block, 0, st, P1, dv, n4, splits);
+    } else if (C == 64) { FA_BWDS(64) } else if (C == 128) { FA_BWDS(128) } else { FA_BWDS(256) }
 #undef FA_BWDS
     return;
   }
@@ -434,7 +725,11 @@ void launch_flash_attn_bwd(const float* q, const float* k, const float* v, const
   hipLaunchKernelGGL(attn_delta_kernel<CC>, gd, block, 0, st, dO, O, D, rows);                                                 \
   hipLaunchKernelGGL(flash_bwd_dq_kernel<CC>, grid, block, 0, st, q, k, v, dO, Lse, Dc, dq, T, scale);                         \
   hipLaunchKernelGGL(flash_bwd_dkv_kernel<CC>, grid, block, 0, st, q, k, v, dO, Lse, Dc, dk, dv, T, scale);
-  if (C == 64) { FA_BWD(64) } else if (C == 128) { FA_BWD(128) } else { FA_BWD(256) }
+  if (C == 32) {
+    hipLaunchKernelGGL(attn_delta_kernel<32>, gd, block, 0, st, dO, O, D, rows);
+    hipLaunchKernelGGL(flash_bwd_dq_c32_kernel, grid, dim3(128), 0, st, q, k, v, dO, Lse, Dc, dq, T, scale);
+    hipLaunchKernelGGL(flash_bwd_dkv_c32_kernel, grid, dim3(128), 0, st, q, k, v, dO, Lse, Dc, dk, dv, T, scale);
+  } else if (C == 64) { FA_BWD(64) } else if (C == 128) { FA_BWD(128) } else { FA_BWD(256) }
 #undef FA_BWD
 }
 

@@ -27,9 +27,9 @@ static int finish() {
   return BUDDY_OK;
 }
 
-static NetCfg mk_cfg(int nf, const int* ch_mult, int nlev, int nrb, int n_fft, int hop) {
+static NetCfg mk_cfg(int nf, const int* ch_mult, int nlev, int nrb, int n_fft, int hop, int attn_mask = 0) {
   NetCfg c; std::memset(&c, 0, sizeof(c));
-  c.nf = nf; c.nlev = nlev; c.nrb = nrb; c.n_fft = n_fft; c.hop = hop;
+  c.nf = nf; c.nlev = nlev; c.nrb = nrb; c.n_fft = n_fft; c.hop = hop; c.attn_mask = attn_mask;
   for (int i = 0; i < nlev && i < 8; ++i) c.ch_mult[i] = ch_mult[i];
   return c;
 }
@@ -45,14 +45,26 @@ int buddy_ncsnpp_param_count(int nf, const int* ch_mult, int n_levels, int num_r
   return BUDDY_OK;
 }
 
-int buddy_ncsnpp_create(const float* host_params, long long n_params, int nf, const int* ch_mult, int n_levels, int num_res_blocks,
-                        int n_fft, int hop, void** handle) {
+int buddy_ncsnpp_param_count_attn(int nf, const int* ch_mult, int n_levels, int num_res_blocks, int attn_mask, long long* count) {
+  if (!ch_mult || !count || n_levels < 1 || n_levels > 8 || attn_mask < 0 || (attn_mask >> n_levels) != 0) { set_error("bad arguments"); return BUDDY_ERR_ARG; }
+  *count = param_count(mk_cfg(nf, ch_mult, n_levels, num_res_blocks, 510, 128, attn_mask));
+  return BUDDY_OK;
+}
+
+int buddy_ncsnpp_create_attn(const float* host_params, long long n_params, int nf, const int* ch_mult, int n_levels, int num_res_blocks,
+                             int n_fft, int hop, int attn_mask, void** handle) {
   if (!host_params || !ch_mult || !handle || n_levels < 1 || n_levels > 8 || nf % 32 != 0) { set_error("bad arguments (nf must be a multiple of 32)"); return BUDDY_ERR_ARG; }
+  if (attn_mask < 0 || (attn_mask >> n_levels) != 0) { set_error("attention mask selects a level the network does not have"); return BUDDY_ERR_ARG; }
   Net* N = nullptr;
-  int rc = net_create(host_params, n_params, mk_cfg(nf, ch_mult, n_levels, num_res_blocks, n_fft, hop), &N);
+  int rc = net_create(host_params, n_params, mk_cfg(nf, ch_mult, n_levels, num_res_blocks, n_fft, hop, attn_mask), &N);
   if (rc) return rc;
   *handle = N;
   return BUDDY_OK;
+}
+
+int buddy_ncsnpp_create(const float* host_params, long long n_params, int nf, const int* ch_mult, int n_levels, int num_res_blocks,
+                        int n_fft, int hop, void** handle) {
+  return buddy_ncsnpp_create_attn(host_params, n_params, nf, ch_mult, n_levels, num_res_blocks, n_fft, hop, 0, handle);
 }
 
 int buddy_ncsnpp_destroy(void* handle) { net_destroy((Net*)handle); return BUDDY_OK; }
@@ -518,15 +530,15 @@ int buddy_fir_resample2(const float* x, float* y, int B, int H, int W, int C, in
 int buddy_flash_attention_fwd(const float* q, const float* k, const float* v, float* O, float* lse, int B, int T, int C, float scale, int prec,
                               void* stream) {
   if (!q || !k || !v || !O || !lse || B < 1 || T < 1 || !flash_attn_supported(C) || prec != 0) {
-    set_error("bad attention arguments (C in {64, 128, 256}; prec 0 -- the 16-bit-operand kernels are buddy_flash_attention16_*)"); return BUDDY_ERR_ARG;
+    set_error("bad attention arguments (C in {32, 64, 128, 256}; prec 0 -- the 16-bit-operand kernels are buddy_flash_attention16_*)"); return BUDDY_ERR_ARG;
   }
   launch_flash_attn_fwd(q, k, v, O, lse, B, T, C, scale, nullptr, 1, (hipStream_t)stream);
   return finish();
 }
-long long buddy_flash_attention16_workspace(int B, int T, int C) { return (B < 1 || T < 1 || !flash_attn_supported(C)) ? 0 : flash_attn16_ws_floats(B, T, C); }
+long long buddy_flash_attention16_workspace(int B, int T, int C) { return (B < 1 || T < 1 || !flash_attn16_supported(C)) ? 0 : flash_attn16_ws_floats(B, T, C); }
 int buddy_flash_attention16_fwd(const float* q, const float* k, const float* v, float* O, float* lse, int B, int T, int C, float scale, int prec, float* ws,
                                 void* stream) {
-  if (!q || !k || !v || !O || !lse || !ws || B < 1 || T < 1 || !flash_attn_supported(C) || prec < 1 || prec > 2) {
+  if (!q || !k || !v || !O || !lse || !ws || B < 1 || T < 1 || !flash_attn16_supported(C) || prec < 1 || prec > 2) {
     set_error("bad attention arguments (C in {64, 128, 256}; prec 1 = bf16, 2 = f16; ws = buddy_flash_attention16_workspace floats)"); return BUDDY_ERR_ARG;
   }
   launch_flash_attn16_fwd(q, k, v, O, lse, B, T, C, scale, prec, ws, (hipStream_t)stream);
@@ -534,7 +546,7 @@ int buddy_flash_attention16_fwd(const float* q, const float* k, const float* v, 
 }
 int buddy_flash_attention16_bwd(const float* q, const float* k, const float* v, const float* O, const float* dO, const float* lse, float* delta, float* dq,
                                 float* dk, float* dv, int B, int T, int C, float scale, int prec, float* ws, void* stream) {
-  if (!q || !k || !v || !O || !dO || !lse || !delta || !dq || !dk || !dv || !ws || B < 1 || T < 1 || !flash_attn_supported(C) || prec < 1 || prec > 2) {
+  if (!q || !k || !v || !O || !dO || !lse || !delta || !dq || !dk || !dv || !ws || B < 1 || T < 1 || !flash_attn16_supported(C) || prec < 1 || prec > 2) {
     set_error("bad attention arguments (C in {64, 128, 256}; prec 1 = bf16, 2 = f16; ws = buddy_flash_attention16_workspace floats)"); return BUDDY_ERR_ARG;
   }
   launch_flash_attn16_bwd(q, k, v, O, dO, lse, delta, dq, dk, dv, B, T, C, scale, prec, ws, (hipStream_t)stream);
@@ -553,7 +565,7 @@ static bool split_args_ok(int T, int splits, const float* ws) {
 int buddy_flash_attention_fwd_split(const float* q, const float* k, const float* v, float* O, float* lse, int B, int T, int C, float scale, int splits,
                                     float* ws, void* stream) {
   if (!q || !k || !v || !O || !lse || B < 1 || T < 1 || !flash_attn_supported(C) || !split_args_ok(T, splits, ws)) {
-    set_error("bad split-attention arguments (C in {64, 128, 256}; every split needs at least one 32-row block)"); return BUDDY_ERR_ARG;
+    set_error("bad split-attention arguments (C in {32, 64, 128, 256}; every split needs at least one 32-row block)"); return BUDDY_ERR_ARG;
   }
   launch_flash_attn_fwd(q, k, v, O, lse, B, T, C, scale, ws, splits, (hipStream_t)stream);
   return finish();
@@ -561,7 +573,7 @@ int buddy_flash_attention_fwd_split(const float* q, const float* k, const float*
 int buddy_flash_attention_bwd_split(const float* q, const float* k, const float* v, const float* O, const float* dO, const float* lse, float* delta,
                                     float* dq, float* dk, float* dv, int B, int T, int C, float scale, int splits, float* ws, void* stream) {
   if (!q || !k || !v || !O || !dO || !lse || !delta || !dq || !dk || !dv || B < 1 || T < 1 || !flash_attn_supported(C) || !split_args_ok(T, splits, ws)) {
-    set_error("bad split-attention arguments (C in {64, 128, 256}; every split needs at least one 32-row block)"); return BUDDY_ERR_ARG;
+    set_error("bad split-attention arguments (C in {32, 64, 128, 256}; every split needs at least one 32-row block)"); return BUDDY_ERR_ARG;
   }
   launch_flash_attn_bwd(q, k, v, O, dO, lse, delta, dq, dk, dv, B, T, C, scale, ws, splits, (hipStream_t)stream);
   return finish();
@@ -569,7 +581,7 @@ int buddy_flash_attention_bwd_split(const float* q, const float* k, const float*
 int buddy_flash_attention_bwd(const float* q, const float* k, const float* v, const float* O, const float* dO, const float* lse, float* delta, float* dq,
                               float* dk, float* dv, int B, int T, int C, float scale, int prec, void* stream) {
   if (prec != 0 || !q || !k || !v || !O || !dO || !lse || !delta || !dq || !dk || !dv || B < 1 || T < 1 || !flash_attn_supported(C)) {
-    set_error("bad attention arguments (C in {64, 128, 256}; prec 0 -- the 16-bit-operand kernels are buddy_flash_attention16_*)"); return BUDDY_ERR_ARG;
+    set_error("bad attention arguments (C in {32, 64, 128, 256}; prec 0 -- the 16-bit-operand kernels are buddy_flash_attention16_*)"); return BUDDY_ERR_ARG;
   }
   launch_flash_attn_bwd(q, k, v, O, dO, lse, delta, dq, dk, dv, B, T, C, scale, nullptr, 1, (hipStream_t)stream);
   return finish();

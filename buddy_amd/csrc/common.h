@@ -181,7 +181,8 @@ void launch_fir_up2(const float* x, float* y, int B, int H, int W, int C, float 
 void launch_fir_down2(const float* x, float* y, int B, int H, int W, int C, float scale, int accumulate, hipStream_t st);
 void launch_pool2(const float* src, float* dst, int B, int H, int W, int C, float scale, int accumulate, hipStream_t st); // (H,W)->(H/2,W/2), sum*scale
 void launch_up2_acc(const float* src, float* dst, int B, int Hs, int Ws, int C, float scale, int accumulate, hipStream_t st); // (Hs,Ws)->(2Hs,2Ws)
-bool flash_attn_supported(int C);
+bool flash_attn_supported(int C);                                    // fp32 kernels: C in {32, 64, 128, 256}
+bool flash_attn16_supported(int C);                                  // 16-bit-operand kernels: C in {64, 128, 256}
 int flash_attn_splits(int B, int T);                                 // loop splits the launchers want for this grid (1 = none)
 long long flash_attn_ws_floats(int B, int T, int C, int splits);     // workspace floats of the split forms (0 for splits <= 1)
 void launch_flash_attn_fwd(const float* q, const float* k, const float* v, float* O, float* Lse, int B, int T, int C, float scale, float* ws, int splits,

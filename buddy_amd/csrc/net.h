@@ -5,7 +5,9 @@
 
 namespace buddy {
 
-struct NetCfg { int nf; int ch_mult[8]; int nlev; int nrb; int n_fft; int hop; };
+// attn_mask: bit l = an AttnBlock after every down ResnetBlock of level l and after the up ResnetBlocks of level l (reference ncsnpp.py:195-196,
+// 232-233: all_resolutions[l] in attn_resolutions); 0 = the bottleneck block only
+struct NetCfg { int nf; int ch_mult[8]; int nlev; int nrb; int n_fft; int hop; int attn_mask; };
 struct Net;
 
 void set_error(const std::string& s);

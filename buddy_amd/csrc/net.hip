@@ -55,10 +55,19 @@ static std::vector<PSpec> build_specs(const NetCfg& c) {
   add("weight", {nf * 4, nf * 2}); add("bias", {nf * 4}); ++idx;
   add("weight", {nf * 4, nf * 4}); add("bias", {nf * 4}); ++idx;
   add("weight", {nf, in_ch, 3, 3}); add("bias", {nf}); ++idx;
+  auto attnblock = [&](int C) {
+    add("GroupNorm_0.weight", {C}); add("GroupNorm_0.bias", {C});
+    for (int k = 0; k < 4; ++k) { add("NIN_" + std::to_string(k) + ".W", {C, C}); add("NIN_" + std::to_string(k) + ".b", {C}); }
+    ++idx;
+  };
   std::vector<int> hs_c{nf};
   int ch = nf;
   for (int l = 0; l < c.nlev; ++l) {
-    for (int b = 0; b < c.nrb; ++b) { int co = nf * c.ch_mult[l]; resblock(ch, co, false); ch = co; hs_c.push_back(ch); }
+    for (int b = 0; b < c.nrb; ++b) {
+      int co = nf * c.ch_mult[l]; resblock(ch, co, false); ch = co;
+      if (c.attn_mask >> l & 1) attnblock(ch);
+      hs_c.push_back(ch);
+    }
     if (l != c.nlev - 1) {
       resblock(ch, ch, true);
       add("Conv_0.weight", {ch, in_ch, 1, 1}); add("Conv_0.bias", {ch}); ++idx;
@@ -66,12 +75,11 @@ static std::vector<PSpec> build_specs(const NetCfg& c) {
     }
   }
   resblock(ch, ch, false);
-  add("GroupNorm_0.weight", {ch}); add("GroupNorm_0.bias", {ch});
-  for (int k = 0; k < 4; ++k) { add("NIN_" + std::to_string(k) + ".W", {ch, ch}); add("NIN_" + std::to_string(k) + ".b", {ch}); }
-  ++idx;
+  attnblock(ch);
   resblock(ch, ch, false);
   for (int l = c.nlev - 1; l >= 0; --l) {
     for (int b = 0; b < c.nrb + 1; ++b) { int co = nf * c.ch_mult[l]; resblock(ch + hs_c.back(), co, false); hs_c.pop_back(); ch = co; }
+    if (c.attn_mask >> l & 1) attnblock(ch);
     add("weight", {ch}); add("bias", {ch}); ++idx;
     add("weight", {in_ch, ch, 3, 3}); add("bias", {in_ch}); ++idx;
     if (l != 0) resblock(ch, ch, true);
@@ -117,7 +125,7 @@ struct ConvW { int cin = 0, cout = 0, taps = 0; const float* raw = nullptr; floa
                mutable WVar var[2][5]; };                      // [forward | data-gradient][direct, F(2x2), F(4x4), F(6x6), F(6x6) sub-pixel up form]
 struct GNW { float* gamma = nullptr; float* beta = nullptr; int C = 0; };
 struct ResW { GNW gn0, gn1; ConvW c0, c1, c2; bool has_c2 = false; int cin = 0, cout = 0, dense_off = 0; };
-struct AttnW { GNW gn; float* Wt[4]; float* Wn[4]; float* b[4]; int C = 0; };
+struct AttnW { GNW gn; float* Wt[4]; float* Wn[4]; float* b[4]; int C = 0; int level = -1; };   // level: the site's level (-1: the bottleneck block)
 
 struct W3Img { const void* img; int N, K; const void* img2 = nullptr; };      // img: bf16x3 stage image; img2: f16x2 stage image (general f16x2 form), where the shape allows
 // Everything derived from the parameters: shared (read-only after preparation) by a handle and its replicas (net_replica)
@@ -132,7 +140,8 @@ struct Weights {
   ConvW conv_in;                       // 2 -> nf (c2in fwd, c2out bwd)
   std::vector<ResW> res;               // in module order
   std::vector<ConvW> combine;          // 1x1 2 -> C
-  AttnW attn;
+  AttnW attn;                           // the bottleneck block
+  std::vector<AttnW> sites;            // the attention sites of cfg.attn_mask in module order (reserved up front: the NIN images are registered by address)
   std::vector<GNW> pyr_gn; std::vector<ConvW> pyr_conv;   // C -> 2 heads, top level first
   float* out_w = nullptr; float* out_b = nullptr;
   float* basisF = nullptr; float* basisI = nullptr;      // [2Fb][Kp], [Kp][2Fb]
@@ -230,6 +239,7 @@ static int weights_create(const float* hp, long long n, const NetCfg& cfg, std::
   N->specs = build_specs(cfg);
   if (n != param_count(cfg)) { set_error("parameter blob size mismatch"); return BUDDY_ERR_ARG; }
   if (cfg.n_fft % 2) { set_error("n_fft must be even"); return BUDDY_ERR_ARG; }
+  if (cfg.attn_mask < 0 || (cfg.attn_mask >> cfg.nlev) != 0) { set_error("attention mask selects a level the network does not have"); return BUDDY_ERR_ARG; }
   {  // the GroupNorm partial-sum scratch is sized for at most 1024 channels; the widest tensor is a skip concatenation (2 x the level width)
     int cmax = 0;
     for (int l = 0; l < cfg.nlev; ++l) cmax = std::max(cmax, cfg.nf * cfg.ch_mult[l]);
@@ -323,10 +333,31 @@ static int weights_create(const float* hp, long long n, const NetCfg& cfg, std::
     packed(&N->conv_in.wf, f); packed(&N->conv_in.wb, b);
     ++idx;
   }
+  // AttnBlock: GroupNorm_0, NIN_0..3 (q, k, v, output projection; layerspp.py:70-80)
+  auto load_attn = [&](AttnW& a, int C, int level) {
+    a.C = C; a.level = level;
+    const std::string p = pre();
+    load_gn(a.gn, p + "GroupNorm_0", C);
+    for (int k = 0; k < 4; ++k) {
+      a.Wn[k] = raw(p + "NIN_" + std::to_string(k) + ".W"); a.b[k] = raw(p + "NIN_" + std::to_string(k) + ".b");
+      packed(&a.Wt[k], transpose2(host(p + "NIN_" + std::to_string(k) + ".W"), C, C));
+      plain3.push_back({&a.Wt[k], {C, C}}); plain3.push_back({&a.Wn[k], {C, C}});
+    }
+    ++idx;
+  };
+  {
+    int n_sites = 0;
+    for (int l = 0; l < cfg.nlev; ++l) if (cfg.attn_mask >> l & 1) n_sites += cfg.nrb + 1;
+    N->sites.reserve(n_sites);
+  }
   std::vector<int> hs_c{nf};
   int ch = nf;
   for (int l = 0; l < cfg.nlev; ++l) {
-    for (int b = 0; b < cfg.nrb; ++b) { int co = nf * cfg.ch_mult[l]; load_res(ch, co, false); ch = co; hs_c.push_back(ch); }
+    for (int b = 0; b < cfg.nrb; ++b) {
+      int co = nf * cfg.ch_mult[l]; load_res(ch, co, false); ch = co;
+      if (cfg.attn_mask >> l & 1) { N->sites.emplace_back(); load_attn(N->sites.back(), ch, l); }
+      hs_c.push_back(ch);
+    }
     if (l != cfg.nlev - 1) {
       load_res(ch, ch, true);
       ConvW c; c.cin = 2; c.cout = ch; c.taps = 1; c.bias = raw(pre() + "Conv_0.bias");
@@ -336,21 +367,12 @@ static int weights_create(const float* hp, long long n, const NetCfg& cfg, std::
     }
   }
   load_res(ch, ch, false);
-  {
-    AttnW& a = N->attn; a.C = ch;
-    const std::string p = pre();
-    load_gn(a.gn, p + "GroupNorm_0", ch);
-    for (int k = 0; k < 4; ++k) {
-      a.Wn[k] = raw(p + "NIN_" + std::to_string(k) + ".W"); a.b[k] = raw(p + "NIN_" + std::to_string(k) + ".b");
-      packed(&a.Wt[k], transpose2(host(p + "NIN_" + std::to_string(k) + ".W"), ch, ch));
-      plain3.push_back({&a.Wt[k], {ch, ch}}); plain3.push_back({&a.Wn[k], {ch, ch}});
-    }
-    ++idx;
-  }
+  load_attn(N->attn, ch, -1);
   load_res(ch, ch, false);
   N->pyr_gn.resize(cfg.nlev); N->pyr_conv.resize(cfg.nlev);
   for (int l = cfg.nlev - 1, j = 0; l >= 0; --l, ++j) {
     for (int b = 0; b < cfg.nrb + 1; ++b) { int co = nf * cfg.ch_mult[l]; load_res(ch + hs_c.back(), co, false); hs_c.pop_back(); ch = co; }
+    if (cfg.attn_mask >> l & 1) { N->sites.emplace_back(); load_attn(N->sites.back(), ch, l); }
     load_gn(N->pyr_gn[j], "all_modules." + std::to_string(idx), ch); ++idx;
     {
       const float* w = host(pre() + "weight");   // [2][ch][3][3]
@@ -925,7 +947,8 @@ static bool attn_use_flash(const Net* N, int C, int T) {
   if (!flash_attn_supported(C) || N->opt.attn == 3) return false;
   return N->opt.attn != 4 || T > ATTN_MATRIX_MAX_T;
 }
-static int attn_prec(const Net* N) { return N->opt.attn == 1 || N->opt.attn == 2 ? N->opt.attn : 0; }
+// 16-bit operands where attn16.hip has a kernel for C; a C = 32 site runs the fp32 flash kernels in every mode
+static int attn_prec(const Net* N, int C) { return (N->opt.attn == 1 || N->opt.attn == 2) && flash_attn16_supported(C) ? N->opt.attn : 0; }
 
 static Tens* attnblock_flash(Net* N, const AttnW& A, Tens* x, bool rec) {
   const int B = x->B, H = x->H, W = x->W, C = A.C, T = H * W, G = gn_groups(C);
@@ -940,7 +963,7 @@ static Tens* attnblock_flash(Net* N, const AttnW& A, Tens* x, bool rec) {
   float* hn = N->tmp(BTC);
   // few utterances: the kernels' sequential loops are split over more workgroups (attn.hip: split_range); workspace from the arena
   // 16-bit modes: the operand arrays of the pre-pass (attn16.hip) live in the same scratch
-  const int prec = attn_prec(N);
+  const int prec = attn_prec(N, C);
   const int splits = prec ? 1 : flash_attn_splits(B, T);
   float* aws = prec ? N->tmp(flash_attn16_ws_floats(B, T, C)) : splits > 1 ? N->tmp(flash_attn_ws_floats(B, T, C, splits)) : nullptr;
   if (!N->dry()) {
@@ -965,7 +988,7 @@ static Tens* attnblock_flash(Net* N, const AttnW& A, Tens* x, bool rec) {
       const float* dout = out->g;
       float* dO = n->tmp(BTC); float* dq = n->tmp(BTC); float* dk = n->tmp(BTC); float* dv = n->tmp(BTC); float* dhn = n->tmp(BTC);
       float* dl = n->tmp((long long)B * T);
-      const int bprec = attn_prec(n);
+      const int bprec = attn_prec(n, C);
       const int bsplits = bprec ? 1 : flash_attn_splits(B, T);
       float* bws = bprec ? n->tmp(flash_attn16_ws_floats(B, T, C)) : bsplits > 1 ? n->tmp(flash_attn_ws_floats(B, T, C, bsplits)) : nullptr;
       gemm_b(n, dout, C, 0, false, Ap->Wn[3], C, 0, false, dO, C, 0, B * T, C, C, nullptr, nullptr, INV_SQRT2, 0, 1);
@@ -1124,7 +1147,7 @@ static void run_forward(Net* N, const float* x, const float* cnoise, const float
     launch_linear(temb, N->W->dense_w, N->W->dense_b, temb_all, B, 4 * nf, N->W->dense_total, 1, st);
   }
 
-  int mi = 3, ri = 0, ci = 0;
+  int mi = 3, ri = 0, ci = 0, si = 0;
   auto tap = [&](int idx, Tens* t) { N->taps.push_back({idx, t}); };
   // input conv
   Tens* h0 = N->mk(B, Tp, Fb, nf, rec);
@@ -1141,6 +1164,9 @@ static void run_forward(Net* N, const float* x, const float* cnoise, const float
     for (int b = 0; b < c.nrb; ++b) {
       View v; v.a = hs.back();
       Tens* h = resblock(N, N->W->res[ri++], v, 0, temb_all, rec); tap(mi, h); ++mi;
+      // attention site (reference ncsnpp.py:340-344): the skip stack gets the block's output.  Its output tensor carries no GroupNorm sums, so
+      // the next GroupNorm (next ResnetBlock, skip concatenation) runs its own reduction pass
+      if (c.attn_mask >> l & 1) { h = attnblock(N, N->W->sites[si++], h, rec); tap(mi, h); ++mi; }
       hs.push_back(h);
     }
     if (l != c.nlev - 1) {
@@ -1184,6 +1210,7 @@ static void run_forward(Net* N, const float* x, const float* cnoise, const float
       View v; v.a = h; v.b = hs.back(); hs.pop_back();
       h = resblock(N, N->W->res[ri++], v, 0, temb_all, rec); tap(mi, h); ++mi;
     }
+    if (c.attn_mask >> l & 1) { h = attnblock(N, N->W->sites[si++], h, rec); tap(mi, h); ++mi; }   // reference ncsnpp.py:386-389
     {  // pyramid head: GroupNorm -> SiLU -> conv3x3 C->2, plus nearest-upsampled previous pyramid (ncsnpp.py:391-412)
       const GNW& gw = N->W->pyr_gn[j]; const ConvW& cw = N->W->pyr_conv[j];
       const int C = h->C, G = gn_groups(C), Hh = h->H, Ww = h->W;
@@ -1256,7 +1283,23 @@ static void run_vjp(Net* N, const float* cot, float* gx) {
   N->arena.off = mark;
 }
 
+// An attention site whose width has no flash kernel (e.g. C = 512) would materialise B x T x T floats: refused beyond ATTN_MATRIX_MAX_T tokens.  The
+// bottleneck block keeps its old behaviour.
+static int check_sites(const Net* N, int L) {
+  const int Tp = (1 + L / N->cfg.hop + 15) / 16 * 16;
+  for (const AttnW& a : N->W->sites) {
+    const long long T = (long long)(Tp >> a.level) * (N->Fb >> a.level);
+    if (!flash_attn_supported(a.C) && T > ATTN_MATRIX_MAX_T) {
+      set_error("attention at level " + std::to_string(a.level) + ": C = " + std::to_string(a.C) + " has no flash kernel (C in {32, 64, 128, 256}) and T = " +
+                std::to_string(T) + " tokens exceeds the materialised form's limit of " + std::to_string(ATTN_MATRIX_MAX_T));
+      return BUDDY_ERR_ARG;
+    }
+  }
+  return BUDDY_OK;
+}
+
 int net_reserve(Net* N, int B, int L, int with_vjp, long long* bytes) {
+  if (int rc = check_sites(N, L)) return rc;
   OptScope scope(&N->opt);
   Arena saved = N->arena;
   N->w4_need = 0;

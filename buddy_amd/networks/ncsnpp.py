@@ -5,7 +5,8 @@ Same surface as the reference class: constructor kwargs = ``conf/network/ncsnpp.
 ``stft:{n_fft,hop_length,center}``), ``nn.Module`` protocol with the reference ``state_dict`` key names
 (``all_modules.N.*``, ``output_layer.*``), ``forward(x:(B,1,L) f32, time_cond:(B,) f32) -> (B,1,L)``,
 differentiable w.r.t. ``x`` (the input-VJP runs in HIP; no weight gradients -- inference only).
-Only the shipped architecture family is supported (biggan resblocks, input_skip/sum, output_skip, one bottleneck attention;
+Only the shipped architecture family is supported (biggan resblocks, input_skip/sum, output_skip, the bottleneck attention plus the
+attention sites of ``attn_resolutions``;
 ``fir`` False or True with the (1,3,3,1) kernel); anything else raises ``NotImplementedError`` at construction.
 """
 from __future__ import annotations
@@ -18,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..synth import module_specs
+from ..synth import attn_mask_of, module_specs
 
 
 class _Bag(nn.Module):
@@ -94,14 +95,24 @@ class NCSNppTime(nn.Module):
         if input_channels != 2 or spatial_channels != 1: unsupported.append("channels")
         if not time_conditional or discriminative or not centered or dropout not in (0, 0.0):
             unsupported.append("time_conditional/discriminative/centered/dropout")
-        res = [image_size // (2 ** i) for i in range(len(ch_mult))]
-        if any(r in tuple(attn_resolutions) for r in res): unsupported.append("attn_resolutions")
         if nf % 32: unsupported.append("nf % 32")
         if unsupported:
             raise NotImplementedError("NCSNppTime (MI355X): unsupported options: " + ", ".join(unsupported))
         get = (lambda k: stft[k]) if isinstance(stft, dict) else (lambda k: getattr(stft, k))
         self.stft_kwargs = stft
         self.n_fft, self.hop_length = int(get("n_fft")), int(get("hop_length"))
+        # attention sites: the reference BUILDS an AttnBlock where image_size // 2^l is in attn_resolutions (ncsnpp.py:195, 232) and RUNS one where the
+        # tensor height -- the frequency bins F >> l -- is (:340, :387).  Where the two tests disagree its module index goes out of step: refused.
+        R = tuple(int(r) for r in attn_resolutions)
+        bins = self.n_fft // 2 + 1
+        for lvl in range(len(ch_mult)):
+            built, run = (int(image_size) >> lvl) in R, (bins >> lvl) in R
+            if built != run:
+                raise NotImplementedError(f"NCSNppTime (MI355X): attn_resolutions={list(R)} selects level {lvl} for image_size={image_size} "
+                                          f"(resolution {int(image_size) >> lvl}: {'built' if built else 'not built'}) but not for the {bins} frequency "
+                                          f"bins of n_fft={self.n_fft} (height {bins >> lvl}: {'run' if run else 'not run'}); the reference would "
+                                          "build and run different attention blocks")
+        self.attn_mask = attn_mask_of(R, image_size, len(ch_mult))
         assert bool(get("center")), "center=False not supported"
         self.nf, self.ch_mult, self.num_res_blocks = int(nf), tuple(int(c) for c in ch_mult), int(num_res_blocks)
         # attention core: None = library default (BUDDY_ATTN, else "auto": fp32, materialised while T <= 4096, flash beyond); "auto" | "flash" | "bf16" | "f16" | "matrix" (build extension, not a reference key:
@@ -116,7 +127,7 @@ class NCSNppTime(nn.Module):
         self.gemm = gemm
         self._options = {}              # per-handle launcher options set through set_option (build extension; keys: include/buddy_hip.h)
         self.fir = bool(fir)            # FIR (1,3,3,1) resampling instead of nearest / box (reference up_or_down_sampling.py:195-257); no parameters
-        self._specs = module_specs(self.nf, self.ch_mult, self.num_res_blocks)
+        self._specs = module_specs(self.nf, self.ch_mult, self.num_res_blocks, attn_mask=self.attn_mask)
         # The architecture family (reference ncsnpp.py:184-270) is built for any level / block count (fixtures net_cm12_rb2, net_cm1122_rb1), with one
         # restriction of the GroupNorm kernels: they normalise float4 channel quads with one group's statistics, so every normalised tensor -- skip
         # concatenations included -- needs a multiple of 4 channels per group: C <= 128 or C % 128 == 0 (min(C // 4, 32) groups).  nf = 32 / 128 with the
@@ -186,8 +197,12 @@ class NCSNppTime(nn.Module):
             blob = np.ascontiguousarray(self._flat_params())
             cm = (C.c_int * len(self.ch_mult))(*self.ch_mult)
             h = C.c_void_p()
-            _lib.check(lib.buddy_ncsnpp_create(blob.ctypes.data, blob.size, self.nf, cm, len(self.ch_mult),
-                                               self.num_res_blocks, self.n_fft, self.hop_length, C.byref(h)))
+            if self.attn_mask:
+                _lib.check(lib.buddy_ncsnpp_create_attn(blob.ctypes.data, blob.size, self.nf, cm, len(self.ch_mult), self.num_res_blocks,
+                                                        self.n_fft, self.hop_length, self.attn_mask, C.byref(h)))
+            else:
+                _lib.check(lib.buddy_ncsnpp_create(blob.ctypes.data, blob.size, self.nf, cm, len(self.ch_mult),
+                                                   self.num_res_blocks, self.n_fft, self.hop_length, C.byref(h)))
             if self.fir:
                 _lib.check(lib.buddy_ncsnpp_set_fir(h, 1))
             if self.attention is not None:

@@ -12,10 +12,12 @@ from __future__ import annotations
 import numpy as np
 
 
-def module_specs(nf=128, ch_mult=(1, 2, 2, 2), num_res_blocks=1, in_ch=2):
+def module_specs(nf=128, ch_mult=(1, 2, 2, 2), num_res_blocks=1, in_ch=2, attn_mask=0):
     """Ordered (name, shape, kind, fan_in) list for the shipped architecture family
-    (biggan resblocks, input_skip/sum, output_skip, one bottleneck attention;
-    construction order = reference ``networks/ncsnpp.py:157-274``)."""
+    (biggan resblocks, input_skip/sum, output_skip, the bottleneck attention;
+    construction order = reference ``networks/ncsnpp.py:157-274``).  ``attn_mask`` bit l: an AttnBlock after every
+    down ResnetBlock of level l and after the up ResnetBlocks of level l (reference ``:195-196, 232-233``); 0 = the
+    bottleneck block only."""
     specs = []
     idx = [0]
 
@@ -39,6 +41,12 @@ def module_specs(nf=128, ch_mult=(1, 2, 2, 2), num_res_blocks=1, in_ch=2):
     add("weight", (nf * 4, nf * 2), "w", nf * 2); add("bias", (nf * 4,), "b"); nxt()
     add("weight", (nf * 4, nf * 4), "w", nf * 4); add("bias", (nf * 4,), "b"); nxt()
     add("weight", (nf, in_ch, 3, 3), "w", in_ch * 9); add("bias", (nf,), "b"); nxt()
+    def attnblock(c):
+        add("GroupNorm_0.weight", (c,), "gamma"); add("GroupNorm_0.bias", (c,), "beta")
+        for k in range(4):
+            add(f"NIN_{k}.W", (c, c), "w", c); add(f"NIN_{k}.b", (c,), "b")
+        nxt()
+
     hs_c = [nf]
     c = nf
     nres = len(ch_mult)
@@ -46,21 +54,22 @@ def module_specs(nf=128, ch_mult=(1, 2, 2, 2), num_res_blocks=1, in_ch=2):
         for _ in range(num_res_blocks):
             co = nf * ch_mult[lvl]
             resblock(c, co); c = co
+            if attn_mask >> lvl & 1:
+                attnblock(c)
             hs_c.append(c)
         if lvl != nres - 1:
             resblock(c, c, resample=True)
             add("Conv_0.weight", (c, in_ch, 1, 1), "w", in_ch); add("Conv_0.bias", (c,), "b"); nxt()
             hs_c.append(c)
     resblock(c, c)
-    add("GroupNorm_0.weight", (c,), "gamma"); add("GroupNorm_0.bias", (c,), "beta")
-    for k in range(4):
-        add(f"NIN_{k}.W", (c, c), "w", c); add(f"NIN_{k}.b", (c,), "b")
-    nxt()
+    attnblock(c)
     resblock(c, c)
     for lvl in reversed(range(nres)):
         for _ in range(num_res_blocks + 1):
             co = nf * ch_mult[lvl]
             resblock(c + hs_c.pop(), co); c = co
+        if attn_mask >> lvl & 1:
+            attnblock(c)
         add("weight", (c,), "gamma"); add("bias", (c,), "beta"); nxt()
         add("weight", (in_ch, c, 3, 3), "w", c * 9); add("bias", (in_ch,), "b"); nxt()
         if lvl != 0:
@@ -71,11 +80,11 @@ def module_specs(nf=128, ch_mult=(1, 2, 2, 2), num_res_blocks=1, in_ch=2):
     return specs
 
 
-def synth_state_dict(seed=0, nf=128, ch_mult=(1, 2, 2, 2), num_res_blocks=1, fourier_scale=16.0):
-    """Deterministic float32 weights keyed by reference state-dict names (numpy arrays)."""
+def synth_state_dict(seed=0, nf=128, ch_mult=(1, 2, 2, 2), num_res_blocks=1, fourier_scale=16.0, attn_mask=0):
+    """Deterministic float32 weights keyed by reference state-dict names (numpy arrays); ``attn_mask`` as in ``module_specs``."""
     rs = np.random.RandomState(seed)
     sd = {}
-    for name, shape, kind, fan_in in module_specs(nf, ch_mult, num_res_blocks):
+    for name, shape, kind, fan_in in module_specs(nf, ch_mult, num_res_blocks, attn_mask=attn_mask):
         if kind == "w":
             a = rs.standard_normal(shape) / np.sqrt(fan_in)
         elif kind == "b":
@@ -121,3 +130,10 @@ def synth_noise(utt_id, n_draws, length):
     from the torch CPU generator, ``testing/EulerHeunSampler.py:21,43``)."""
     rs = np.random.RandomState(777 + utt_id)
     return rs.standard_normal((n_draws, length)).astype(np.float32)
+
+
+def attn_mask_of(attn_resolutions, image_size, n_levels):
+    """Level mask of the attention sites the reference builds: bit l set when ``image_size // 2**l in attn_resolutions``
+    (reference ``networks/ncsnpp.py:133,195``)."""
+    res = {int(r) for r in attn_resolutions}
+    return sum(1 << lvl for lvl in range(n_levels) if int(image_size) // (2 ** lvl) in res)

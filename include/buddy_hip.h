@@ -32,6 +32,15 @@ int buddy_ncsnpp_param_count(int nf, const int* ch_mult, int n_levels, int num_r
  * state dict, test.py:60-75; this is the library side of NCSNppTime.load_state_dict + .to(device).) */
 int buddy_ncsnpp_create(const float* host_params, long long n_params, int nf, const int* ch_mult, int n_levels,
                         int num_res_blocks, int n_fft, int hop, void** handle);
+/* The same two entries for a network with attention sites (reference networks/ncsnpp.py:195-196, 232-233): bit l of attn_mask = an AttnBlock after
+ * every down ResnetBlock of level l and one after the up ResnetBlocks of level l (NCSNppTime derives it from attn_resolutions:
+ * image_size // 2^l in attn_resolutions).  Its parameters (GroupNorm_0.*, NIN_0..3.*) take their places in the blob in module order and shift the
+ * all_modules.N indices after them.  attn_mask = 0 is buddy_ncsnpp_param_count / buddy_ncsnpp_create.  A site runs the attention core of the handle
+ * (buddy_ncsnpp_set_attention); a C = 32 site has no 16-bit kernel and runs the fp32 flash kernels in the bf16 / f16 modes too.  A forward whose
+ * site has a width without a flash kernel (C not in {32, 64, 128, 256}) and more than 4096 tokens fails with BUDDY_ERR_ARG. */
+int buddy_ncsnpp_param_count_attn(int nf, const int* ch_mult, int n_levels, int num_res_blocks, int attn_mask, long long* count);
+int buddy_ncsnpp_create_attn(const float* host_params, long long n_params, int nf, const int* ch_mult, int n_levels,
+                             int num_res_blocks, int n_fft, int hop, int attn_mask, void** handle);
 int buddy_ncsnpp_destroy(void* handle);
 /* a second handle on the SAME prepared weights (reference-counted, read-only): own activation arena, VJP tape and attention / gemm / fir
  * settings (copied from `handle`).  For concurrent sub-batches on several streams; no reference counterpart (testing/tester.py:132-153 samples
@@ -290,14 +299,14 @@ int buddy_ncsnpp_set_attention(void* handle, int mode);
  * Env BUDDY_GEMM=fp32|bf16x3|f16x2|f16 sets the process default. */
 int buddy_ncsnpp_set_gemm(void* handle, int mode);
 
-/* single-head attention over T tokens without the T x T matrix (online softmax, fp32 MFMA), token-major q, k, v, O [B][T][C], C in {64,128,256}:
+/* single-head attention over T tokens without the T x T matrix (online softmax, fp32 MFMA), token-major q, k, v, O [B][T][C], C in {32,64,128,256}:
  * O = softmax(scale * q k^T) v, lse [B][T] = row log-sum-exp; replaces the einsum / softmax / einsum of AttnBlockpp.forward
  * (networks/ncsnpp_utils/layerspp.py:82-86).  bwd: gradients of the same three steps given dO (delta [B][T] is scratch).
  * prec must be 0 (fp32 operands, the reference arithmetic); the 16-bit-operand kernels take a workspace and are the next three entries. */
 int buddy_flash_attention_fwd(const float* q, const float* k, const float* v, float* O, float* lse, int B, int T, int C, float scale, int prec, void* stream);
 int buddy_flash_attention_bwd(const float* q, const float* k, const float* v, const float* O, const float* dO, const float* lse, float* delta,
                               float* dq, float* dk, float* dv, int B, int T, int C, float scale, int prec, void* stream);
-/* The same three steps with 16-bit MFMA operands (prec 1 = bf16, 2 = f16; v_mfma_f32_32x32x16_*), fp32 accumulation and fp32 softmax statistics --
+/* The same three steps with 16-bit MFMA operands, C in {64,128,256} only (C = 32: the fp32 entries) (prec 1 = bf16, 2 = f16; v_mfma_f32_32x32x16_*), fp32 accumulation and fp32 softmax statistics --
  * the opt-in fast mode of buddy_ncsnpp_set_attention(handle, 1 | 2) (BASELINE configs[4] "fp16 MFMA attention path"; not the reference's arithmetic).
  * A pre-pass converts q (times scale log2 e), k, v, dO once into 16-bit operand arrays in `ws` (buddy_flash_attention16_workspace floats: token-major
  * rows and channel-major transposes, T padded to 128); the kernels stream them through LDS by DMA and keep the softmax in registers (csrc/attn16.hip). */
