@@ -36,6 +36,8 @@ _SIGS = {
     "buddy_ncsnpp_reserve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_longlong)]),
     "buddy_ncsnpp_forward": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "buddy_ncsnpp_vjp": (C.c_int, [C.c_void_p, _f32p, _f32p, C.c_void_p]),
+    "buddy_ncsnpp_vjp_params": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_int, C.c_void_p]),
+    "buddy_ncsnpp_update_params": (C.c_int, [C.c_void_p, _f32p, C.c_void_p]),
     "buddy_ncsnpp_tap": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int * 4)]),
     "buddy_prof_enable": (C.c_int, [C.c_int]),
     "buddy_wpe": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -106,6 +106,16 @@ int buddy_ncsnpp_vjp(void* handle, const float* cot, float* grad_x, void* stream
   return net_vjp((Net*)handle, cot, grad_x, (hipStream_t)stream);
 }
 
+int buddy_ncsnpp_vjp_params(void* handle, const float* cot, float* grad_x, float* grad_params, int accumulate, void* stream) {
+  if (!handle || !cot || !grad_params) { set_error("null argument"); return BUDDY_ERR_ARG; }
+  return net_vjp_params((Net*)handle, cot, grad_x, grad_params, accumulate, (hipStream_t)stream);
+}
+
+int buddy_ncsnpp_update_params(void* handle, const float* dev_params, void* stream) {
+  if (!handle || !dev_params) { set_error("null argument"); return BUDDY_ERR_ARG; }
+  return net_update_params((Net*)handle, dev_params, (hipStream_t)stream);
+}
+
 int buddy_ncsnpp_tap(void* handle, int module_idx, const float** ptr, int dims[4]) {
   if (!handle || !ptr || !dims) { set_error("null argument"); return BUDDY_ERR_ARG; }
   return net_get_tap((Net*)handle, module_idx, ptr, dims);

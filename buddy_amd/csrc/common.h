@@ -212,4 +212,22 @@ void launch_unpad_adj(const float* dframes, int ldF, int T, int n_fft, int hop, 
 
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
+// ---- parameter gradients (wgrad.hip) ----------------------------------------------------------------------
+// dY[m][n] = p[(m / T) * sb + (m % T) * sm + n * sn]: an NHWC gradient (T = M, sm = ld, sn = 1) or a per-utterance transposed one
+struct WgY { const float* p; long long T, sb, sm, sn; };
+// A[m][k], k = tap * Cin + c, on the (H, W) grid of the convolution's output: act(GroupNorm(x)) (stats null: x itself), x at (H, W) (rs 0),
+// at (2H, 2W) averaged over 2 x 2 (rs 1: box downsample) or at (H/2, W/2) (rs 2: nearest upsample); taps 9 = the zero-padded 3 x 3 neighbourhood
+struct WgA { Src2 x; int H, W, Cin, taps, rs; const float* stats; const float* gamma; const float* beta; int G, silu; };
+int wgrad_chunks(long long M, int N, int K);
+long long wgrad_ws_floats(long long M, int N, int K);
+// out (+)= alpha * sum_m dY[m][n] A[m][k] in layout 0 [N][K], 1 torch OIHW of a 3x3 conv (N = O, K = 9 I), 2 [K][N]; ws: wgrad_ws_floats
+void launch_wgrad(const WgY& y, const WgA& a, long long M, int N, int layout, float alpha, float* ws, float* out, hipStream_t st);
+long long colsum_ws_floats(int B, long long T, int N);
+void launch_colsum(const WgY& y, int B, int N, float alpha, float* ws, float* bc, int ld_bc, float* out, float* out2, hipStream_t st);
+long long gn_pgrad_ws_floats(int B, int H, int W, int C);
+void launch_gn_pgrad(const Src2& x, const float* stats, const float* gamma, const float* beta, int G, int silu, const float* da, int da_mode, int B,
+                     int H, int W, int C, float* ws, float* dgamma, float* dbeta, hipStream_t st);
+void launch_linear_bwd_w(const float* dy, int ld_dy, const float* x, int silu_in, int B, int N, int K, float* gw, float* gb, float* gb2, hipStream_t st);
+void launch_linear_bwd_x(const float* dy, const float* W, const float* x, int silu_in, int B, int N, int K, float* dx, hipStream_t st);
+
 }  // namespace buddy

@@ -26,6 +26,8 @@ int net_reserve(Net* N, int B, int L, int with_vjp, long long* bytes);
 int net_forward(Net* N, const float* x, const float* cnoise, const float* cin_b, const float* cskip_b, const float* cout_b, float* y, int B, int L,
                 int save, hipStream_t st);
 int net_vjp(Net* N, const float* cot, float* gx, hipStream_t st);
+int net_vjp_params(Net* N, const float* cot, float* gx, float* gp, int accumulate, hipStream_t st);   // + parameter gradients (forward save = 2)
+int net_update_params(Net* N, const float* dev_params, hipStream_t st);    // new weights into the shared store, derived forms rebuilt
 int net_get_tap(Net* N, int module_idx, const float** p, int dims[4]);
 
 

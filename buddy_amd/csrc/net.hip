@@ -1,7 +1,8 @@
 // Host-side graph of the NCSN++ score network (reference networks/ncsnpp.py:281-449 + STFT/iSTFT wrapper :473-506)
 // and its input-VJP, driving the gfx950 kernels of igemm.hip / ops.hip.  One call = one forward (or one VJP) of the
 // whole network for a batch of utterances; activations live in one HBM arena owned by the handle (sized by a dry run).
-// The VJP is a reverse "tape" of closures recorded during the forward (no weight gradients: inference only).
+// The VJP is a reverse "tape" of closures recorded during the forward.  A forward saved for the parameter VJP (save = 2) also gives the weight
+// gradients: each closure launches its layer's parameter-gradient kernels (wgrad.hip) while that layer's output gradient exists.
 #include "common.h"
 #include "net.h"
 
@@ -122,10 +123,12 @@ struct WVar { float* u = nullptr; void* x = nullptr; void* x2 = nullptr; void* x
 // (direction, kernel variant, arithmetic) per layer is ever built for a given workload, on the GPU (wprep.hip).  wf / wb: forms prepared at
 // creation (the small 2-channel convolutions, 1x1 convolutions)
 struct ConvW { int cin = 0, cout = 0, taps = 0; const float* raw = nullptr; float* wf = nullptr; float* wb = nullptr; float* bias = nullptr;
-               mutable WVar var[2][5]; };                      // [forward | data-gradient][direct, F(2x2), F(4x4), F(6x6), F(6x6) sub-pixel up form]
-struct GNW { float* gamma = nullptr; float* beta = nullptr; int C = 0; };
-struct ResW { GNW gn0, gn1; ConvW c0, c1, c2; bool has_c2 = false; int cin = 0, cout = 0, dense_off = 0; };
-struct AttnW { GNW gn; float* Wt[4]; float* Wn[4]; float* b[4]; int C = 0; int level = -1; };   // level: the site's level (-1: the bottleneck block)
+               mutable WVar var[2][5];                         // [forward | data-gradient][direct, F(2x2), F(4x4), F(6x6), F(6x6) sub-pixel up form]
+               long long go = -1; };                           // offset of the weight in the flat parameter order (the bias follows it)
+struct GNW { float* gamma = nullptr; float* beta = nullptr; int C = 0; long long go = -1; };   // go: flat offset of gamma (beta follows)
+struct ResW { GNW gn0, gn1; ConvW c0, c1, c2; bool has_c2 = false; int cin = 0, cout = 0, dense_off = 0; long long dense_go = -1; };
+struct AttnW { GNW gn; float* Wt[4]; float* Wn[4]; float* b[4]; int C = 0; int level = -1;   // level: the site's level (-1: the bottleneck block)
+               long long go[4] = {-1, -1, -1, -1}; };                                       // flat offsets of NIN_k.W (each bias follows its W)
 
 struct W3Img { const void* img; int N, K; const void* img2 = nullptr; };      // img: bf16x3 stage image; img2: f16x2 stage image (general f16x2 form), where the shape allows
 // Everything derived from the parameters: shared (read-only after preparation) by a handle and its replicas (net_replica)
@@ -134,6 +137,14 @@ struct Weights {
   std::vector<PSpec> specs;
   float* dparams = nullptr;    // raw parameters (device)
   float* dpacked = nullptr;    // small packed weights (device): 2-channel convolutions, transposed 1x1 / NIN, Dense_0 stack, DFT bases
+  std::vector<long long> doff; // padded device offset of every tensor (specs order)
+  // buddy_ncsnpp_update_params: the host image of dpacked and the jobs that rebuild its parameter-derived parts; the 1x1 / NIN stage images
+  std::vector<float> host_pack;
+  std::vector<std::pair<long long, std::function<std::vector<float>(const float*)>>> repack;
+  struct Img { const float* src; void* img; void* img2; int n, k; };
+  std::vector<Img> imgs;
+  int gen = 0;                 // bumped by every update: a tape saved before it is refused
+  long long lin1_go = -1, lin2_go = -1, out_go = -1;
   // modules in execution order
   float* Wf = nullptr; float* lin1_w = nullptr; float* lin1_b = nullptr; float* lin2_w = nullptr; float* lin2_b = nullptr;
   float* dense_w = nullptr; float* dense_b = nullptr; int dense_total = 0;
@@ -174,6 +185,10 @@ struct Net {
   double* partial = nullptr; float* red = nullptr;       // reduction scratch
   bool have_tape = false;
   hipStream_t st = nullptr;
+  // parameter VJP: pgrad = the forward was saved for it (save = 2; the arena is sized for the gradient kernels' workspaces).  pg: the flat
+  // gradient buffer of the running call (null in the sizing dry run); dtemb: d temb_all [B][dense_total]; tape_gen: Weights::gen of the saved forward
+  bool pgrad = false, pg_run = false; float* pg = nullptr; float* dtemb = nullptr; int tape_gen = 0;
+  const float* k_four = nullptr; const float* k_t1 = nullptr; const float* k_temb = nullptr;
   // saved for vjp
   Tens* spec = nullptr; Tens* pyr0 = nullptr;
   const float* k_cin = nullptr; const float* k_cskip = nullptr; const float* k_cout = nullptr;
@@ -259,7 +274,8 @@ static int weights_create(const float* hp, long long n, const NetCfg& cfg, std::
   }
   const int Fb = cfg.n_fft / 2 + 1, Kp = (cfg.n_fft + 3) / 4 * 4;
   if (Fb % (1 << (cfg.nlev - 1))) { set_error("frequency bins not divisible by 2^(levels-1)"); return BUDDY_ERR_ARG; }
-  std::vector<long long> doff(N->specs.size());
+  std::vector<long long>& doff = N->doff;
+  doff.resize(N->specs.size());
   {
     long long o = 0;
     for (size_t i = 0; i < N->specs.size(); ++i) { doff[i] = o; o += (N->specs[i].numel + 63) / 64 * 64; }
@@ -283,20 +299,21 @@ static int weights_create(const float* hp, long long n, const NetCfg& cfg, std::
     for (size_t i = 0; i < N->specs.size(); ++i) if (N->specs[i].name == name) return N->dparams + doff[i];
     return nullptr;
   };
-  auto host = [&](const std::string& name) -> const float* {
-    const PSpec* s = find_spec(N->specs, name);
-    return s ? hp + s->off : nullptr;
-  };
-  auto packed = [&](float** dst, const std::vector<float>& v) { fixes.push_back({dst, pk.put(v)}); };
+  auto packed = [&](float** dst, const std::vector<float>& v) { fixes.push_back({dst, pk.put(v)}); };     // constant forms (DFT bases)
+  // forms derived from parameters: the generator is kept, buddy_ncsnpp_update_params runs it again on the new host parameters
+  using Gen = std::function<std::vector<float>(const float*)>;
+  auto packed_gen = [&](float** dst, Gen g) { const long long o = pk.put(g(hp)); fixes.push_back({dst, o}); N->repack.push_back({o, std::move(g)}); };
+  auto hoff = [&](const std::string& name) -> long long { const PSpec* s = find_spec(N->specs, name); return s ? s->off : -1; };
 
   const int nf = cfg.nf;
   int idx = 0;
   auto pre = [&]() { return "all_modules." + std::to_string(idx) + "."; };
-  std::vector<float> dense_w_all, dense_b_all;
-  auto load_gn = [&](GNW& g, const std::string& p, int C) { g.gamma = raw(p + ".weight"); g.beta = raw(p + ".bias"); g.C = C; };
+  int dense_total = 0;
+  auto load_gn = [&](GNW& g, const std::string& p, int C) { g.gamma = raw(p + ".weight"); g.beta = raw(p + ".bias"); g.C = C; g.go = hoff(p + ".weight"); };
   auto load_conv3 = [&](ConvW& c, const std::string& p, int cin, int cout) {
-    c.cin = cin; c.cout = cout; c.taps = 9; c.bias = raw(p + ".bias"); c.raw = raw(p + ".weight");
+    c.cin = cin; c.cout = cout; c.taps = 9; c.bias = raw(p + ".bias"); c.raw = raw(p + ".weight"); c.go = hoff(p + ".weight");
   };
+  std::vector<std::pair<long long, int>> dense_src;     // (flat offset of Dense_0.weight, cout) per ResBlock: the Dense_0 stack's generator
   auto load_res = [&](int cin, int cout, bool resample) {
     ResW r; r.cin = cin; r.cout = cout;
     const std::string p = pre();
@@ -305,32 +322,41 @@ static int weights_create(const float* hp, long long n, const NetCfg& cfg, std::
     ResW& R = N->res.back();
     load_conv3(R.c0, p + "Conv_0", cin, cout);
     load_conv3(R.c1, p + "Conv_1", cout, cout);
-    R.dense_off = (int)dense_b_all.size();
-    const float* dw = host(p + "Dense_0.weight"); const float* db = host(p + "Dense_0.bias");
-    dense_w_all.insert(dense_w_all.end(), dw, dw + (size_t)cout * nf * 4);
-    dense_b_all.insert(dense_b_all.end(), db, db + cout);
+    R.dense_off = dense_total;
+    R.dense_go = hoff(p + "Dense_0.weight");
+    dense_src.push_back({R.dense_go, cout});
+    dense_total += cout;
     R.has_c2 = (cin != cout) || resample;
     if (R.has_c2) {
       R.c2.cin = cin; R.c2.cout = cout; R.c2.taps = 1; R.c2.bias = raw(p + "Conv_2.bias");
       R.c2.wf = raw(p + "Conv_2.weight");                                  // [cout][cin] already k-contiguous
-      packed(&R.c2.wb, transpose2(host(p + "Conv_2.weight"), cout, cin));  // [cin][cout]
+      R.c2.go = hoff(p + "Conv_2.weight");
+      packed_gen(&R.c2.wb, [o = R.c2.go, cout, cin](const float* h) { return transpose2(h + o, cout, cin); });  // [cin][cout]
       plain3.push_back({&R.c2.wf, {cout, cin}}); plain3.push_back({&R.c2.wb, {cin, cout}});
     }
     ++idx;
   };
   N->res.reserve(64);
   N->Wf = raw(pre() + "W"); ++idx;
+  N->lin1_go = hoff(pre() + "weight");
   N->lin1_w = raw(pre() + "weight"); N->lin1_b = raw(pre() + "bias"); ++idx;
+  N->lin2_go = hoff(pre() + "weight");
   N->lin2_w = raw(pre() + "weight"); N->lin2_b = raw(pre() + "bias"); ++idx;
   {  // input conv 2 -> nf
-    const float* w = host(pre() + "weight");
-    N->conv_in.cin = 2; N->conv_in.cout = nf; N->conv_in.taps = 9; N->conv_in.bias = raw(pre() + "bias");
-    std::vector<float> f((size_t)nf * 18), b((size_t)9 * nf * 2);
-    for (int o = 0; o < nf; ++o) for (int dy = 0; dy < 3; ++dy) for (int dx = 0; dx < 3; ++dx) for (int i = 0; i < 2; ++i) {
-      f[((size_t)o * 9 + dy * 3 + dx) * 2 + i] = w3(w, nf, 2, o, i, dy, dx);
-      b[((size_t)(dy * 3 + dx) * nf + o) * 2 + i] = w3(w, nf, 2, o, i, 2 - dy, 2 - dx);
-    }
-    packed(&N->conv_in.wf, f); packed(&N->conv_in.wb, b);
+    const long long o_w = hoff(pre() + "weight");
+    N->conv_in.cin = 2; N->conv_in.cout = nf; N->conv_in.taps = 9; N->conv_in.bias = raw(pre() + "bias"); N->conv_in.go = o_w;
+    packed_gen(&N->conv_in.wf, [o_w, nf](const float* h) {
+      std::vector<float> f((size_t)nf * 18);
+      for (int o = 0; o < nf; ++o) for (int dy = 0; dy < 3; ++dy) for (int dx = 0; dx < 3; ++dx) for (int i = 0; i < 2; ++i)
+        f[((size_t)o * 9 + dy * 3 + dx) * 2 + i] = w3(h + o_w, nf, 2, o, i, dy, dx);
+      return f;
+    });
+    packed_gen(&N->conv_in.wb, [o_w, nf](const float* h) {
+      std::vector<float> b((size_t)9 * nf * 2);
+      for (int o = 0; o < nf; ++o) for (int dy = 0; dy < 3; ++dy) for (int dx = 0; dx < 3; ++dx) for (int i = 0; i < 2; ++i)
+        b[((size_t)(dy * 3 + dx) * nf + o) * 2 + i] = w3(h + o_w, nf, 2, o, i, 2 - dy, 2 - dx);
+      return b;
+    });
     ++idx;
   }
   // AttnBlock: GroupNorm_0, NIN_0..3 (q, k, v, output projection; layerspp.py:70-80)
@@ -340,7 +366,8 @@ static int weights_create(const float* hp, long long n, const NetCfg& cfg, std::
     load_gn(a.gn, p + "GroupNorm_0", C);
     for (int k = 0; k < 4; ++k) {
       a.Wn[k] = raw(p + "NIN_" + std::to_string(k) + ".W"); a.b[k] = raw(p + "NIN_" + std::to_string(k) + ".b");
-      packed(&a.Wt[k], transpose2(host(p + "NIN_" + std::to_string(k) + ".W"), C, C));
+      a.go[k] = hoff(p + "NIN_" + std::to_string(k) + ".W");
+      packed_gen(&a.Wt[k], [o = a.go[k], C](const float* h) { return transpose2(h + o, C, C); });
       plain3.push_back({&a.Wt[k], {C, C}}); plain3.push_back({&a.Wn[k], {C, C}});
     }
     ++idx;
@@ -360,7 +387,7 @@ static int weights_create(const float* hp, long long n, const NetCfg& cfg, std::
     }
     if (l != cfg.nlev - 1) {
       load_res(ch, ch, true);
-      ConvW c; c.cin = 2; c.cout = ch; c.taps = 1; c.bias = raw(pre() + "Conv_0.bias");
+      ConvW c; c.cin = 2; c.cout = ch; c.taps = 1; c.bias = raw(pre() + "Conv_0.bias"); c.go = hoff(pre() + "Conv_0.weight");
       c.wf = raw(pre() + "Conv_0.weight"); c.wb = c.wf;   // [C][2]: both kernels index it the same way for one tap
       N->combine.push_back(c); ++idx;
       hs_c.push_back(ch);
@@ -375,21 +402,36 @@ static int weights_create(const float* hp, long long n, const NetCfg& cfg, std::
     if (cfg.attn_mask >> l & 1) { N->sites.emplace_back(); load_attn(N->sites.back(), ch, l); }
     load_gn(N->pyr_gn[j], "all_modules." + std::to_string(idx), ch); ++idx;
     {
-      const float* w = host(pre() + "weight");   // [2][ch][3][3]
-      ConvW& c = N->pyr_conv[j]; c.cin = ch; c.cout = 2; c.taps = 9; c.bias = raw(pre() + "bias");
-      std::vector<float> f((size_t)9 * ch * 2), b((size_t)ch * 18);
-      for (int dy = 0; dy < 3; ++dy) for (int dx = 0; dx < 3; ++dx) for (int i = 0; i < ch; ++i) for (int o = 0; o < 2; ++o) {
-        f[((size_t)(dy * 3 + dx) * ch + i) * 2 + o] = w3(w, 2, ch, o, i, dy, dx);
-        b[((size_t)i * 9 + dy * 3 + dx) * 2 + o] = w3(w, 2, ch, o, i, 2 - dy, 2 - dx);
-      }
-      packed(&c.wf, f); packed(&c.wb, b);
+      const long long o_w = hoff(pre() + "weight");   // [2][ch][3][3]
+      ConvW& c = N->pyr_conv[j]; c.cin = ch; c.cout = 2; c.taps = 9; c.bias = raw(pre() + "bias"); c.go = o_w;
+      packed_gen(&c.wf, [o_w, ch](const float* h) {
+        std::vector<float> f((size_t)9 * ch * 2);
+        for (int dy = 0; dy < 3; ++dy) for (int dx = 0; dx < 3; ++dx) for (int i = 0; i < ch; ++i) for (int o = 0; o < 2; ++o)
+          f[((size_t)(dy * 3 + dx) * ch + i) * 2 + o] = w3(h + o_w, 2, ch, o, i, dy, dx);
+        return f;
+      });
+      packed_gen(&c.wb, [o_w, ch](const float* h) {
+        std::vector<float> b((size_t)ch * 18);
+        for (int dy = 0; dy < 3; ++dy) for (int dx = 0; dx < 3; ++dx) for (int i = 0; i < ch; ++i) for (int o = 0; o < 2; ++o)
+          b[((size_t)i * 9 + dy * 3 + dx) * 2 + o] = w3(h + o_w, 2, ch, o, i, 2 - dy, 2 - dx);
+        return b;
+      });
       ++idx;
     }
     if (l != 0) load_res(ch, ch, true);
   }
-  N->out_w = raw("output_layer.weight"); N->out_b = raw("output_layer.bias");
-  N->dense_total = (int)dense_b_all.size();
-  packed(&N->dense_w, dense_w_all); packed(&N->dense_b, dense_b_all);
+  N->out_w = raw("output_layer.weight"); N->out_b = raw("output_layer.bias"); N->out_go = hoff("output_layer.weight");
+  N->dense_total = dense_total;
+  packed_gen(&N->dense_w, [dense_src, nf](const float* h) {      // Dense_0 weights [cout][4 nf] stacked
+    std::vector<float> v;
+    for (auto& d : dense_src) v.insert(v.end(), h + d.first, h + d.first + (size_t)d.second * nf * 4);
+    return v;
+  });
+  packed_gen(&N->dense_b, [dense_src, nf](const float* h) {      // their biases (each follows its weight)
+    std::vector<float> v;
+    for (auto& d : dense_src) { const float* b = h + d.first + (size_t)d.second * nf * 4; v.insert(v.end(), b, b + d.second); }
+    return v;
+  });
 
   // DFT bases with the periodic Hann window folded in (reference ncsnpp.py:464,473-496 via the stft / istft of PyTorch).
   {
@@ -414,6 +456,7 @@ static int weights_create(const float* hp, long long n, const NetCfg& cfg, std::
   HIPCHK(hipMalloc(&N->dpacked, pk.buf.size() * 4));
   HIPCHK(hipMemcpyAsync(N->dpacked, pk.buf.data(), pk.buf.size() * 4, hipMemcpyHostToDevice, nullptr));
   for (auto& f : fixes) *f.dst = N->dpacked + f.off;
+  N->host_pack = pk.buf;
   std::vector<size_t> plain_off;
   size_t pack3_bytes = 0;
   for (auto& j : plain3) {
@@ -438,6 +481,7 @@ static int weights_create(const float* hp, long long n, const NetCfg& cfg, std::
         im.img2 = N->dpacked3 + pack3_bytes + plain_off2[i];
       }
       N->w3[*plain3[i].first] = im;
+      N->imgs.push_back({*plain3[i].first, (void*)im.img, (void*)im.img2, n3, k3});
     }
   }
   HIPCHK(hipDeviceSynchronize());     // the host staging buffers go out of scope here
@@ -471,6 +515,44 @@ int net_replica(Net* src, Net** out) {
   if (int rc = net_from_weights(src->W, &N)) return rc;
   N->opt = src->opt; N->fir = src->fir;
   *out = N;
+  return BUDDY_OK;
+}
+
+// New raw parameters (device, flat in the parameter order) into the shared store, in place: the raw tensors by device copies, the host-packed forms
+// (2-channel convolutions, transposed 1x1 / NIN, the Dense_0 stack) rebuilt from one host copy, the 1x1 / NIN stage images packed again, and the
+// lazily prepared 3x3 forms dropped (rebuilt on next use).  Every handle on the store sees the new weights; a forward saved by any of them before
+// the update can no longer be differentiated (vjp -> BUDDY_ERR_STATE).  No handle on the store may have work in flight on another stream.
+int net_update_params(Net* N, const float* dev, hipStream_t st) {
+  Weights* Wt = N->W.get();
+  std::lock_guard<std::mutex> lk(Wt->mu);
+  const long long n = param_count(Wt->cfg);
+  for (size_t i = 0; i < Wt->specs.size();) {         // runs of tensors whose padded and flat offsets advance together: one copy each
+    size_t j = i; long long len = Wt->specs[i].numel;
+    while (j + 1 < Wt->specs.size() && Wt->specs[j].numel % 64 == 0) { ++j; len += Wt->specs[j].numel; }
+    HIPCHK(hipMemcpyAsync(Wt->dparams + Wt->doff[i], dev + Wt->specs[i].off, (size_t)len * 4, hipMemcpyDeviceToDevice, st));
+    i = j + 1;
+  }
+  std::vector<float> hp((size_t)n);
+  HIPCHK(hipMemcpyAsync(hp.data(), dev, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (auto& j : Wt->repack) {
+    const std::vector<float> v = j.second(hp.data());
+    std::copy(v.begin(), v.end(), Wt->host_pack.begin() + j.first);
+  }
+  HIPCHK(hipMemcpyAsync(Wt->dpacked, Wt->host_pack.data(), Wt->host_pack.size() * 4, hipMemcpyHostToDevice, st));
+  for (auto& im : Wt->imgs) {
+    wgemm_pack_weights(im.src, im.img, 1, im.n, im.k, st);
+    if (im.img2) wgemm_f16x2_pack_weights(im.src, im.img2, 1, im.n, im.k, st);
+  }
+  HIPCHK(hipStreamSynchronize(st));
+  for (ResW& R : Wt->res)
+    for (ConvW* c : {&R.c0, &R.c1})
+      for (auto& row : c->var) for (WVar& v : row) v = WVar{};
+  for (void* q : Wt->lazy_allocs) (void)hipFree(q);
+  Wt->lazy_allocs.clear(); Wt->lazy_bytes = 0; Wt->lazy_count = 0;
+  ++Wt->gen;
+  N->tape.clear(); N->have_tape = false;
+  HIPCHK(hipGetLastError());
   return BUDDY_OK;
 }
 
@@ -769,6 +851,34 @@ static void view_stats(Net* N, const View& x, int HW, int G, float* stats) {
   launch_gn_stats_csum(x.a->csum, x.b ? x.b->csum : nullptr, x.a->C, B, HW, x.C(), G, 1e-6f, stats, st);
 }
 
+// ------------------------------------------------------------------------------------------------ parameter-gradient helpers (wgrad.hip)
+// All of them take their workspace from the arena in the sizing dry run too (the arena of a save = 2 forward holds it) and add into the flat
+// gradient buffer N->pg at a tensor's offset in the parameter order.
+static WgY wy(const float* p, long long T, int ld) { WgY y; y.p = p; y.T = T; y.sb = T * ld; y.sm = ld; y.sn = 1; return y; }
+static WgA wa(Src2 x, int H, int W, int Cin, int taps, int rs) {
+  WgA a; a.x = x; a.H = H; a.W = W; a.Cin = Cin; a.taps = taps; a.rs = rs; a.stats = nullptr; a.gamma = nullptr; a.beta = nullptr; a.G = 1; a.silu = 0;
+  return a;
+}
+static WgA wa_gn(Src2 x, int H, int W, int Cin, int taps, int rs, const float* stats, const GNW& g, int G, int silu) {
+  WgA a = wa(x, H, W, Cin, taps, rs); a.stats = stats; a.gamma = g.gamma; a.beta = g.beta; a.G = G; a.silu = silu;
+  return a;
+}
+// weight [N][taps * Cin] (layout: launch_wgrad) of the flat tensor at go
+static void pg_weight(Net* n, const WgY& y, const WgA& a, long long M, int Nn, int layout, float alpha, long long go) {
+  float* ws = n->tmp(wgrad_ws_floats(M, Nn, a.taps * a.Cin));
+  if (!n->dry()) launch_wgrad(y, a, M, Nn, layout, alpha, ws, n->pg + go, n->st);
+}
+// column sums of y over the pixels of each utterance: into the tensors at go1 / go2 (-1: none), per utterance into bc (ld_bc)
+static void pg_colsum(Net* n, const WgY& y, int B, int Nn, float alpha, float* bc, int ld_bc, long long go1, long long go2) {
+  float* ws = n->tmp(colsum_ws_floats(B, y.T, Nn));
+  if (!n->dry()) launch_colsum(y, B, Nn, alpha, ws, bc, ld_bc, go1 >= 0 ? n->pg + go1 : nullptr, go2 >= 0 ? n->pg + go2 : nullptr, n->st);
+}
+// GroupNorm gamma / beta from the gradient da of act(GroupNorm(x)) (da_mode: wgrad.hip gn_pgrad_part_kernel)
+static void pg_gn(Net* n, Src2 x, const float* stats, const GNW& g, int G, int silu, const float* da, int da_mode, int B, int H, int W, int C) {
+  float* ws = n->tmp(gn_pgrad_ws_floats(B, H, W, C));
+  if (!n->dry()) launch_gn_pgrad(x, stats, g.gamma, g.beta, G, silu, da, da_mode, B, H, W, C, ws, n->pg + g.go, n->pg + g.go + C, n->st);
+}
+
 // ------------------------------------------------------------------------------------------------ composite ops
 static Tens* resblock(Net* N, const ResW& R, View x, int mode, const float* temb_all, bool rec) {
   const int B = x.a->B, H = x.a->H, W = x.a->W, Cin = R.cin, Cout = R.cout;
@@ -895,6 +1005,11 @@ static Tens* resblock(Net* N, const ResW& R, View x, int mode, const float* temb
       d0c.out = da0; d0c.gn = &gb1; d0c.gn_tmp = dh1; d0c.bwd_gn = (mode == 0 || up6) ? &b0 : nullptr;
       if (up6) { d0c.H = H; d0c.W = W; d0c.up = 2; }      // da0 comes out at (H, W): the nearest-upsample's adjoint is inside the convolution
       const int s0 = conv3(n, d0c);
+      if (n->pg_run && !n->dry()) {      // parameter VJP: Conv_0's output gradient dh1 itself (F(6x6,3x3) only forms it inside its input transform)
+        Dst2 dd; dd.p0 = dh1; dd.p1 = nullptr; dd.C0 = Cout; dd.ld0 = Cout; dd.ld1 = 0; dd.acc0 = 0; dd.acc1 = 0;
+        launch_gn_bwd_apply(single(h1->p, Cout), stats1, Rp->gn1.gamma, Rp->gn1.beta, da1, B, Ho, Wo, Cout, G1, 0, 1, nullptr, 0, 0.f, n->red, dd, s);
+      }
+      float* da0f_keep = nullptr;
       if (c2i) {
         if (!n->dry()) {
           launch_gn_bwd_sums(src_of(x), stats0, Rp->gn0.gamma, Rp->gn0.beta, da0, B, H, W, Cin, G0, 0, 1, n->partial, n->red, s, s0);
@@ -911,6 +1026,7 @@ static Tens* resblock(Net* N, const ResW& R, View x, int mode, const float* temb
       } else
       if (firm) {
         float* da0f = n->tmp((long long)B * H * W * Cin);
+        da0f_keep = da0f;
         if (!n->dry()) {
           if (mode == 2) launch_fir_down2(da0, da0f, B, Ho, Wo, Cin, 4.f, 0, s);
           else launch_fir_up2(da0, da0f, B, Ho, Wo, Cin, 0.25f, 0, s);
@@ -920,6 +1036,41 @@ static Tens* resblock(Net* N, const ResW& R, View x, int mode, const float* temb
       if (!n->dry())
         launch_gn_bwd(src_of(x), stats0, Rp->gn0.gamma, Rp->gn0.beta, da0, B, H, W, Cin, G0, up6 ? 0 : mode, 1, extra, extra_mode, extra_scale,
                       n->partial, n->red, d0, s, s0);
+      if (n->pg_run) {
+        const long long Mo = (long long)B * Ho * Wo;
+        const WgY yo = wy(dout, (long long)Ho * Wo, Cout), yh = wy(dh1, (long long)Ho * Wo, Cout);
+        // Conv_1 and its bias; Conv_2's bias: the gradient at the residual sum is dout / sqrt 2
+        pg_weight(n, yo, wa_gn(single(h1->p, Cout), Ho, Wo, Cout, 9, 0, stats1, Rp->gn1, G1, 1), Mo, Cout, 1, INV_SQRT2, Rp->c1.go);
+        pg_colsum(n, yo, B, Cout, INV_SQRT2, nullptr, 0, Rp->c1.go + 9LL * Cout * Cout, Rp->has_c2 ? Rp->c2.go + (long long)Cout * Cin : -1);
+        // Conv_0 over act(GroupNorm_0(x)), box-downsampled (mode 1) or nearest-upsampled (mode 2) inside the loader; the FIR forms are materialised
+        if (firm) {
+          float* a0f = n->tmp((long long)B * H * W * Cin); float* a0r = n->tmp(Mo * Cin);
+          if (!n->dry()) {
+            launch_gn_apply(src_of(x), stats0, Rp->gn0.gamma, Rp->gn0.beta, B, H, W, Cin, G0, 0, 1, a0f, nullptr, s);
+            if (mode == 2) launch_fir_up2(a0f, a0r, B, H, W, Cin, 1.f, 0, s); else launch_fir_down2(a0f, a0r, B, H, W, Cin, 1.f, 0, s);
+          }
+          pg_weight(n, yh, wa(single(a0r, Cin), Ho, Wo, Cin, 9, 0), Mo, Cout, 1, 1.f, Rp->c0.go);
+        } else
+          pg_weight(n, yh, wa_gn(src_of(x), Ho, Wo, Cin, 9, mode, stats0, Rp->gn0, G0, 1), Mo, Cout, 1, 1.f, Rp->c0.go);
+        // Conv_0's bias, and the per-utterance sums that the time-embedding backward turns into Dense_0's gradient (after the walk)
+        pg_colsum(n, yh, B, Cout, 1.f, n->dtemb + Rp->dense_off, n->W->dense_total, Rp->c0.go + 9LL * Cout * Cin, -1);
+        if (Rp->has_c2) {                // Conv_2 (1x1) on the skip path
+          if (firm) {
+            float* xr2 = n->tmp(Mo * Cin);
+            if (!n->dry()) { if (mode == 2) launch_fir_up2(x.a->p, xr2, B, H, W, Cin, 1.f, 0, s); else launch_fir_down2(x.a->p, xr2, B, H, W, Cin, 1.f, 0, s); }
+            pg_weight(n, yo, wa(single(xr2, Cin), Ho, Wo, Cin, 1, 0), Mo, Cout, 0, INV_SQRT2, Rp->c2.go);
+          } else if (mode == 2) {        // Conv_2 ran at the input resolution, its output was nearest-upsampled: the gradient is the 2 x 2 sum of dout
+            float* pooled2 = n->tmp((long long)B * H * W * Cout);
+            if (!n->dry()) launch_pool2(dout, pooled2, B, Ho, Wo, Cout, 1.f, 0, s);
+            pg_weight(n, wy(pooled2, (long long)H * W, Cout), wa(src_of(x), H, W, Cin, 1, 0), (long long)B * H * W, Cout, 0, INV_SQRT2, Rp->c2.go);
+          } else
+            pg_weight(n, yo, wa(src_of(x), Ho, Wo, Cin, 1, mode), Mo, Cout, 0, INV_SQRT2, Rp->c2.go);
+        }
+        // GroupNorm_1 and GroupNorm_0 affine parameters
+        pg_gn(n, single(h1->p, Cout), stats1, Rp->gn1, G1, 1, da1, 0, B, Ho, Wo, Cout);
+        if (firm) pg_gn(n, src_of(x), stats0, Rp->gn0, G0, 1, da0f_keep, 0, B, H, W, Cin);
+        else pg_gn(n, src_of(x), stats0, Rp->gn0, G0, 1, da0, up6 ? 0 : mode == 1 ? 1 : mode == 2 ? 2 : 0, B, H, W, Cin);
+      }
       n->arena.off = mk;
     });
   }
@@ -949,6 +1100,23 @@ static bool attn_use_flash(const Net* N, int C, int T) {
 }
 // 16-bit operands where attn16.hip has a kernel for C; a C = 32 site runs the fp32 flash kernels in every mode
 static int attn_prec(const Net* N, int C) { return (N->opt.attn == 1 || N->opt.attn == 2) && flash_attn16_supported(C) ? N->opt.attn : 0; }
+
+// AttnBlock parameters: NIN_0..2 over hn = GroupNorm_0(x) (evaluated in the loader), NIN_3 over the attention output O, biases, GroupNorm_0
+static void attn_pgrad(Net* n, const AttnW& A, Tens* x, const float* stats, const float* dq, const float* dk, const WgY& ydv, const float* O,
+                       const float* dout, const float* dhn) {
+  const int B = x->B, H = x->H, W = x->W, C = A.C, T = H * W, G = gn_groups(C);
+  const long long M = (long long)B * T;
+  const WgA ahn = wa_gn(single(x->p, C), H, W, C, 1, 0, stats, A.gn, G, 0);
+  const WgY ys[3] = {wy(dq, T, C), wy(dk, T, C), ydv};
+  for (int k = 0; k < 3; ++k) {
+    pg_weight(n, ys[k], ahn, M, C, 2, 1.f, A.go[k]);
+    pg_colsum(n, ys[k], B, C, 1.f, nullptr, 0, A.go[k] + (long long)C * C, -1);
+  }
+  const WgY yo = wy(dout, T, C);
+  pg_weight(n, yo, wa(single(O, C), H, W, C, 1, 0), M, C, 2, INV_SQRT2, A.go[3]);
+  pg_colsum(n, yo, B, C, INV_SQRT2, nullptr, 0, A.go[3] + (long long)C * C, -1);
+  pg_gn(n, single(x->p, C), stats, A.gn, G, 0, dhn, 0, B, H, W, C);
+}
 
 static Tens* attnblock_flash(Net* N, const AttnW& A, Tens* x, bool rec) {
   const int B = x->B, H = x->H, W = x->W, C = A.C, T = H * W, G = gn_groups(C);
@@ -1003,6 +1171,7 @@ static Tens* attnblock_flash(Net* N, const AttnW& A, Tens* x, bool rec) {
       Dst2 d = gdst_of(xv);
       if (!n->dry())
         launch_gn_bwd(single(x->p, C), stats, Ap->gn.gamma, Ap->gn.beta, dhn, B, H, W, C, G, 0, 0, dout, 1, INV_SQRT2, n->partial, n->red, d, s);
+      if (n->pg_run) attn_pgrad(n, *Ap, x, stats, dq, dk, wy(dv, T, C), O, dout, dhn);
       n->arena.off = mk;
     });
   }
@@ -1076,6 +1245,13 @@ static Tens* attnblock(Net* N, const AttnW& A, Tens* x, bool rec) {
       Dst2 d = gdst_of(xv);
       if (!n->dry())
         launch_gn_bwd(single(x->p, C), stats, Ap->gn.gamma, Ap->gn.beta, dhn, B, H, W, C, G, 0, 0, dout, 1, INV_SQRT2, n->partial, n->red, d, s);
+      if (n->pg_run) {
+        float* O2 = n->tmp(B * TC);        // the forward's O = P V was a temporary: once more, with the same GEMM
+        gemm_b(n, P, T, TT, false, vT, T, (long long)C * T, false, O2, C, TC, T, C, T, nullptr, nullptr, 1.f, 0, B);
+        WgY ydv = wy(dvT, T, C);           // dV [T][C] (transposed form) or dV^T [C][T] per utterance
+        if (!tr) { ydv.sb = TC; ydv.sm = 1; ydv.sn = T; }
+        attn_pgrad(n, *Ap, x, stats, dq, dk, ydv, O2, dout, dhn);
+      }
       n->arena.off = mk;
     });
   }
@@ -1146,6 +1322,7 @@ static void run_forward(Net* N, const float* x, const float* cnoise, const float
     launch_linear(t1, N->W->lin2_w, N->W->lin2_b, temb, B, 4 * nf, 4 * nf, 1, st);
     launch_linear(temb, N->W->dense_w, N->W->dense_b, temb_all, B, 4 * nf, N->W->dense_total, 1, st);
   }
+  N->k_four = four; N->k_t1 = t1; N->k_temb = temb;      // for the time-embedding backward of the parameter VJP
 
   int mi = 3, ri = 0, ci = 0, si = 0;
   auto tap = [&](int idx, Tens* t) { N->taps.push_back({idx, t}); };
@@ -1153,6 +1330,11 @@ static void run_forward(Net* N, const float* x, const float* cnoise, const float
   Tens* h0 = N->mk(B, Tp, Fb, nf, rec);
   if (!N->dry()) launch_conv_c2in(spec->p, N->W->conv_in.wf, N->W->conv_in.bias, nullptr, 0, h0->p, nf, B, Tp, Fb, nf, 9, 0, st);
   if (rec) N->tape.push_back([=]() {
+    if (N->pg_run) {
+      const WgY y0 = wy(h0->g, (long long)Tp * Fb, nf);
+      pg_weight(N, y0, wa(single(spec->p, 2), Tp, Fb, 2, 9, 0), (long long)B * Tp * Fb, nf, 1, 1.f, N->W->conv_in.go);
+      pg_colsum(N, y0, B, nf, 1.f, nullptr, 0, N->W->conv_in.go + 18LL * nf, -1);
+    }
     if (N->dry()) { spec->ginit = 1; return; }
     launch_conv_c2out(h0->g, nf, N->W->conv_in.wb, nullptr, nullptr, spec->g, B, Tp, Fb, nf, 9, spec->ginit, N->st);
     spec->ginit = 1;
@@ -1195,6 +1377,11 @@ static void run_forward(Net* N, const float* x, const float* cnoise, const float
           launch_conv_c2out(hc->g, h->C, cwp->wb, nullptr, nullptr, pin->g, B, h->H, h->W, h->C, 1, pin->ginit, N->st);
         }
         h->ginit = 1; pin->ginit = 1;
+        if (N->pg_run) {
+          const WgY yc = wy(hc->g, (long long)h->H * h->W, h->C);
+          pg_weight(N, yc, wa(single(pin->p, 2), h->H, h->W, 2, 1, 0), (long long)B * h->H * h->W, h->C, 0, 1.f, cwp->go);
+          pg_colsum(N, yc, B, h->C, 1.f, nullptr, 0, cwp->go + 2LL * h->C, -1);
+        }
       }); }
       tap(mi, hc); ++mi;
       hs.push_back(hc);
@@ -1241,6 +1428,12 @@ static void run_forward(Net* N, const float* x, const float* cnoise, const float
         View hv; hv.a = hh;
         Dst2 d = gdst_of(hv);
         if (!N->dry()) launch_gn_bwd(single(hh->p, C), stats, gp->gamma, gp->beta, da, B, Hh, Ww, C, G, 0, 1, nullptr, 0, 0.f, N->partial, N->red, d, N->st);
+        if (N->pg_run) {        // the C -> 2 head over act(GroupNorm(h)), its bias, the GroupNorm
+          const WgY yp = wy(np->g, (long long)Hh * Ww, 2);
+          pg_weight(N, yp, wa_gn(single(hh->p, C), Hh, Ww, C, 9, 0, stats, *gp, G, 1), (long long)B * Hh * Ww, 2, 1, 1.f, cp->go);
+          pg_colsum(N, yp, B, 2, 1.f, nullptr, 0, cp->go + 18LL * C, -1);
+          pg_gn(N, single(hh->p, C), stats, *gp, G, 1, da, 0, B, Hh, Ww, C);
+        }
         N->arena.off = mk;
       }); }
       pyr = np; mi += 2; tap(mi - 1, pyr);
@@ -1273,9 +1466,30 @@ static void run_vjp(Net* N, const float* cot, float* gx) {
     launch_mix2(do2, N->W->out_w, nullptr, N->pyr0->g, (long long)B * Tp * Fb, 1, 0, st);
   }
   N->pyr0->ginit = 1;
+  const int nf = c.nf, DT = N->W->dense_total;
+  N->dtemb = N->pg_run ? N->tmp((long long)B * DT) : nullptr;
+  if (N->pg_run) {                  // output_layer (1x1, 2 -> 2)
+    const WgY y2 = wy(do2, (long long)Tp * Fb, 2);
+    pg_weight(N, y2, wa(single(N->pyr0->p, 2), Tp, Fb, 2, 1, 0), (long long)B * Tp * Fb, 2, 0, 1.f, N->W->out_go);
+    pg_colsum(N, y2, B, 2, 1.f, nullptr, 0, N->W->out_go + 4, -1);
+  }
   for (int i = (int)N->tape.size() - 1; i >= 0; --i) N->tape[i]();
+  if (N->pg_run) {                  // time embedding: Dense_0 of every ResBlock, then the two MLP layers (the Fourier projection W has no gradient)
+    float* dte = N->tmp((long long)B * 4 * nf);
+    float* dt1 = N->tmp((long long)B * 4 * nf);
+    if (!N->dry()) {
+      const Weights* Wt = N->W.get();
+      for (const ResW& R : Wt->res)
+        launch_linear_bwd_w(N->dtemb + R.dense_off, DT, N->k_temb, 1, B, R.cout, 4 * nf, N->pg + R.dense_go, N->pg + R.dense_go + (long long)R.cout * 4 * nf,
+                            nullptr, st);
+      launch_linear_bwd_x(N->dtemb, Wt->dense_w, N->k_temb, 1, B, DT, 4 * nf, dte, st);
+      launch_linear_bwd_w(dte, 4 * nf, N->k_t1, 1, B, 4 * nf, 4 * nf, N->pg + Wt->lin2_go, N->pg + Wt->lin2_go + 16LL * nf * nf, nullptr, st);
+      launch_linear_bwd_x(dte, Wt->lin2_w, N->k_t1, 1, B, 4 * nf, 4 * nf, dt1, st);
+      launch_linear_bwd_w(dt1, 4 * nf, N->k_four, 0, B, 4 * nf, 2 * nf, N->pg + Wt->lin1_go, N->pg + Wt->lin1_go + 8LL * nf * nf, nullptr, st);
+    }
+  }
   float* dfx = N->tmp((long long)B * T * Kp);
-  if (!N->dry()) {
+  if (!N->dry() && gx) {
     gemm_b(N, N->spec->g, 2 * Fb, (long long)Tp * 2 * Fb, false, N->W->basisF, Kp, 0, true, dfx, Kp, (long long)T * Kp, T, Kp, 2 * Fb, nullptr, nullptr,
            1.f, 0, B);
     launch_unpad_adj(dfx, Kp, T, nfft, hop, B, L, N->pad, 1.f, N->k_cin, N->k_cskip ? cot : nullptr, N->k_cskip, gx, st);
@@ -1310,7 +1524,9 @@ int net_reserve(Net* N, int B, int L, int with_vjp, long long* bytes) {
   N->vdry = 0;
   run_forward(N, nullptr, nullptr, dry_scalars, dry_scalars, dry_scalars, nullptr, B, L, with_vjp != 0);
   const int conv_fwd = N->vdry;
+  N->pg_run = with_vjp >= 2;          // the parameter VJP's workspaces
   if (with_vjp) run_vjp(N, nullptr, nullptr);
+  N->pg_run = false;
   const int conv_slots = std::max(conv_fwd, N->vdry - conv_fwd) + 1;
   const size_t need = N->arena.peak + (1 << 20);
   N->arena = saved;
@@ -1337,7 +1553,7 @@ int net_reserve(Net* N, int B, int L, int with_vjp, long long* bytes) {
     N->vmax_cap = (size_t)conv_slots * B * VMAX_SUB * VMAX_STRIDE;
   }
   N->vslot_need[0] = N->vslot_need[1] = 0;
-  N->rsv_B = B; N->rsv_L = L; N->rsv_vjp = with_vjp != 0;
+  N->rsv_B = B; N->rsv_L = L; N->rsv_vjp = with_vjp >= 2 ? 2 : with_vjp != 0;
   return BUDDY_OK;
 }
 
@@ -1348,7 +1564,8 @@ int net_forward(Net* N, const float* x, const float* cnoise, const float* cin_b,
   const int T = 1 + L / N->cfg.hop, Tp = (T + 15) / 16 * 16;
   if (Tp % (1 << (N->cfg.nlev - 1))) { set_error("frames not divisible"); return BUDDY_ERR_ARG; }
   int rc = BUDDY_OK;
-  if (!(N->rsv_B == B && N->rsv_L == L && N->rsv_vjp >= (save != 0))) rc = net_reserve(N, B, L, save, nullptr);   // host dry run only on a new shape
+  const int save_lvl = save >= 2 ? 2 : save != 0;
+  if (!(N->rsv_B == B && N->rsv_L == L && N->rsv_vjp >= save_lvl)) rc = net_reserve(N, B, L, save_lvl, nullptr);   // host dry run only on a new shape
   if (rc) return rc;
   rc = ensure_env(N, Tp);
   if (rc) return rc;
@@ -1356,6 +1573,7 @@ int net_forward(Net* N, const float* x, const float* cnoise, const float* cin_b,
   N->arena.dry = false; N->arena.overflow = false;
   if (N->opt.gemm >= 2) { HIPCHK(hipMemsetAsync(N->vmax, 0, (size_t)(N->vslot_need[0] ? N->vslot_need[0] : N->vslots) * B * VMAX_SUB * VMAX_STRIDE * 4, st)); N->vslot = 0; }
   run_forward(N, x, cnoise, cin_b, cskip_b, cout_b, y, B, L, save != 0);
+  N->pgrad = save_lvl == 2; N->tape_gen = N->W->gen;
   N->vslot_need[0] = N->vslot;
   if (N->arena.overflow) { set_error("arena overflow"); return BUDDY_ERR_STATE; }
   if (N->prep_failed) { N->prep_failed = false; return BUDDY_ERR_HIP; }
@@ -1363,12 +1581,21 @@ int net_forward(Net* N, const float* x, const float* cnoise, const float* cin_b,
   return BUDDY_OK;
 }
 
-int net_vjp(Net* N, const float* cot, float* gx, hipStream_t st) {
+int net_vjp(Net* N, const float* cot, float* gx, hipStream_t st) { return net_vjp_params(N, cot, gx, nullptr, 0, st); }
+
+// gp == null: the input VJP alone (buddy_ncsnpp_vjp).  gp: also the parameter gradients, flat in the parameter order, overwritten (accumulate 0)
+// or added to; needs a forward saved with save = 2
+int net_vjp_params(Net* N, const float* cot, float* gx, float* gp, int accumulate, hipStream_t st) {
   if (!N->have_tape) { set_error("vjp without a saved forward"); return BUDDY_ERR_STATE; }
+  if (N->tape_gen != N->W->gen) { set_error("the weights were updated (buddy_ncsnpp_update_params) after the saved forward"); return BUDDY_ERR_STATE; }
+  if (gp && !N->pgrad) { set_error("parameter VJP without a forward saved for it (save_for_vjp = 2)"); return BUDDY_ERR_STATE; }
   OptScope scope(&N->opt);
   N->st = st;
   if (N->opt.gemm >= 2) { HIPCHK(hipMemsetAsync(N->vmax, 0, (size_t)(N->vslot_need[1] ? N->vslot_need[1] : N->vslots) * N->rsv_B * VMAX_SUB * VMAX_STRIDE * 4, st)); N->vslot = 0; }
+  if (gp && !accumulate) HIPCHK(hipMemsetAsync(gp, 0, (size_t)param_count(N->cfg) * 4, st));
+  N->pg = gp; N->pg_run = gp != nullptr;
   run_vjp(N, cot, gx);
+  N->pg = nullptr; N->pg_run = false;
   N->vslot_need[1] = N->vslot;
   if (N->arena.overflow) { set_error("arena overflow"); return BUDDY_ERR_STATE; }
   if (N->prep_failed) { N->prep_failed = false; return BUDDY_ERR_HIP; }

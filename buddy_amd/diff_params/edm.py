@@ -1,6 +1,7 @@
 """EDM (Karras et al. 2022) parameterisation -- same surface as reference ``diff_params/edm.py`` (``EDM(type, sde_hp)``;
-``cskip/cout/cin/cnoise``, ``Tweedie2score``, ``score2Tweedie``, ``_mean``, ``_std``, ``_ode_integrand``, ``denoiser``).
-Training-only methods (``loss_fn``, ``sample_time_training``) are out of scope."""
+``cskip/cout/cin/cnoise``, ``Tweedie2score``, ``score2Tweedie``, ``_mean``, ``_std``, ``_ode_integrand``, ``denoiser``) and the training
+methods ``sample_time_training`` (edm.py:24-33), ``prepare_train_preconditioning`` and ``loss_fn`` (shared.py:123-160).  With the MI355X
+``NCSNppTime`` after ``requires_grad_(True)``, ``loss_fn(net, x).mean().backward()`` gives every parameter its gradient from the HIP kernels."""
 from __future__ import annotations
 
 import torch
@@ -15,6 +16,10 @@ class EDM(SDE):
         self.sigma_min = self.sde_hp.sigma_min
         self.sigma_max = self.sde_hp.sigma_max
         self.rho = self.sde_hp.rho
+
+    def sample_time_training(self, N):     # reference edm.py:24-33
+        a = torch.rand(N)
+        return (self.sigma_max ** (1 / self.rho) + a * (self.sigma_min ** (1 / self.rho) - self.sigma_max ** (1 / self.rho))) ** self.rho
 
     def sample_prior(self, shape):
         return torch.randn(shape)

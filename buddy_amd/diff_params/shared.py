@@ -1,4 +1,4 @@
-"""Diffusion parameterisation base (inference part of reference ``diff_params/shared.py:8-120``)."""
+"""Diffusion parameterisation base (reference ``diff_params/shared.py:8-160``: inference part and the training loss)."""
 from __future__ import annotations
 
 import numpy as np
@@ -51,3 +51,26 @@ class SDE:
             return y[:, None] if xn.dim() == 3 else y
         shape = (B,) + (1,) * (xn.dim() - 1)
         return cskip.view(shape) * xn + cout.view(shape) * net(cin.view(shape) * xn, cnoise)
+
+    def prepare_train_preconditioning(self, x, t, n=None, *args, **kwargs):
+        """(cin * x_perturbed, target, cnoise) for a clean batch x (B, L) and sigmas t (B,) -- reference shared.py:123-146"""
+        mu, sigma = self._mean(x, t), self._std(t).unsqueeze(-1)
+        sigma = sigma.view(*sigma.size(), *(1,) * (x.ndim - sigma.ndim))
+        if n is None:
+            n = self.sample_prior(x.shape).to(x.device)
+        x_perturbed = mu + sigma * n
+        cskip, cout, cin = self.cskip(sigma), self.cout(sigma), self.cin(sigma)
+        cnoise = self.cnoise(sigma.squeeze())
+        cnoise = cnoise.repeat(x.shape[0],) if len(cnoise.shape) == 0 else cnoise.view(x.shape[0],)
+        target = 1 / cout * (x - cskip * x_perturbed)
+        return cin * x_perturbed, target, cnoise
+
+    def loss_fn(self, net, x, n=None, *args, **kwargs):
+        """(error ** 2, sigma) of the denoiser on a clean batch x (B, L) -- reference shared.py:148-160.  ``t`` (keyword, build extension):
+        fixed sigmas instead of ``sample_time_training``."""
+        t = kwargs.get("t")
+        t = self.sample_time_training(x.shape[0]).to(x.device) if t is None else t.to(x.device)
+        input, target, cnoise = self.prepare_train_preconditioning(x, t, n=n)
+        estimate = net(input.unsqueeze(1), cnoise).squeeze(1)
+        error = estimate - target
+        return error ** 2, self._std(t)

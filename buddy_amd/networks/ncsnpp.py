@@ -4,7 +4,9 @@ reference ``networks/ncsnpp.py:455-506``) backed by the hand-written gfx950 netw
 Same surface as the reference class: constructor kwargs = ``conf/network/ncsnpp.yaml`` keys (incl. nested
 ``stft:{n_fft,hop_length,center}``), ``nn.Module`` protocol with the reference ``state_dict`` key names
 (``all_modules.N.*``, ``output_layer.*``), ``forward(x:(B,1,L) f32, time_cond:(B,) f32) -> (B,1,L)``,
-differentiable w.r.t. ``x`` (the input-VJP runs in HIP; no weight gradients -- inference only).
+differentiable w.r.t. ``x`` (the input-VJP runs in HIP).  Parameters are registered with ``requires_grad=False``; after
+``net.requires_grad_(True)`` the module is trainable: the parameter gradients run in HIP too (``buddy_ncsnpp_vjp_params``), and the
+weights an optimizer changed in place are pushed to the library at the next forward (``buddy_ncsnpp_update_params``).
 Only the shipped architecture family is supported (biggan resblocks, input_skip/sum, output_skip, the bottleneck attention plus the
 attention sites of ``attn_resolutions``;
 ``fir`` False or True with the (1,3,3,1) kernel); anything else raises ``NotImplementedError`` at construction.
@@ -36,13 +38,15 @@ def _variance_scaling_uniform(shape, scale, in_axis, out_axis):
 
 
 class _NetFn(torch.autograd.Function):
+    # params: empty (inference, input-VJP only) or every parameter in the flat order of the library (training: save = 2)
     @staticmethod
-    def forward(ctx, x, cnoise, scal, net):
+    def forward(ctx, x, cnoise, scal, net, *params):
         B, L = x.shape
         lib = _lib.require_gpu()
         x = x.contiguous()
         y = torch.empty_like(x)
-        save = 1 if ctx.needs_input_grad[0] else 0
+        ctx.train = any(ctx.needs_input_grad[4:])
+        save = 2 if ctx.train else (1 if ctx.needs_input_grad[0] else 0)
         cin = cskip = cout = None
         if scal is not None:
             cin, cskip, cout = (s.contiguous() for s in scal)
@@ -50,6 +54,7 @@ class _NetFn(torch.autograd.Function):
                                             _lib.ptr(cskip), _lib.ptr(cout), _lib.ptr(y), B, L, save, _lib.stream_ptr()))
         net._fwd_id += 1
         ctx.net, ctx.fwd_id = net, net._fwd_id
+        ctx.saved_params = params
         return y
 
     @staticmethod
@@ -59,9 +64,18 @@ class _NetFn(torch.autograd.Function):
             raise _lib.BuddyHipError("backward through a stale NCSNppTime forward: the handle keeps one tape (call "
                                      "backward before the next forward)")
         g = g.contiguous()
-        gx = torch.empty_like(g)
-        _lib.check(_lib.load().buddy_ncsnpp_vjp(net._get_handle(), _lib.ptr(g), _lib.ptr(gx), _lib.stream_ptr()))
-        return gx, None, None, None
+        if not ctx.train:
+            gx = torch.empty_like(g)
+            _lib.check(_lib.load().buddy_ncsnpp_vjp(net._get_handle(), _lib.ptr(g), _lib.ptr(gx), _lib.stream_ptr()))
+            return (gx, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 4)
+        gx = torch.empty_like(g) if ctx.needs_input_grad[0] else None
+        gp = torch.empty(net._n_params, dtype=torch.float32, device=g.device)
+        _lib.check(_lib.load().buddy_ncsnpp_vjp_params(net._get_handle(), _lib.ptr(g), _lib.ptr(gx), _lib.ptr(gp), 0, _lib.stream_ptr()))
+        grads = []
+        for (name, shape, kind, _), (off, n), p, need in zip(net._specs, net._offsets, ctx.saved_params, ctx.needs_input_grad[4:]):
+            # the Fourier projection W has no gradient (reference layerspp.py: requires_grad=False): None, so optimizers skip it
+            grads.append(gp[off:off + n].view(shape).to(p.device) if need and kind != "fourier" else None)
+        return (gx, None, None, None) + tuple(grads)
 
 
 class NCSNppTime(nn.Module):
@@ -155,6 +169,15 @@ class NCSNppTime(nn.Module):
         self._handle = None
         self._fwd_id = 0
         self._parent = None
+        self._offsets, o = [], 0
+        for _, shape, _, _ in self._specs:
+            n = int(np.prod(shape))
+            self._offsets.append((o, n))
+            o += n
+        self._n_params = o
+        self._plist = None          # the parameters in the flat order (built on first use)
+        self._watch = False         # set by the first training forward (and in deep copies): forwards check the parameters' versions
+        self._synced = None         # the parameters' _version when the library last received them
 
     @staticmethod
     def _init(name, shape, kind, init_scale, fourier_scale):
@@ -192,6 +215,7 @@ class NCSNppTime(nn.Module):
             for k, v in self._options.items():
                 _lib.check(lib.buddy_ncsnpp_set_option(h, k.encode(), int(v)))
             self._handle = h
+            self._synced = self._versions()
         if self._handle is None:
             lib = _lib.require_gpu()
             blob = np.ascontiguousarray(self._flat_params())
@@ -212,7 +236,58 @@ class NCSNppTime(nn.Module):
             for k, v in self._options.items():
                 _lib.check(lib.buddy_ncsnpp_set_option(h, k.encode(), int(v)))
             self._handle = h
+            self._synced = self._versions()
         return self._handle
+
+    # ---- training: parameters as autograd inputs, freshness after in-place optimizer steps ----------------------------
+    def _params(self):
+        if self._plist is None:
+            named = dict(self.named_parameters())
+            self._plist = [named[n] for n, *_ in self._specs]
+        return self._plist
+
+    def _versions(self):
+        return tuple(p._version for p in self._params())
+
+    def _sync_params(self, device):
+        """After an in-place change of the parameters (optimizer step, EMA update, a copy_ before fine-tuning) push them to the library's
+        weight store (``buddy_ncsnpp_update_params``: no new handle).  Watched once the module trains (any parameter requires grad), has
+        trained, or is a deep copy.  ``device``: the GPU the call runs on (its input's device)."""
+        if not self._watch and torch.is_grad_enabled() and any(p.requires_grad for p in self._params()):
+            self._watch = True          # before the check: weights changed in place while the module was not yet watched are caught too
+        if not self._watch or self._handle is None:
+            return
+        v = self._versions()
+        if v == self._synced:
+            return
+        with torch.no_grad():
+            flat = torch.cat([p.detach().reshape(-1).float().to(device) for p in self._params()])
+        _lib.check(_lib.require_gpu().buddy_ncsnpp_update_params(self._handle, _lib.ptr(flat), _lib.stream_ptr()))
+        self._synced = v
+
+    def _train_params(self):
+        """The parameters as autograd inputs when any of them requires grad (training), else ()"""
+        if not torch.is_grad_enabled():
+            return ()
+        ps = self._params()
+        if not any(p.requires_grad for p in ps):
+            return ()
+        self._watch = True
+        return tuple(ps)
+
+    def __deepcopy__(self, memo):
+        """EMA copies (reference trainer: copy.deepcopy(network)): the copy gets its own library handle on first use, never the original's"""
+        cls = self.__class__
+        new = cls.__new__(cls)
+        memo[id(self)] = new
+        for k, v in self.__dict__.items():
+            if k in ("_handle", "_parent", "_plist", "_synced"):
+                new.__dict__[k] = None
+            else:
+                new.__dict__[k] = copy.deepcopy(v, memo)
+        new._fwd_id = 0
+        new._watch = True
+        return new
 
     def set_option(self, key, value):
         """Per-handle launcher option (``buddy_ncsnpp_set_option``: fusion / layout A/B switches, attention core, GEMM arithmetic; an unknown key or
@@ -247,12 +322,14 @@ class NCSNppTime(nn.Module):
 
     def load_state_dict(self, *a, **k):
         r = super().load_state_dict(*a, **k)
+        self._plist = None
         self._drop_handle()
         self._parent = None                     # new weights: this module owns its handle again
         return r
 
     def _apply(self, fn, *a, **k):
         r = super()._apply(fn, *a, **k)
+        self._plist = None
         self._drop_handle()
         self._parent = None
         return r
@@ -279,13 +356,15 @@ class NCSNppTime(nn.Module):
         """x: (B,1,L) (reference signature) or (B,L); time_cond: (B,) = c_noise."""
         squeeze = x.dim() == 3
         x2 = x[:, 0] if squeeze else x
-        y = _NetFn.apply(x2.float(), time_cond.float().reshape(-1), None, self)
+        self._sync_params(x2.device)
+        y = _NetFn.apply(x2.float(), time_cond.float().reshape(-1), None, self, *self._train_params())
         return y[:, None] if squeeze else y
 
     def denoise_fused(self, x, cnoise, cin, cskip, cout):
         """EDM denoiser with the preconditioning scalars folded into the STFT / overlap-add kernels:
         cskip[b]*x + cout[b]*net(cin[b]*x, cnoise[b]) (reference diff_params/shared.py:98-120).  x: (B,L); rest (B,)."""
-        return _NetFn.apply(x.float(), cnoise.float(), (cin.float(), cskip.float(), cout.float()), self)
+        self._sync_params(x.device)
+        return _NetFn.apply(x.float(), cnoise.float(), (cin.float(), cskip.float(), cout.float()), self, *self._train_params())
 
     def denoise_saved(self, x, scal4):
         """The EDM denoiser (as ``denoise_fused``) WITHOUT an autograd graph: forward with the handle's VJP tape kept; pair it with ``input_vjp``.
@@ -295,6 +374,7 @@ class NCSNppTime(nn.Module):
         x = x.contiguous().float()
         B, L = x.shape
         y = torch.empty_like(x)
+        self._sync_params(x.device)
         _lib.check(lib.buddy_ncsnpp_forward(self._get_handle(), _lib.ptr(x), _lib.ptr(scal4[0]), _lib.ptr(scal4[1]), _lib.ptr(scal4[2]), _lib.ptr(scal4[3]),
                                             _lib.ptr(y), B, L, 1, _lib.stream_ptr()))
         self._fwd_id += 1           # an autograd node of an earlier forward is stale from here on

@@ -59,12 +59,27 @@ int buddy_ncsnpp_reserve(void* handle, int B, int L, int with_vjp, long long* by
 
 /* y = cskip[b]*x + cout[b]*net(cin[b]*x, cnoise[b])  if cin/cskip/cout are non-NULL (EDM denoiser,
  * reference diff_params/shared.py:98-120), else y = net(x, cnoise) (NCSNppTime.forward).
- * x, y: [B][L]; cnoise, cin, cskip, cout: [B].  save_for_vjp != 0 keeps activations for buddy_ncsnpp_vjp. */
+ * x, y: [B][L]; cnoise, cin, cskip, cout: [B].  save_for_vjp != 0 keeps activations for buddy_ncsnpp_vjp; 2 also for buddy_ncsnpp_vjp_params. */
 int buddy_ncsnpp_forward(void* handle, const float* x, const float* cnoise, const float* cin, const float* cskip,
                          const float* cout, float* y, int B, int L, int save_for_vjp, void* stream);
 
 /* grad_x = (d y / d x)^T cot for the last forward issued with save_for_vjp (includes the EDM scalars if they were given). */
 int buddy_ncsnpp_vjp(void* handle, const float* cot, float* grad_x, void* stream);
+
+/* Parameter gradients (training / fine-tuning; reference training/trainer.py:225-243 loss.backward()).  After a forward issued with
+ * save_for_vjp = 2 (the activation arena then also holds the gradient kernels' workspaces): grad_params = (d y / d params)^T cot, ONE device
+ * buffer of buddy_ncsnpp_param_count(_attn) floats in the flat parameter order that buddy_ncsnpp_create(_attn) takes (attention sites included).
+ * accumulate = 0 overwrites it, 1 adds to it.  The Fourier projection W gets zero (the reference registers it with requires_grad=False).
+ * grad_x (nullable) receives the same input gradient as buddy_ncsnpp_vjp, bit for bit.  Exact fp32 arithmetic in every GEMM mode; deterministic
+ * (split-K over fixed pixel chunks, reduced in a fixed order, no atomics).  BUDDY_ERR_STATE after a forward with save_for_vjp = 0 / 1. */
+int buddy_ncsnpp_vjp_params(void* handle, const float* cot, float* grad_x, float* grad_params, int accumulate, void* stream);
+
+/* Replace the raw weights of the handle's weight store in place (dev_params: device, same flat layout) -- e.g. after an optimizer step.  No new
+ * handle: a device copy of the parameters, one copy to the host to rebuild the small packed forms there, and every derived form (lazy 3x3 operand forms, packed 1x1 / NIN images and their stage images, the Dense_0 tables) is rebuilt or
+ * dropped.  Replicas share the store: every handle made with buddy_ncsnpp_replica from it sees the new weights at its next forward, and a forward
+ * saved by any of them before the update is refused by buddy_ncsnpp_vjp / _vjp_params (BUDDY_ERR_STATE).  No handle on the store may have work in
+ * flight on another stream while it runs. */
+int buddy_ncsnpp_update_params(void* handle, const float* dev_params, void* stream);
 
 /* debugging / per-module parity: device pointer + NHWC dims ([B][frames][bins][C]) of the output of all_modules[idx]. */
 int buddy_ncsnpp_tap(void* handle, int module_idx, const float** ptr, int dims[4]);
