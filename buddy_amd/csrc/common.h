@@ -19,12 +19,11 @@ struct Options {
   int conv;            // 3x3 convolution form: 0 by shape (F(6x6) / F(4x4) three-pass, fused F(2x2), direct), 1 direct, 2 wino2, 3 wino4
   int gemm;            // Winograd-domain GEMM arithmetic: 2 f16x2 (default: two-term f16 splits, 2^-22), 1 bf16x3 (exact split), 0 fp32 MFMA, 3 f16 (opt-in fast mode)
   int attn;            // attention core 0 .. 4 (net.hip)
-  int gn_fuse, gn_fuse_bwdin, gn_fuse_bwd, upconv, c2_fuse, attn_tr;                 // fusions of the network graph (A/B switches, default 1)
-  int attn_split, attn_nw;                                                           // fp32 attention: forced loop-split count / forward tile height (0 = by shape)
-  int igemm_epi, igemm_variant, wgemm_gen_epi, wgemm_xcdpos, wgemm_epi, wgemm_rt, wgemm_nt, gen_f16x2, gen_rows, gen_cp, gnb_nt;              // GEMM kernels
-  int wino_epi, wino_abl, wino_geo, w6_xcd, w6_nt;                                          // Winograd kernels
-  int gn_fast, gn_trips, ew_grid, c2in4, c2out_tiled;                                                   // GroupNorm / 2-channel convolutions
-  int fir_lds, op_graph;                                                             // blind operator
+  int gn_fuse, upconv, c2_fuse;                        // fusions of the network graph (default 1)
+  int attn_split, attn_nw;                             // fp32 attention: forced loop-split count / forward tile height (0 = by shape)
+  int wgemm_rt, gen_f16x2, gen_rows, gen_cp, gnb_nt;   // kernel forms of the GEMMs
+  int c2out_tiled;                                     // kernel form of the Cin -> 2 convolutions
+  int op_graph;                                        // blind operator: 0 = launch the optimisation loop eagerly instead of as a captured graph
 };
 const Options& default_options();           // process defaults (environment)
 int options_check();                        // BUDDY_ERR_ARG (+ set_error) when the environment holds an unknown BUDDY_* name or a bad value

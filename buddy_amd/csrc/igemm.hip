@@ -31,12 +31,11 @@ __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.
 // MT = 32-row MFMA tiles per wave along M: 2 -> 128-row block tile (default), 1 -> 64-row block tile for GEMMs whose 128-row
 // tiling would leave CUs idle (the operator's 4040 x 512 x 1028 DFT GEMMs are 128 tiles on 256 CUs).
 // TAG only names an instantiation (the 36-batch GEMM of the F(4x4,3x3) convolutions shows up as its own row in rocprofv3 summaries).
-template <int TAPS, bool TA, bool TB, int V = 2, int MT = 2, int TAG = 0>
+template <int TAPS, bool TA, bool TB, int MT = 2, int TAG = 0>
 __global__ __launch_bounds__(NT, 2) void igemm_kernel(const IgemmParams p) {
   static_assert(MT == 2 || !TA, "64-row tiles are only built for row-major A");
-  constexpr int NBUF = (V >= 4) ? 2 : 1;
   constexpr int BMt = 64 * MT, AR = BMt / 32;
-  constexpr int SM_MAIN = NBUF * (BMt + BN) * LDS_LD, SM_EPI = 64 * (BN + 4);
+  constexpr int SM_MAIN = (BMt + BN) * LDS_LD, SM_EPI = 64 * (BN + 4);
   __shared__ __attribute__((aligned(16))) float smem[SM_MAIN > SM_EPI ? SM_MAIN : SM_EPI];
   float* As = smem;
   float* Bs = smem + BMt * LDS_LD;
@@ -169,41 +168,18 @@ __global__ __launch_bounds__(NT, 2) void igemm_kernel(const IgemmParams p) {
     }
   };
 
-  if (V < 4) {
-    for (int kt = 0; kt < nk; ++kt) {
-      store_tile(As, ra, TA, AR);
-      store_tile(Bs, rb, TB);
-      __syncthreads();
-      if (V == 0 && kt + 1 < nk) { loadA(kt + 1, ra); loadB(kt + 1, rb); }
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        if (V == 2 && g == 1 && kt + 1 < nk) { loadA(kt + 1, ra); loadB(kt + 1, rb); }
-        if (V == 3 && g == 1 && kt + 1 < nk) loadA(kt + 1, ra);
-        if (V == 3 && g == 2 && kt + 1 < nk) loadB(kt + 1, rb);
-        mfma_group(Af, Bf, g);
-      }
-      __syncthreads();
-    }
-  } else {
-    // double-buffered LDS: one barrier per K step
-    constexpr int BUFSZ = (BMt + BN) * LDS_LD;
+  // the next tile's global loads are issued after the first quarter of the MFMA block (+4 % measured over issuing them before it,
+  // profiles/README.md; double-buffered LDS with one barrier per K step was slower: 2 blocks/CU)
+  for (int kt = 0; kt < nk; ++kt) {
     store_tile(As, ra, TA, AR);
     store_tile(Bs, rb, TB);
     __syncthreads();
-    for (int kt = 0; kt < nk; ++kt) {
-      const int cur = (kt & 1) * BUFSZ, nxt = BUFSZ - cur;
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        if (g == 1 && kt + 1 < nk) loadA(kt + 1, ra);
-        if (g == 2 && kt + 1 < nk) loadB(kt + 1, rb);
-        mfma_group(Af + cur, Bf + cur, g);
-      }
-      if (kt + 1 < nk) {
-        store_tile(As + nxt, ra, TA, AR);
-        store_tile(Bs + nxt, rb, TB);
-      }
-      __syncthreads();
+    for (int g = 0; g < 4; ++g) {
+      if (g == 1 && kt + 1 < nk) { loadA(kt + 1, ra); loadB(kt + 1, rb); }
+      mfma_group(Af, Bf, g);
     }
+    __syncthreads();
   }
 
   // epilogue.  Accumulator layout (transposed tile): m = lane&31, n = (r&3) + 8*(r>>2) + 4*(lane>>5) within a 32x32 tile.
@@ -398,8 +374,7 @@ void launch_igemm(const IgemmParams& p, int taps, bool transA, bool transB, int 
     if (p.bias_n) wide = wide && al16(p.bias_n);
     if (p.bias_bn) wide = wide && al16(p.bias_bn) && (p.ld_bias_bn % 4 == 0);
     if (p.res_mode) wide = wide && al16(p.res) && (p.ldRes % 4 == 0);
-    const bool force_scalar = cur_opt().igemm_epi == 0;   // A/B switch
-    pw.wide_epi = (wide && !force_scalar) ? 1 : 0;
+    pw.wide_epi = wide ? 1 : 0;     // the scalar epilogue is the fallback for ragged N / unaligned rows
   }
   ProfRec rec{};
   if (g_prof_on) {
@@ -411,20 +386,15 @@ void launch_igemm(const IgemmParams& p, int taps, bool transA, bool transB, int 
     (void)hipEventRecord(rec.e0, st);
   }
   struct Fin { ProfRec& r; hipStream_t s; ~Fin() { if (g_prof_on) { (void)hipEventRecord(r.e1, s); g_prof.push_back(r); } } } fin{rec, st};
-  // V: 0 = next-tile global loads issued before the MFMA block, 2 = after its first quarter (default; +4 % measured,
-  // profiles/README.md), 4 = double-buffered LDS, one barrier per K step (slower: 2 blocks/CU).  A/B switch for the 3x3 kernel:
-  const int variant = cur_opt().igemm_variant;
   if (taps == 9) {
-    if (variant == 0) hipLaunchKernelGGL((igemm_kernel<9, false, false, 0>), grid, block, 0, st, pw);
-    else if (variant == 4) hipLaunchKernelGGL((igemm_kernel<9, false, false, 4>), grid, block, 0, st, pw);
-    else hipLaunchKernelGGL((igemm_kernel<9, false, false, 2>), grid, block, 0, st, pw);
+    hipLaunchKernelGGL((igemm_kernel<9, false, false>), grid, block, 0, st, pw);
   } else if (!transA && !transB && p.tag == 36 && !small_grid) {
-    hipLaunchKernelGGL((igemm_kernel<1, false, false, 2, 2, 36>), grid, block, 0, st, pw);
+    hipLaunchKernelGGL((igemm_kernel<1, false, false, 2, 36>), grid, block, 0, st, pw);
   } else if (!transA && !transB) {
-    if (small_grid) hipLaunchKernelGGL((igemm_kernel<1, false, false, 2, 1>), grid, block, 0, st, pw);
+    if (small_grid) hipLaunchKernelGGL((igemm_kernel<1, false, false, 1>), grid, block, 0, st, pw);
     else hipLaunchKernelGGL((igemm_kernel<1, false, false>), grid, block, 0, st, pw);
   } else if (!transA && transB) {
-    if (small_grid) hipLaunchKernelGGL((igemm_kernel<1, false, true, 2, 1>), grid, block, 0, st, pw);
+    if (small_grid) hipLaunchKernelGGL((igemm_kernel<1, false, true, 1>), grid, block, 0, st, pw);
     else hipLaunchKernelGGL((igemm_kernel<1, false, true>), grid, block, 0, st, pw);
   } else if (transA && !transB) {
     hipLaunchKernelGGL((igemm_kernel<1, true, false>), grid, block, 0, st, pw);

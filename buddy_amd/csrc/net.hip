@@ -117,8 +117,9 @@ struct Arena {
   float* f(long long n) { return (float*)alloc((size_t)n * 4); }
 };
 
-// One prepared operand form of a 3x3 convolution's weights: u = fp32 (direct / Winograd-domain), x = the bf16x3 stage image of u (wgemm.hip)
-struct WVar { float* u = nullptr; void* x = nullptr; void* x2 = nullptr; void* x1 = nullptr; };   // fp32 form, bf16x3 / f16x2 / f16 (gemm = f16) stage image
+// One prepared operand form of a 3x3 convolution's weights: u = fp32 (direct / Winograd-domain), x[a] = the stage image of u in GEMM arithmetic a
+// (1 bf16x3, 2 f16x2, 3 f16: kArith below; x[0] stays null -- the fp32 GEMM reads u itself)
+struct WVar { float* u = nullptr; void* x[4] = {nullptr, nullptr, nullptr, nullptr}; };
 // raw: the torch OIHW tensor on the device.  3x3 convolutions of the ResBlocks get their operand forms LAZILY (conv_weights below): one
 // (direction, kernel variant, arithmetic) per layer is ever built for a given workload, on the GPU (wprep.hip).  wf / wb: forms prepared at
 // creation (the small 2-channel convolutions, 1x1 convolutions)
@@ -194,7 +195,7 @@ struct Net {
   const float* k_cin = nullptr; const float* k_cskip = nullptr; const float* k_cout = nullptr;
 
   int rsv_B = 0, rsv_L = 0, rsv_vjp = -1;   // shape the arena was last sized for (the sizing dry run is skipped while it still fits)
-  Options opt;                 // this handle's launcher options (options.hip): attention core, GEMM arithmetic, every A/B switch; from the environment
+  Options opt;                 // this handle's launcher options (options.hip): attention core, GEMM arithmetic, fusions and kernel forms; from the environment
                                // defaults at creation, changed with buddy_ncsnpp_set_option; the launchers read it through cur_opt() while a call runs
   bool prep_failed = false;    // a lazily prepared weight form could not be built (out of memory): the call reports it
   bool fir = false;            // fir=True: FIR (1,3,3,1) resampling instead of nearest / box (reference up_or_down_sampling.py:195-257)
@@ -591,16 +592,34 @@ void net_destroy(Net* N) {
   delete N;
 }
 
+// The arithmetics of the Winograd-domain batched GEMM, indexed by option gemm (0 fp32: the MFMA kernel of igemm.hip on the fp32 form, no stage image)
+struct GemmArith {
+  bool (*supported)(int Cout, int Cin);
+  size_t (*packed_bytes)(int P, int Cout, int Cin);
+  void (*pack_weights)(const float* U_dev, void* img, int P, int Cout, int Cin, hipStream_t st);
+};
+static const GemmArith kArith[4] = {{nullptr, nullptr, nullptr},
+                                    {wgemm_supported, wgemm_packed_bytes, wgemm_pack_weights},                          // 1 bf16x3 (wgemm.hip)
+                                    {wgemm_f16x2_supported, wgemm_f16x2_packed_bytes, wgemm_f16x2_pack_weights},        // 2 f16x2 (wgemm.hip)
+                                    {wgemm_f16_supported, wgemm_f16_packed_bytes, wgemm_f16_pack_weights}};             // 3 f16 (wgemm16.hip)
+// The arithmetic a (Cout, Cin) batched GEMM runs under the handle's gemm option: a form whose tiling does not divide the shape falls back to the next
+// more exact one (f16 -> f16x2 -> bf16x3), a shape that bf16x3 does not take runs the fp32 kernel in every mode
+static int gemm_arith(const Net* N, int Cout, int Cin) {
+  int a = wgemm_supported(Cout, Cin) ? N->opt.gemm : 0;
+  while (a > 1 && !kArith[a].supported(Cout, Cin)) --a;
+  return a;
+}
+
 // The operand form `kind` (0 direct, 2 / 4 / 6 = Winograd F(kind x kind, 3x3), 61 = F(6x6,3x3) of the sub-pixel up form) of a 3x3 convolution for one direction, built on first use on
-// the GPU from the raw OIHW tensor (wprep.hip) and cached in the shared store.  want_x: 1 the bf16x3 / 2 the f16x2 stage image (the fp32 form is then only a
-// staging buffer, reused for the next layer); 3: the f16 stage image (wgemm16.hip, gemm = f16); 0: the fp32 form itself is kept.  The preparing stream is drained before the pointer is
+// the GPU from the raw OIHW tensor (wprep.hip) and cached in the shared store.  want_x: the arithmetic whose stage image is wanted (kArith; the fp32 form is then
+// only a staging buffer, reused for the next layer); 0: the fp32 form itself is kept.  The preparing stream is drained before the pointer is
 // published, so a replica on another stream may use it at once.
 static const WVar* conv_weights(Net* N, const ConvW& c, bool dgrad, int kind, int want_x) {
   Weights* Wt = N->W.get();
   const int ki = kind == 0 ? 0 : kind == 2 ? 1 : kind == 4 ? 2 : kind == 6 ? 3 : 4;
   WVar& v = c.var[dgrad ? 1 : 0][ki];
   std::lock_guard<std::mutex> lk(Wt->mu);
-  if (want_x == 3 ? v.x1 != nullptr : want_x == 2 ? v.x2 != nullptr : want_x ? v.x != nullptr : v.u != nullptr) return &v;
+  if (want_x ? v.x[want_x] != nullptr : v.u != nullptr) return &v;
   const int ph = kind == 61 ? 4 : 1;                          // sub-pixel up form: four phase kernels per output channel (wprep.hip)
   const int Co = dgrad ? c.cin : ph * c.cout, Ci = dgrad ? ph * c.cout : c.cin;
   const size_t nfl = (size_t)conv3_weight_floats(c.cout, c.cin, kind);
@@ -624,15 +643,13 @@ static const WVar* conv_weights(Net* N, const ConvW& c, bool dgrad, int kind, in
   void* x = nullptr;
   if (want_x) {
     const int P = kind == 4 ? 36 : 64;
-    const size_t bytes = want_x == 3 ? wgemm_f16_packed_bytes(P, Co, Ci) : want_x == 2 ? wgemm_f16x2_packed_bytes(P, Co, Ci) : wgemm_packed_bytes(P, Co, Ci);
+    const size_t bytes = kArith[want_x].packed_bytes(P, Co, Ci);
     if (hipMalloc(&x, bytes) != hipSuccess) { N->prep_failed = true; set_error("out of memory preparing convolution weights"); return nullptr; }
     Wt->lazy_allocs.push_back(x); Wt->lazy_bytes += bytes;
-    if (want_x == 3) wgemm_f16_pack_weights(u, x, P, Co, Ci, st);
-    else if (want_x == 2) wgemm_f16x2_pack_weights(u, x, P, Co, Ci, st);
-    else wgemm_pack_weights(u, x, P, Co, Ci, st);
+    kArith[want_x].pack_weights(u, x, P, Co, Ci, st);
   }
   (void)hipStreamSynchronize(st);
-  if (want_x == 3) v.x1 = x; else if (want_x == 2) v.x2 = x; else if (want_x) v.x = x; else v.u = u;
+  if (want_x) v.x[want_x] = x; else v.u = u;
   ++Wt->lazy_count;
   return &v;
 }
@@ -688,7 +705,7 @@ static unsigned* vmax_slot(Net* N, int B) {
 static bool conv3_up_ok(Net* N, int B, int H, int W, int Cin, int Cout) {
   if (H < 7 || W < 7) return false;
   const Options& o = N->opt;
-  const bool on = o.conv == 0 && o.gn_fuse && o.gn_fuse_bwdin && o.gn_fuse_bwd && o.upconv;     // A/B switches
+  const bool on = o.conv == 0 && o.gn_fuse && o.upconv;
   if (!on || Cin % 8 || Cout % 8 || H < 6 || W < 6) return false;
   IgemmParams p = ig_base();
   p.ldA0 = Cin; p.Cin = Cin; p.H = H; p.W = W; p.M = B * H * W; p.N = Cout; p.ldC = Cout; p.ld_bias_bn = 4;
@@ -723,9 +740,7 @@ static int conv3(Net* N, const Conv3& c) {
     IgemmParams p = ig_base();
     p.A0 = a; p.ldA0 = Cin; p.Cin = Cin; p.H = H; p.W = W; p.M = B * H * W; p.N = Cout; p.C = c.out; p.ldC = Cout;
     p.bias_n = c.bias; p.bias_bn = c.bias_bn; p.ld_bias_bn = c.ld_bn; p.rows_per_batch = H * W; p.alpha = c.alpha; p.out_scale = c.out_scale;
-    int x3 = wgemm_supported((c.up == 1 ? 4 : 1) * Cout, (c.up == 2 ? 4 : 1) * Cin) ? N->opt.gemm : 0;     // 1 bf16x3, 2 f16x2, 3 f16
-    if (x3 == 3 && !wgemm_f16_supported((c.up == 1 ? 4 : 1) * Cout, (c.up == 2 ? 4 : 1) * Cin)) x3 = 2;       // what mode 2 runs
-    if (x3 == 2 && !wgemm_f16x2_supported((c.up == 1 ? 4 : 1) * Cout, (c.up == 2 ? 4 : 1) * Cin)) x3 = 1;
+    const int x3 = gemm_arith(N, (c.up == 1 ? 4 : 1) * Cout, (c.up == 2 ? 4 : 1) * Cin);
     const WVar* wv = conv_weights(N, *c.w, c.dgrad, 61, x3);
     unsigned* vm = x3 == 2 ? vmax_slot(N, B) : nullptr;
     if (x3 == 2 && !vm) return -1;
@@ -738,7 +753,7 @@ static int conv3(Net* N, const Conv3& c) {
     const double xr = wino6_exec_ratio(p, c.up);
     igemm_prof_record(pr, 9, 1, N->st, true, xr);
     launch_wino6(p, wv->u, N->w4_scratch, N->w4_scratch + vf, N->st, gn, stat ? N->partial : nullptr, (stat && want_bwd) ? bwd_gn : nullptr,
-                 x3 == 3 ? wv->x1 : x3 == 2 ? wv->x2 : x3 ? wv->x : nullptr, c.up, x3, vm);
+                 wv->x[x3], c.up, x3, vm);
     igemm_prof_record(pr, 9, 1, N->st, false, xr);
     if (stat && (want_bwd || direct)) return sc;
     if (stat && stat_out) { launch_csum_collapse(N->partial, sc, B, Cout, stat_out->csum, N->st); stat_out->has_csum = true; }
@@ -752,8 +767,7 @@ static int conv3(Net* N, const Conv3& c) {
   const bool fuse_gn = N->opt.gn_fuse != 0;
   const bool w6 = use_wino6 && wino_ok && N->w4_scratch != nullptr && wino6_supported(p) && wino6_pays(p);
   const bool w4 = !w6 && use_wino4 && wino_ok && N->w4_scratch != nullptr && wino4_supported(p);
-  const bool fuse_bwd_in = N->opt.gn_fuse_bwdin != 0;
-  if (gn != nullptr && gn->da != nullptr && !(w6 && fuse_gn && fuse_bwd_in)) {       // GroupNorm backward as the input: only F(6x6,3x3) fuses it
+  if (gn != nullptr && gn->da != nullptr && !(w6 && fuse_gn)) {       // GroupNorm backward as the input: only F(6x6,3x3) fuses it
     Dst2 d; d.p0 = gn_tmp; d.p1 = nullptr; d.C0 = Cin; d.ld0 = Cin; d.ld1 = 0; d.acc0 = 0; d.acc1 = 0;
     launch_gn_bwd_apply(gn->x, gn->stats, gn->gamma, gn->beta, gn->da, B, H, W, Cin, gn->G, 0, gn->silu, nullptr, 0, 0.f, gn->red, d, N->st);
     p.A0 = gn_tmp; gn = nullptr;
@@ -762,19 +776,15 @@ static int conv3(Net* N, const Conv3& c) {
     launch_gn_apply(gn->x, gn->stats, gn->gamma, gn->beta, B, H, W, Cin, gn->G, 0, gn->silu, gn_tmp, nullptr, N->st);
     p.A0 = gn_tmp; gn = nullptr;
   }
-  const bool x3 = N->opt.gemm >= 1 && wgemm_supported(Cout, Cin);     // the batched GEMM pass in split arithmetic: only the stage image is needed
+  const int xf = gemm_arith(N, Cout, Cin);     // != 0: the batched GEMM pass in split arithmetic, only the stage image is needed
   if (w6) {
-    int xf = !x3 ? 0 : N->opt.gemm;                                                                        // 1 bf16x3, 2 f16x2, 3 f16
-    if (xf == 3 && !wgemm_f16_supported(Cout, Cin)) xf = 2;                                                // what mode 2 runs
-    if (xf == 2 && !wgemm_f16x2_supported(Cout, Cin)) xf = 1;
     const WVar* wv = conv_weights(N, *c.w, c.dgrad, 6, xf);
     if (!wv) return -1;
     unsigned* vm = xf == 2 ? vmax_slot(N, B) : nullptr;
     if (xf == 2 && !vm) return -1;
-    const float* U6 = wv->u; const void* U6x = xf == 3 ? wv->x1 : xf == 2 ? wv->x2 : xf ? wv->x : nullptr;
+    const float* U6 = wv->u; const void* U6x = wv->x[xf];
     long long vf = 0, mf = 0; wino6_scratch(p, &vf, &mf);
-    const bool fuse_bwd = N->opt.gn_fuse_bwd != 0;
-    const bool want_bwd = bwd_gn != nullptr && fuse_gn && fuse_bwd;
+    const bool want_bwd = bwd_gn != nullptr && fuse_gn;
     const int sc = ((stat_out != nullptr && fuse_gn) || want_bwd) ? wino6_stat_chunks(p) : 0;
     const bool stat = sc > 0 && (long long)sc * Cout <= 256LL * 1024;
     const double xr = wino6_exec_ratio(p);
@@ -784,9 +794,10 @@ static int conv3(Net* N, const Conv3& c) {
     if (stat && (want_bwd || direct)) return sc;
     if (stat && stat_out) { launch_csum_collapse(N->partial, sc, B, Cout, stat_out->csum, N->st); stat_out->has_csum = true; }
   } else if (w4) {
-    const WVar* wv = conv_weights(N, *c.w, c.dgrad, 4, x3 ? 1 : 0);       // F(4x4,3x3): the small layers stay on bf16x3 in both split modes
+    const int x4 = xf ? 1 : 0;                                            // F(4x4,3x3): the small layers stay on bf16x3 in every split mode
+    const WVar* wv = conv_weights(N, *c.w, c.dgrad, 4, x4);
     if (!wv) return -1;
-    const float* U4 = wv->u; const void* U4x = x3 ? wv->x : nullptr;
+    const float* U4 = wv->u; const void* U4x = wv->x[x4];
     long long vf = 0, mf = 0; wino4_scratch(p, &vf, &mf);
     const int sc = (stat_out != nullptr && fuse_gn) ? wino4_stat_chunks(p) : 0;
     const bool stat = sc > 0 && (long long)sc * Cout <= 256LL * 1024;     // N->partial holds 256 x 1024 (chunk, channel) pairs per utterance
@@ -795,13 +806,13 @@ static int conv3(Net* N, const Conv3& c) {
     igemm_prof_record(p, 9, 1, N->st, false, 0.25);
     if (stat) { launch_csum_collapse(N->partial, sc, B, Cout, stat_out->csum, N->st); stat_out->has_csum = true; }
   } else if (use_wino && wino_ok && wino_supported(p)) {
-    const WVar* wv = conv_weights(N, *c.w, c.dgrad, 2, false);
+    const WVar* wv = conv_weights(N, *c.w, c.dgrad, 2, 0);
     if (!wv) return -1;
     igemm_prof_record(p, 9, 1, N->st, true);
     launch_wino(p, wv->u, N->st);
     igemm_prof_record(p, 9, 1, N->st, false);
   } else {
-    const WVar* wv = conv_weights(N, *c.w, c.dgrad, 0, false);
+    const WVar* wv = conv_weights(N, *c.w, c.dgrad, 0, 0);
     if (!wv) return -1;
     p.Bt = wv->u;
     launch_igemm(p, 9, false, false, 1, N->st);
@@ -947,7 +958,7 @@ static Tens* resblock(Net* N, const ResW& R, View x, int mode, const float* temb
       // (wgemm.hip GNB): the block's input gradient in one launch, neither the 1x1 result nor a separate apply pass in HBM
       const W3Img* c2i = nullptr;
       const float* c2a = dout;                               // A operand of that GEMM (the pooled gradient for the sub-pixel up block)
-      const bool fuse_c2_on = n->opt.c2_fuse != 0;     // A/B switch
+      const bool fuse_c2_on = n->opt.c2_fuse != 0;
       if (fuse_c2_on && Rp->has_c2 && !firm && (mode == 0 || (mode == 2 && up6)) && n->opt.gemm >= 1 && Cin % 4 == 0 && (Cin / G0) % 4 == 0) {
         const auto it = n->W->w3.find(Rp->c2.wb);
         if (it != n->W->w3.end() && it->second.N == Cin && it->second.K == Cout && wgemm_gnbwd_supported(Cin, Cout, Cout, src_of(x), d0, dout, dout))
@@ -1219,8 +1230,7 @@ static Tens* attnblock(Net* N, const AttnW& A, Tens* x, bool rec) {
       float* dq = n->tmp(B * TC); float* dk = n->tmp(B * TC); float* dhn = n->tmp(B * TC);
       // P^T and dS^T by a tiled transpose (T % 32 == 0): the two products that need them then take the row-major-A kernel (and its half-height tiles when
       // the grid is small) instead of the doubly transposed one (272 us per launch at B = 8 against 41 + ~150)
-      const bool use_tr = n->opt.attn_tr != 0;     // A/B switch
-      const bool tr = use_tr && T % 32 == 0;
+      const bool tr = T % 32 == 0;
       float* Tr = tr ? n->tmp(B * TT) : nullptr;
       gemm_b(n, dout, C, 0, false, Ap->Wn[3], C, 0, false, dO, C, 0, B * T, C, C, nullptr, nullptr, INV_SQRT2, 0, 1);
       gemm_b(n, dO, C, TC, false, vT, T, TC, true, dP, T, TT, T, T, C, nullptr, nullptr, 1.f, 0, B);        // dP = dO V^T

@@ -78,70 +78,9 @@ __global__ __launch_bounds__(256) void fir_adjx_kernel(const float* GY, const fl
     reinterpret_cast<float2*>(GX + ((long long)u * T + t) * LDSP)[f] = make_float2(ar, ai);
   }
 }
-// GH[u][k][f] (+)= sum_t conj(X[t + 1 - k]) * GY[t]
-// A thread owns FOUR consecutive taps k0..k0+3 of one (utterance, bin) and one QUARTER of the frame range (per frame: one GY load and
-// one new X frame, the other three slide through registers); the four partial sums are added in fixed order through LDS.
-constexpr int GH_SEG = 4, GH_F = 64;
-__global__ __launch_bounds__(256) void fir_gradh_kernel(const float* X, long long xs, const float* GY, float* GH, int U, int T, int Nf, int accumulate) {
-  __shared__ float2 red[GH_SEG][FT][GH_F];
-  const int KG = (Nf + FT - 1) / FT, FGn = (FB + GH_F - 1) / GH_F;
-  const int fl = threadIdx.x & (GH_F - 1), seg = threadIdx.x / GH_F;
-  const int fg = blockIdx.x % FGn, kg = (blockIdx.x / FGn) % KG, u = blockIdx.x / (FGn * KG);
-  const int f = fg * GH_F + fl, k0 = kg * FT;
-  const bool ok = f < FB;
-  const float2* Xu = reinterpret_cast<const float2*>(X + (long long)u * xs) + (ok ? f : 0);
-  const float2* Gu = reinterpret_cast<const float2*>(GY + (long long)u * T * LDSP) + (ok ? f : 0);
-  auto ldx = [&](int tt) { return (tt >= 0 && tt < T) ? Xu[(long long)tt * (LDSP / 2)] : make_float2(0.f, 0.f); };
-  float ar[FT], ai[FT];
-#pragma unroll
-  for (int j = 0; j < FT; ++j) { ar[j] = 0.f; ai[j] = 0.f; }
-  const int ts = k0 > 0 ? k0 - 1 : 0;                       // first frame with a non-negative index for tap k0
-  const int len = (T - ts + GH_SEG - 1) / GH_SEG;
-  int t = ts + seg * len;
-  const int te = (t + len < T) ? t + len : T;
-  float2 w[FT];                                             // window w[j] = X[t + 1 - k0 - j]
-#pragma unroll
-  for (int j = 0; j < FT; ++j) w[j] = ldx(t + 1 - k0 - j);
-  for (; t + 8 <= te; t += 8) {                             // eight frames per trip: all 16 loads are issued before the arithmetic
-    float2 g8[8], x8[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) { g8[q] = Gu[(long long)(t + q) * (LDSP / 2)]; x8[q] = ldx(t + q + 2 - k0); }
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-#pragma unroll
-      for (int j = 0; j < FT; ++j) { ar[j] += w[j].x * g8[q].x + w[j].y * g8[q].y; ai[j] += w[j].x * g8[q].y - w[j].y * g8[q].x; }
-#pragma unroll
-      for (int j = FT - 1; j > 0; --j) w[j] = w[j - 1];
-      w[0] = x8[q];
-    }
-  }
-  for (; t < te; ++t) {
-    const float2 g = Gu[(long long)t * (LDSP / 2)];
-#pragma unroll
-    for (int j = 0; j < FT; ++j) { ar[j] += w[j].x * g.x + w[j].y * g.y; ai[j] += w[j].x * g.y - w[j].y * g.x; }
-#pragma unroll
-    for (int j = FT - 1; j > 0; --j) w[j] = w[j - 1];
-    w[0] = ldx(t + 2 - k0);
-  }
-#pragma unroll
-  for (int j = 0; j < FT; ++j) red[seg][j][fl] = make_float2(ar[j], ai[j]);
-  __syncthreads();
-  if (seg == 0 && ok) {
-#pragma unroll
-    for (int j = 0; j < FT; ++j) {
-      if (k0 + j >= Nf) continue;
-      float r = red[0][j][fl].x, im = red[0][j][fl].y;
-#pragma unroll
-      for (int sg = 1; sg < GH_SEG; ++sg) { r += red[sg][j][fl].x; im += red[sg][j][fl].y; }
-      float2* o = reinterpret_cast<float2*>(GH + ((long long)u * Nf + k0 + j) * LDSP) + f;
-      if (accumulate) { r += o->x; im += o->y; }
-      *o = make_float2(r, im);
-    }
-  }
-}
 
-// ---- LDS-staged forms of the two FIR kernels of the optimisation loop (round 3).  The register-tiled kernels above re-load every X / H value
-// from L2 once per 4 complex MACs and sit at 12 % of the VALU rate on dependent loads (8 frames per thread instead of 4 changed nothing: latency, not
+// ---- LDS-staged forms of the two FIR kernels of the optimisation loop (round 3).  The register-tiled kernel above (and the tap-gradient one that went with
+// it, retired) re-loads every X / H value from L2 once per 4 complex MACs and sits at 12 % of the VALU rate on dependent loads (8 frames per thread instead of 4 changed nothing: latency, not
 // bytes); here a workgroup stages its (frames x 32 bins) slab once, the tap loop reads LDS only (two conflict-free ds_read_b64 per 8 complex MACs).
 typedef float v2f __attribute__((ext_vector_type(2)));
 // complex multiply-accumulate as TWO packed fmas (v_pk_fma_f32): acc += h.x * (w.x, w.y); acc += h.y * (-w.y, w.x)   [h * w]
@@ -1411,10 +1350,7 @@ struct BlindOp {
     istft_adj(gh0, Nf + 2, WIN, env_c, Lh, 1.f, GFin);
   }
   void update_H() { cons_forward(); }
-  bool fir_lds_ok() const {
-    const bool lds = cur_opt().fir_lds != 0;
-    return lds && big_lds && Nf == FIR_NF;
-  }
+  bool fir_lds_ok() const { return big_lds && Nf == FIR_NF; }
   // Y0 = FIR(X0, H) and, when X1b is given, Y1 = FIR(X1b, H) in the same launch (LDS kernel only)
   void fir2(const float* X0, long long xs0, int T0, float* Y0, const float* X1b, long long xs1, int T1, float* Y1) {
     FirSegs sg; std::memset(&sg, 0, sizeof(sg));
@@ -1435,10 +1371,7 @@ struct BlindOp {
     hipLaunchKernelGGL(fir_gradh_lds_kernel, dim3((FB + FL_BINS - 1) / FL_BINS, U, (Nf + GL_TAPS - 1) / GL_TAPS), dim3(256), 0, st, sg, GH, Nf, accumulate);
   }
   void gradh(const float* X, long long xs, const float* GY, int Tn, int accumulate) {
-    const bool lds = cur_opt().fir_lds != 0;
-    if (lds) gradh2(X, xs, GY, Tn, nullptr, 0, nullptr, 0, accumulate);
-    else
-      hipLaunchKernelGGL(fir_gradh_kernel, dim3(U * ((Nf + FT - 1) / FT) * ((FB + GH_F - 1) / GH_F)), dim3(256), 0, st, X, xs, GY, GH, U, Tn, Nf, accumulate);
+    gradh2(X, xs, GY, Tn, nullptr, 0, nullptr, 0, accumulate);
   }
   // ---- loss slots ----
   static bool is_td(const LossDesc& d) { return d.kind == LK_L2_SUM || d.kind == LK_L2_MEAN; }

@@ -908,7 +908,7 @@ __global__ __launch_bounds__(256) void unpad_adj_kernel(const float* dframes, in
 
 inline int grid_for(long long total) {
   long long g = (total + 255) / 256;
-  const long long cap = 1LL << cur_opt().ew_grid;            // option ew_grid (default 16: 58.2 -> 58.0 ms/step A/B, results identical): 12 = rounds 1-5 (4096 workgroups, long grid-stride loops)
+  const long long cap = 1LL << 16;                           // 58.2 -> 58.0 ms/step A/B against 4096 workgroups with long grid-stride loops, results identical
   if (g > cap) g = cap;
   if (g < 1) g = 1;
   return (int)g;
@@ -985,12 +985,12 @@ int gn_num_chunks(int HW) {
   return c;
 }
 
-static GnFast gn_fast(int HW, int C, int G) {
+static GnFast gn_m0_geo(int HW, int C, int G) {
   GnFast a; a.HW = HW; a.C = C; a.G = G; a.q = C / 4; a.pl = 256 / a.q; if (a.pl < 1) a.pl = 1;
-  // pixels per thread = option gn_trips (default 4 since round 6: short-lived workgroups, like the one-shot copy of the streaming ubench: 4.34 -> 4.54 TB/s for the
-  // GroupNorm group; 32 = rounds 2-5: ~4096 workgroups over the batch at the big layers, 8 trips of 4 pixels per thread).  Elementwise kernels: results identical.
-  const int trips = cur_opt().gn_trips;
-  int chunks = HW / (a.pl * trips); if (chunks < 1) chunks = 1; if (chunks > (trips >= 32 ? 512 : 32768)) chunks = trips >= 32 ? 512 : 32768;
+  // 4 pixels per thread: short-lived workgroups, like the one-shot copy of the streaming ubench (4.34 -> 4.54 TB/s for the GroupNorm group against 32 pixels
+  // per thread in ~4096 workgroups over the batch at the big layers).  Elementwise kernels: results identical.
+  constexpr int trips = 4;
+  int chunks = HW / (a.pl * trips); if (chunks < 1) chunks = 1; if (chunks > 32768) chunks = 32768;
   a.ppc = (HW + chunks - 1) / chunks;
   a.ppc = (a.ppc + a.pl - 1) / a.pl * a.pl;
   return a;
@@ -1036,9 +1036,8 @@ void launch_gn_apply(Src2 x, const float* stats, const float* gamma, const float
   const long long total = (long long)B * (mode == 1 ? (H / 2) * (W / 2) : H * W) * (C / 4);
   const double n_in = (double)B * H * W * C, n_out = mode == 1 ? n_in / 4 : (mode == 2 ? n_in * 4 : n_in);
   prof_hbm_begin(4.0 * (n_in + n_out + (pooled_raw ? n_out : 0.0)), st);   // read x, write the (resampled) activation
-  const bool fast = cur_opt().gn_fast != 0;
-  if (fast && mode == 0 && C % 4 == 0 && C / 4 <= 256) {
-    GnFast a = gn_fast(H * W, C, G);
+  if (mode == 0 && C % 4 == 0 && C / 4 <= 256) {
+    GnFast a = gn_m0_geo(H * W, C, G);
     hipLaunchKernelGGL(gn_apply_m0_kernel, dim3((H * W + a.ppc - 1) / a.ppc, B), dim3(a.q * a.pl), 0, st, x, stats, gamma, beta, a, silu, out);
   } else {
     hipLaunchKernelGGL(gn_apply_kernel, dim3(grid_for(total)), dim3(256), 0, st, x, stats, gamma, beta, B, H, W, C, G, mode, silu, out, pooled_raw);
@@ -1067,9 +1066,8 @@ void launch_gn_bwd_apply(Src2 x, const float* stats, const float* gamma, const f
   // reads x and da again, writes dx (+ reads the extra gradient)
   prof_hbm_begin(4.0 * (n_in + n_da + n_in + (extra_mode ? (extra_mode == 2 ? n_in / 4 : n_in) : 0.0)), st);
   const long long total = (long long)B * H * W * (C / 4);
-  const bool fast = cur_opt().gn_fast != 0;
-  if (fast && mode == 0 && extra_mode != 2 && C % 4 == 0 && C / 4 <= 256) {
-    GnFast g = gn_fast(H * W, C, G);
+  if (mode == 0 && extra_mode != 2 && C % 4 == 0 && C / 4 <= 256) {
+    GnFast g = gn_m0_geo(H * W, C, G);
     const bool ex = extra_mode == 1 && extra != nullptr, acc = dx.acc0 != 0 || (dx.p1 != nullptr && dx.acc1 != 0);
     const dim3 grid((H * W + g.ppc - 1) / g.ppc, B), block(g.q * g.pl);
 #define GN_M0(E, A) hipLaunchKernelGGL((gn_bwd_apply_m0_kernel<E, A>), grid, block, 0, st, x, stats, gamma, beta, da, g, silu, ex ? extra : nullptr, extra_scale, red, dx)
@@ -1140,8 +1138,7 @@ void launch_conv_c2in(const float* x, const float* w, const float* bias, const f
     const int ppb = 256 / (Cout / 4);
     long long g = ((long long)B * H * W + ppb - 1) / ppb;
     if (g > 256 * 8) g = 256 * 8;
-    const bool four = cur_opt().c2in4 != 0;
-    if (taps == 9 && four && W % 4 == 0) {
+    if (taps == 9 && W % 4 == 0) {
       long long g4 = ((long long)B * H * (W / 4) + ppb - 1) / ppb;
       if (g4 > 256 * 16) g4 = 256 * 16;
       hipLaunchKernelGGL(conv_c2in_reg4_kernel, dim3((int)g4), dim3(256), 0, st, x, w, bias, add, add_ld, y, ldY, B, H, W, Cout, accumulate);

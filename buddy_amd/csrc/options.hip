@@ -1,12 +1,13 @@
 // Per-handle options of the launchers -- the ONE place the BUDDY_* environment is read.
 //
-// Every A/B switch a launcher consults is a field of `Options`.  A network handle carries its own copy (Net::opt, changed with
+// Every switch a launcher consults is a field of `Options`.  A network handle carries its own copy (Net::opt, changed with
 // buddy_ncsnpp_set_option(handle, key, value)); while one of its calls runs, an OptScope makes that copy the calling thread's current options, which is
 // what the launchers read (cur_opt()).  Outside a handle call -- the single-kernel entry points of the unit tests -- the process defaults apply.
 // The process defaults come from the environment, parsed and VALIDATED once: a value outside its range, or a BUDDY_* name that is a NEAR MISS of a
 // switch of this table (edit distance <= 2: BUDDY_UPCONVV, BUDDY_GN_FUSED), makes every handle creation (and buddy_option_check) fail with a message
 // naming it -- a misspelt switch is never silently ignored.  A BUDDY_* name that resembles none of them (BUDDY_ROOT, BUDDY_DATA: the project is
-// called BUDDy) belongs to somebody else: it is left alone, with one note on stderr.
+// called BUDDy) belongs to somebody else: it is left alone, with one note on stderr.  The A/B switches whose experiment is settled were retired with the
+// kernel variants only they reached (kRetiredEnv): setting one is an error too, so that a script that still does never quietly measures the default.
 #include "common.h"
 #include "net.h"
 #include <cstdlib>
@@ -36,37 +37,23 @@ const Entry kTable[] = {
     {"gemm", "BUDDY_GEMM", &Options::gemm, 0, 3, 2, kGemmWords},
     {"attention", "BUDDY_ATTN", &Options::attn, 0, 4, 4, kAttnWords},
     {"gn_fuse", "BUDDY_GN_FUSE", &Options::gn_fuse, 0, 1, 1, nullptr},
-    {"gn_fuse_bwdin", "BUDDY_GN_FUSE_BWDIN", &Options::gn_fuse_bwdin, 0, 1, 1, nullptr},
-    {"gn_fuse_bwd", "BUDDY_GN_FUSE_BWD", &Options::gn_fuse_bwd, 0, 1, 1, nullptr},
     {"upconv", "BUDDY_UPCONV", &Options::upconv, 0, 1, 1, nullptr},
     {"c2_fuse", "BUDDY_C2_FUSE", &Options::c2_fuse, 0, 1, 1, nullptr},
-    {"attn_tr", "BUDDY_ATTN_TR", &Options::attn_tr, 0, 1, 1, nullptr},
     {"attn_split", "BUDDY_ATTN_SPLIT", &Options::attn_split, 0, 4096, 0, nullptr},
     {"attn_nw", "BUDDY_ATTN_NW", &Options::attn_nw, 0, 8, 0, nullptr},
-    {"igemm_epi", "BUDDY_IGEMM_EPI", &Options::igemm_epi, 0, 1, 1, nullptr},
-    {"igemm_variant", "BUDDY_IGEMM_VARIANT", &Options::igemm_variant, 0, 2, 2, nullptr},
-    {"wgemm_gen_epi", "BUDDY_WGEMM_GEN_EPI", &Options::wgemm_gen_epi, 0, 1, 1, nullptr},
-    {"wgemm_xcdpos", "BUDDY_WGEMM_XCDPOS", &Options::wgemm_xcdpos, 0, 1, 1, nullptr},
-    {"wgemm_epi", "BUDDY_WGEMM_EPI", &Options::wgemm_epi, 0, 1, 1, nullptr},
     {"wgemm_rt", "BUDDY_WGEMM_RT", &Options::wgemm_rt, 0, 2, 0, nullptr},
-    {"wgemm_nt", "BUDDY_WGEMM_NT", &Options::wgemm_nt, 0, 3, 0, nullptr},
     {"gen_f16x2", "BUDDY_GEN_F16X2", &Options::gen_f16x2, 0, 2, 1, nullptr},
     {"gen_rows", "BUDDY_GEN_ROWS", &Options::gen_rows, 0, 64, 0, nullptr},
     {"gen_cp", "BUDDY_GEN_CP", &Options::gen_cp, 0, 2, 1, nullptr},
     {"gnb_nt", "BUDDY_GNB_NT", &Options::gnb_nt, 0, 1, 1, nullptr},
-    {"wino_epi", "BUDDY_WINO_EPI", &Options::wino_epi, 0, 1, 1, nullptr},
-    {"wino_abl", "BUDDY_WINO_ABL", &Options::wino_abl, 0, 3, 0, nullptr},
-    {"wino_geo", "BUDDY_WINO_GEO", &Options::wino_geo, 42, 82, 42, nullptr},
-    {"w6_xcd", "BUDDY_W6_XCD", &Options::w6_xcd, 0, 1, 1, nullptr},
-    {"w6_nt", "BUDDY_W6_NT", &Options::w6_nt, 0, 1, 1, nullptr},
-    {"gn_fast", "BUDDY_GN_FAST", &Options::gn_fast, 0, 1, 1, nullptr},
-    {"ew_grid", "BUDDY_EW_GRID", &Options::ew_grid, 8, 22, 16, nullptr},
-    {"gn_trips", "BUDDY_GN_TRIPS", &Options::gn_trips, 1, 64, 4, nullptr},
-    {"c2in4", "BUDDY_C2IN4", &Options::c2in4, 0, 1, 1, nullptr},
     {"c2out_tiled", "BUDDY_C2OUT_TILED", &Options::c2out_tiled, 0, 2, 2, nullptr},
-    {"fir_lds", "BUDDY_FIR_LDS", &Options::fir_lds, 0, 1, 1, nullptr},
     {"op_graph", "BUDDY_OP_GRAPH", &Options::op_graph, 0, 1, 1, nullptr},
 };
+// environment names of the retired A/B switches (their keys are plain unknown options)
+const char* const kRetiredEnv[] = {
+    "BUDDY_GN_FUSE_BWDIN", "BUDDY_GN_FUSE_BWD", "BUDDY_ATTN_TR", "BUDDY_IGEMM_EPI", "BUDDY_IGEMM_VARIANT", "BUDDY_WGEMM_GEN_EPI", "BUDDY_WGEMM_XCDPOS",
+    "BUDDY_WGEMM_EPI", "BUDDY_WGEMM_NT", "BUDDY_WINO_EPI", "BUDDY_WINO_ABL", "BUDDY_WINO_GEO", "BUDDY_W6_XCD", "BUDDY_W6_NT", "BUDDY_GN_FAST",
+    "BUDDY_EW_GRID", "BUDDY_GN_TRIPS", "BUDDY_C2IN4", "BUDDY_FIR_LDS"};
 // environment variables that are not launcher options (read elsewhere: the profiling dump path below, the bench driver)
 const char* const kOtherEnv[] = {"BUDDY_PROF_DUMP", "BUDDY_BENCH_PROF"};
 
@@ -111,6 +98,9 @@ const Defaults& defaults() {
         else r.opt.*(e.field) = v;
       }
       if (known) continue;
+      bool retired = false;
+      for (const char* o : kRetiredEnv) retired = retired || name == o;
+      if (retired) { if (r.error.empty()) r.error = "environment: " + name + " was an A/B switch and has been retired; unset it"; continue; }
       const char* near = nullptr;
       for (const Entry& e : kTable) if (edit_distance(name, e.env) <= 2) near = e.env;
       for (const char* o : kOtherEnv) if (edit_distance(name, o) <= 2) near = o;

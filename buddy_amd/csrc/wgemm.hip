@@ -101,8 +101,8 @@ __device__ __forceinline__ float dsilu_g(float z) {
   return s * (1.f + z * (1.f - s));
 }
 
-// GEN: the general form (two-source A, row strides, alpha / bias / accumulate epilogue).  EPI: the accumulator tile goes through a wave-private LDS
-// slab (the weight buffers are free after the last stage) and leaves as 256-byte row pieces instead of 32-byte pieces per lane pair.
+// GEN: the general form (two-source A, row strides, alpha / bias / accumulate epilogue).  The accumulator tile goes through a wave-private LDS
+// slab (the weight buffers are free after the last stage) and leaves as 256-byte row pieces (32-byte pieces per lane pair: +0.3 ... 1.9 % slower).
 // Measured and rejected (profiles/README.md r03a): a second stage of A in flight (190 VGPRs: -3 %), 64 rows per wave (256+ VGPRs: -25 %), two
 // instead of three workgroups per CU (-2...4 %).
 // GNB (with GEN): the skip path's 1x1 data-gradient of a ResBlock (Conv_2^T, layerspp.py:262-264) and the GroupNorm_0 backward's apply pass in ONE launch:
@@ -114,7 +114,7 @@ __device__ __forceinline__ float dsilu_g(float z) {
 // branch inside the K loop (same effect: 65 -> 81 ms/step); a from-scratch large-tile kernel (tools/probes/wgemm2_large_tile.hip: 256-row workgroups, one wave
 // per SIMD, both operands by LDS-DMA, cross-stage split pipelining): bit-identical and within +-5 % on every shape -- two unrelated structures, one
 // throughput: the shape is bounded by the power budget of its instruction mix (pipe 49 % busy at 2.06 GHz; a register-only loop: 100 % at 1.57 GHz).
-template <bool GEN, bool EPI, bool GNB = false>
+template <bool GEN, bool GNB = false>
 __global__ __launch_bounds__(WNT, 3) void wgemm_bf16x3_kernel(const WgemmArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE_BYTES];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -140,9 +140,7 @@ __global__ __launch_bounds__(WNT, 3) void wgemm_bf16x3_kernel(const WgemmArgs a)
   const int S = a.S;
 
   // A: lane (row r = lane & 31, half h = lane >> 5) reads 16 consecutive floats per stage; rows past M are clamped (never stored)
-  int row = m0 + wid * 32 + (lane & 31);
-  const bool row_ok = row < a.Mt;
-  if (!row_ok) row = a.Mt - 1;
+  const int row = min(m0 + wid * 32 + (lane & 31), a.Mt - 1);
   const float* Ap = V + (long long)row * (GEN ? a.ldA0 : a.Cin) + 16 * (lane >> 5);
   const float* Ap1 = (GEN && a.A1) ? a.A1 + (long long)row * a.ldA1 + 16 * (lane >> 5) - a.C0 : nullptr;   // channels >= C0 come from the second source
   // B: the stage image is copied linearly, 6 x 16 B per thread (thread t moves bytes 16 t + 4096 j)
@@ -199,7 +197,7 @@ __global__ __launch_bounds__(WNT, 3) void wgemm_bf16x3_kernel(const WgemmArgs a)
   }
 
   // epilogue: accumulator = C^T tile, lane (row = lane & 31, h = lane >> 5) holds channels 8 g + 4 h + 0..3 of each 32-channel block
-  if (EPI && !GNB) {
+  if constexpr (!GNB) {
     constexpr int SP = 68;                                   // floats per staged row (64 columns + 4: conflict-free 16-byte writes down a column)
     float* St = reinterpret_cast<float*>(smem) + wid * (32 * SP);
     const int rr = lane >> 4, c4 = (lane & 15) * 4;
@@ -215,7 +213,7 @@ __global__ __launch_bounds__(WNT, 3) void wgemm_bf16x3_kernel(const WgemmArgs a)
               make_float4(acc[2 * hb + cl][4 * g], acc[2 * hb + cl][4 * g + 1], acc[2 * hb + cl][4 * g + 2], acc[2 * hb + cl][4 * g + 3]);
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
-      if (GEN) {                                              // general form: alpha * acc, + bias, + C (same operation order as the direct-store epilogue)
+      if (GEN) {                                              // general form: alpha * acc, + bias, + C (same operation order as the fp32 kernel's epilogue)
         float4 bs = make_float4(0.f, 0.f, 0.f, 0.f);
         if (a.bias_n) bs = *reinterpret_cast<const float4*>(a.bias_n + nb * WBN + hb * 64 + c4);
         float4 pv[8];
@@ -244,10 +242,8 @@ __global__ __launch_bounds__(WNT, 3) void wgemm_bf16x3_kernel(const WgemmArgs a)
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       __builtin_amdgcn_wave_barrier();
     }
-    return;
-  }
-  if constexpr (GNB) {
-    // The accumulator tile goes through the wave-private LDS slab of the EPI epilogue so that a lane owns 16-byte pieces of 256-byte ROW pieces
+  } else {
+    // The accumulator tile goes through the same wave-private LDS slab so that a lane owns 16-byte pieces of 256-byte ROW pieces
     // (16 lanes per row): the x / da loads and the dx stores are whole cache lines (in MFMA order a lane pair covers 32 bytes of 32 rows).
     constexpr int SP = 68;
     float* St = reinterpret_cast<float*>(smem) + wid * (32 * SP);
@@ -309,22 +305,7 @@ __global__ __launch_bounds__(WNT, 3) void wgemm_bf16x3_kernel(const WgemmArgs a)
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       __builtin_amdgcn_wave_barrier();
     }
-    return;
   }
-  if (!row_ok) return;
-  float* dst = a.M + (long long)p * a.sM + (long long)row * (GEN ? a.ldC : a.Cout) + nb * WBN + 4 * (lane >> 5);
-#pragma unroll
-  for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      float4 v = make_float4(acc[cb][4 * g], acc[cb][4 * g + 1], acc[cb][4 * g + 2], acc[cb][4 * g + 3]);
-      if (GEN) {     // same operation order as the fp32 kernel's epilogue: alpha * acc, + bias, + C
-        v.x *= a.alpha; v.y *= a.alpha; v.z *= a.alpha; v.w *= a.alpha;
-        if (a.bias_n) { const float4 t = *reinterpret_cast<const float4*>(a.bias_n + nb * WBN + 4 * (lane >> 5) + cb * 32 + 8 * g); v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w; }
-        if (a.accumulate) { const float4 t = *reinterpret_cast<const float4*>(dst + cb * 32 + 8 * g); v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w; }
-      }
-      *reinterpret_cast<float4*>(dst + cb * 32 + 8 * g) = v;
-    }
 }
 
 // ------------------------------------------------------------------------------------------------ f16x2 form of the batched GEMM
@@ -336,7 +317,7 @@ __global__ __launch_bounds__(WNT, 3) void wgemm_bf16x3_kernel(const WgemmArgs a)
 // two per position (their abs-max -> [2^14, 2^15), applied when packing; the inverse is in the image's tail), V one per UTTERANCE (abs-max collected by the
 // input transform with an atomic max, the power of two derived here from its exponent field), so that an utterance's result does not depend on its batch;
 // lo is a normal f16 for |x s| >= 2^-3, i.e. 2^-18 of the abs-max; below that the representation error is absolute, <= 2^-25 = 2^-40 of the abs-max.
-// Same workgroup / wave tiling, staging, XCD order and epilogue as wgemm_bf16x3_kernel<false, true>; a stage image is 16 KB ([k chunk][column block][plane]
+// Same workgroup / wave tiling, staging, XCD order and epilogue as wgemm_bf16x3_kernel<false>; a stage image is 16 KB ([k chunk][column block][plane]
 // [lane] x 16 B), 24 MFMAs per wave and barrier.
 // LDS-DMA of 16 bytes per lane as inline asm: source = uniform 64-bit base (SGPR pair) + a 32-bit per-lane byte offset, LDS destination = M0 + 16 * lane
 __device__ __forceinline__ void glds16_asm(const void* sbase, unsigned voff, unsigned lds_addr) {
@@ -420,7 +401,6 @@ __global__ __launch_bounds__(256) void wgemm_pack2_kernel(const float* __restric
   out[i] = (u32x4)sp.p[q];
 }
 
-template <bool EPI>
 __global__ __launch_bounds__(WNT, 3) void wgemm_f16x2_kernel(const WgemmArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[(2 * STAGE2_BYTES > 4 * 32 * 68 * 4) ? 2 * STAGE2_BYTES : 4 * 32 * 68 * 4];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -439,9 +419,7 @@ __global__ __launch_bounds__(WNT, 3) void wgemm_f16x2_kernel(const WgemmArgs a) 
   const unsigned char* __restrict__ U2 = a.U3 + ((long long)p * a.NB + nb) * a.S * STAGE2_BYTES;
   const int S = a.S;
 
-  int row = m0 + wid * 32 + (lane & 31);
-  const bool row_ok = row < a.Mt;
-  if (!row_ok) row = a.Mt - 1;
+  const int row = min(m0 + wid * 32 + (lane & 31), a.Mt - 1);
   // the utterance's abs-max = the maximum of its VMAX_SUB partial words: one word per lane, a wave-wide maximum; a wave's 32 rows touch at most two utterances
   // (tpu >= 32)
   float sv, inv;
@@ -531,39 +509,29 @@ __global__ __launch_bounds__(WNT, 3) void wgemm_f16x2_kernel(const WgemmArgs a) 
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[c][r] *= inv;               // the accumulator is C^T: a lane holds ONE row, so one (utterance, position) scale
 
-  if (EPI) {
-    constexpr int SP = 68;
-    float* St = reinterpret_cast<float*>(smem) + wid * (32 * SP);
-    const int rr = lane >> 4, c4 = (lane & 15) * 4;
-    float* Mrow = a.M + (long long)p * a.sM + (long long)(m0 + wid * 32) * a.Cout + nb * WBN;
+  constexpr int SP = 68;
+  float* St = reinterpret_cast<float*>(smem) + wid * (32 * SP);
+  const int rr = lane >> 4, c4 = (lane & 15) * 4;
+  float* Mrow = a.M + (long long)p * a.sM + (long long)(m0 + wid * 32) * a.Cout + nb * WBN;
 #pragma unroll
-    for (int hb = 0; hb < 2; ++hb) {
+  for (int hb = 0; hb < 2; ++hb) {
 #pragma unroll
-      for (int cl = 0; cl < 2; ++cl)
+    for (int cl = 0; cl < 2; ++cl)
 #pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *reinterpret_cast<float4*>(St + (lane & 31) * SP + cl * 32 + 8 * g + 4 * (lane >> 5)) =
-              make_float4(acc[2 * hb + cl][4 * g], acc[2 * hb + cl][4 * g + 1], acc[2 * hb + cl][4 * g + 2], acc[2 * hb + cl][4 * g + 3]);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      for (int g = 0; g < 4; ++g)
+        *reinterpret_cast<float4*>(St + (lane & 31) * SP + cl * 32 + 8 * g + 4 * (lane >> 5)) =
+            make_float4(acc[2 * hb + cl][4 * g], acc[2 * hb + cl][4 * g + 1], acc[2 * hb + cl][4 * g + 2], acc[2 * hb + cl][4 * g + 3]);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
 #pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const int r = 4 * it + rr;
-        const float4 v = *reinterpret_cast<const float4*>(St + r * SP + c4);
-        if (m0 + wid * 32 + r < a.Mt) *reinterpret_cast<float4*>(Mrow + (long long)r * a.Cout + hb * 64 + c4) = v;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+    for (int it = 0; it < 8; ++it) {
+      const int r = 4 * it + rr;
+      const float4 v = *reinterpret_cast<const float4*>(St + r * SP + c4);
+      if (m0 + wid * 32 + r < a.Mt) *reinterpret_cast<float4*>(Mrow + (long long)r * a.Cout + hb * 64 + c4) = v;
     }
-    return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
   }
-  if (!row_ok) return;
-  float* dst = a.M + (long long)p * a.sM + (long long)row * a.Cout + nb * WBN + 4 * (lane >> 5);
-#pragma unroll
-  for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-    for (int g = 0; g < 4; ++g)
-      *reinterpret_cast<float4*>(dst + cb * 32 + 8 * g) = make_float4(acc[cb][4 * g], acc[cb][4 * g + 1], acc[cb][4 * g + 2], acc[cb][4 * g + 3]);
 }
 
 // ------------------------------------------------------------------------------------------------ f16x2 form of the GENERAL GEMM (round 6)
@@ -573,10 +541,10 @@ __global__ __launch_bounds__(WNT, 3) void wgemm_f16x2_kernel(const WgemmArgs a) 
 // of the row's 32 values it is about to split; while that stays below 2^15 under the current scale nothing happens, otherwise the row's accumulators are
 // multiplied by the (exact) power of two that takes them to the new scale, which puts the stage's abs-max into [2^12, 2^13).  A row's result depends on
 // nothing but the row, no pre-pass re-reads A (the first version's did, from beyond L2: it took away what the halved MFMA count gave), and the rescale is a
-// wave-uniform branch taken a few times per row.  Structure = wgemm_f16x2_kernel<true> (32-row waves, LDS-DMA weight stages, two K-stages of A in flight)
-// with the two-source A of wgemm_bf16x3_kernel<true, ...> and its epilogues.
+// wave-uniform branch taken a few times per row.  Structure = wgemm_f16x2_kernel (32-row waves, LDS-DMA weight stages, two K-stages of A in flight)
+// with the two-source A of wgemm_bf16x3_kernel<true, GNB> and its epilogues.
 
-// epilogues of wgemm_bf16x3_kernel<true, true, GNB> for one 32-row x 128-column accumulator tile of a wave (rows rbase ..., x the rows' inverse scale)
+// epilogues of wgemm_bf16x3_kernel<true, GNB> for one 32-row x 128-column accumulator tile of a wave (rows rbase ..., x the rows' inverse scale)
 // through the wave-private LDS slab St, 256-byte row pieces
 template <bool GNB>
 __device__ __forceinline__ void f16x2_gen_epilogue(const WgemmArgs& a, const f32x16 (&acc)[4], const float inv, const int rbase, const int nb, float* St, const int lane) {
@@ -999,17 +967,13 @@ __global__ __launch_bounds__(WNT, 2) void wgemm_f16x2_gen2_kernel(const WgemmArg
 }
 
 // 64 rows per wave (two 32-row tiles; workgroup = 256 rows x 128 columns, 128 accumulators per lane, two workgroups per CU): every weight fragment read from LDS
-// feeds two MFMAs per product term instead of one (the 32-row form reads 0.67 fragments per MFMA) and a barrier separates 48 instead of 24 MFMAs per wave.  One K-stage of A in flight (a stage is 48 MFMAs per wave), reloaded in place after the split; the rest as wgemm_f16x2_kernel<true>.
-// NT (A/B switch wgemm_nt): bit 0 = the V rows are read with non-temporal loads (V is read exactly once: it should not displace the weight panels from
-// this XCD's L2), bit 1 = M leaves with non-temporal stores (its reader is the next launch, 0.4 - 1 GB later).
+// feeds two MFMAs per product term instead of one (the 32-row form reads 0.67 fragments per MFMA) and a barrier separates 48 instead of 24 MFMAs per wave.  One K-stage of A in flight (a stage is 48 MFMAs per wave), reloaded in place after the split; the rest as wgemm_f16x2_kernel.
 // Measured and rejected (round 6, profiles/README.md): a PERSISTENT form -- 2 x CUs workgroups walking (position, row block, column block) items with the K-stage
 // pipeline running across items, so that an item's stores leave while the next item's first rows and weights are in flight: 422.8 us against 401.7 us per
 // launch (29584 x 128 x 128 x 64, rocprofv3), +-1.5 % on the other shapes.  Taken apart in isolation the kernel's time is close to the SUM of its parts (whole
 // 0.454 ms; V read + split only 0.176; + stores 0.16; + MFMAs 0.09; + weight DMA 0.07), but what fails to overlap is not one workgroup's phases.
 // Also: 8 waves per workgroup (512 rows, one workgroup per CU: a weight stage fetched from L2 once per 512 rows, half the L2 -> LDS traffic): 2-15 % slower on six
 // shapes (0.451 vs 0.431, 1.293 vs 1.263, 0.358 vs 0.310, 0.640 vs 0.594, 0.078 vs 0.075, 0.787 vs 0.713 ms).
-typedef float f32x4nt __attribute__((ext_vector_type(4)));
-template <int NT>
 __global__ __launch_bounds__(WNT, 2) void wgemm_f16x2_rt2_kernel(const WgemmArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[(2 * STAGE2_BYTES > 4 * 32 * 68 * 4) ? 2 * STAGE2_BYTES : 4 * 32 * 68 * 4];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -1068,10 +1032,7 @@ __global__ __launch_bounds__(WNT, 2) void wgemm_f16x2_rt2_kernel(const WgemmArgs
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (NT & 1) { const f32x4nt v = __builtin_nontemporal_load(reinterpret_cast<const f32x4nt*>(base + aoff[t] + 16 * j)); ra[t][j] = make_float4(v.x, v.y, v.z, v.w); }
-        else ra[t][j] = *reinterpret_cast<const float4*>(base + aoff[t] + 16 * j);
-      }
+      for (int j = 0; j < 4; ++j) ra[t][j] = *reinterpret_cast<const float4*>(base + aoff[t] + 16 * j);
   };
   auto dmaB = [&](int s) {
     const void* base = uniform_ptr(Ub + (long long)s * STAGE2_BYTES);
@@ -1137,10 +1098,7 @@ __global__ __launch_bounds__(WNT, 2) void wgemm_f16x2_rt2_kernel(const WgemmArgs
       for (int it = 0; it < 8; ++it) {
         const int r = 4 * it + rr;
         const float4 v = *reinterpret_cast<const float4*>(St + r * SP + c4);
-        if (rb + r < a.Mt) {
-          if (NT & 2) __builtin_nontemporal_store(f32x4nt{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4nt*>(Mrow + (long long)r * a.Cout + hb * 64 + c4));
-          else *reinterpret_cast<float4*>(Mrow + (long long)r * a.Cout + hb * 64 + c4) = v;
-        }
+        if (rb + r < a.Mt) *reinterpret_cast<float4*>(Mrow + (long long)r * a.Cout + hb * 64 + c4) = v;
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -1172,9 +1130,7 @@ void launch_wgemm_bf16x3_general(const float* A0, int ldA0, const float* A1, int
   a.A1 = A1; a.C0 = A1 ? C0 : K; a.ldA0 = ldA0; a.ldA1 = ldA1; a.ldC = ldC; a.bias_n = bias_n; a.alpha = alpha; a.accumulate = accumulate;
   a.pz = 0; a.gx = 0;
   const dim3 grid((unsigned)(cdiv((int)M, WBM) * a.NB), 1, 1);
-  const bool direct_store = cur_opt().wgemm_gen_epi == 0;      // A/B switch: 32-byte-piece stores
-  if (direct_store) hipLaunchKernelGGL((wgemm_bf16x3_kernel<true, false>), grid, dim3(WNT), 0, st, a);
-  else hipLaunchKernelGGL((wgemm_bf16x3_kernel<true, true>), grid, dim3(WNT), 0, st, a);
+  hipLaunchKernelGGL((wgemm_bf16x3_kernel<true>), grid, dim3(WNT), 0, st, a);
 }
 
 // out (two-destination view) = alpha * A (M x K) . W^T (N x K, pre-split) + GroupNorm backward apply of (x, da): see the GNB epilogue
@@ -1193,7 +1149,7 @@ void launch_wgemm_bf16x3_gnbwd(const float* A, int ldA, const void* W3, long lon
   a.pz = 0; a.gx = 0;
   a.gxv = x; a.gd = d; a.gda = da; a.gstats = stats; a.gred = red; a.ggamma = gamma; a.gbeta = beta; a.gG = G; a.gsilu = silu; a.gHW = HW;
   const dim3 grid((unsigned)(cdiv((int)M, WBM) * a.NB), 1, 1);
-  hipLaunchKernelGGL((wgemm_bf16x3_kernel<true, false, true>), grid, dim3(WNT), 0, st, a);
+  hipLaunchKernelGGL((wgemm_bf16x3_kernel<true, true>), grid, dim3(WNT), 0, st, a);
 }
 
 // 64-row waves where option gen_rows says so; 0 = by size: from 32768 rows on (below that the halved workgroup count leaves CUs idle: 16384 x 256 x 256
@@ -1237,14 +1193,11 @@ void launch_wgemm_bf16x3(const float* V, const void* U3, float* M, long long Mt,
   a.V = V; a.U3 = reinterpret_cast<const unsigned char*>(U3); a.M = M;
   a.Mt = (int)Mt; a.Cin = Cin; a.Cout = Cout; a.S = Cin / WKS; a.NB = Cout / WBN;
   a.sV = Mt * Cin; a.sM = Mt * Cout;
-  const bool by_pos = cur_opt().wgemm_xcdpos != 0;     // A/B switch
   const int gx = cdiv((int)Mt, WBM) * a.NB;
-  const bool fold = by_pos && P % 8 == 0 && (long long)gx * P < (1LL << 31);
+  const bool fold = P % 8 == 0 && (long long)gx * P < (1LL << 31);     // positions folded into a 1-D grid, one XCD per position (see the kernel)
   a.pz = fold ? P : 0; a.gx = gx;
   const dim3 grid(fold ? (unsigned)(gx * P) : (unsigned)gx, 1, fold ? 1u : (unsigned)P);
-  const bool direct_store = cur_opt().wgemm_epi == 0;      // A/B switch: 32-byte-piece stores (+0.3 ... 1.9 % slower)
-  if (direct_store) hipLaunchKernelGGL((wgemm_bf16x3_kernel<false, false>), grid, dim3(WNT), 0, st, a);
-  else hipLaunchKernelGGL((wgemm_bf16x3_kernel<false, true>), grid, dim3(WNT), 0, st, a);
+  hipLaunchKernelGGL((wgemm_bf16x3_kernel<false>), grid, dim3(WNT), 0, st, a);
 }
 
 // f16x2 form
@@ -1269,24 +1222,15 @@ void launch_wgemm_f16x2(const float* V, const void* U2, float* M, long long Mt, 
   a.Mt = (int)Mt; a.Cin = Cin; a.Cout = Cout; a.S = Cin / WKS; a.NB = Cout / WBN;
   a.sV = Mt * Cin; a.sM = Mt * Cout;
   a.vmax = vmax; a.tpu = tiles_per_utt; a.uinv = reinterpret_cast<const float*>(a.U3 + (size_t)P * Cout * Cin * 4);
-  const bool by_pos = cur_opt().wgemm_xcdpos != 0;
   // 64-row waves (wgemm_f16x2_rt2_kernel): 4-6 % faster on every shape of the shipped network (tools/wgemm_modes_bench.py, profiles/README.md r05i); option
-  // wgemm_rt 1 = the 32-row kernel (A/B switch)
-  const bool rt2 = tiles_per_utt >= 64 && cur_opt().wgemm_epi != 0 && cur_opt().wgemm_rt != 1;
+  // wgemm_rt 1 = the 32-row kernel
+  const bool rt2 = tiles_per_utt >= 64 && cur_opt().wgemm_rt != 1;
   const int gx = cdiv((int)Mt, rt2 ? 2 * WBM : WBM) * a.NB;
-  const bool fold = by_pos && P % 8 == 0 && (long long)gx * P < (1LL << 31);
+  const bool fold = P % 8 == 0 && (long long)gx * P < (1LL << 31);
   a.pz = fold ? P : 0; a.gx = gx;
   const dim3 grid(fold ? (unsigned)(gx * P) : (unsigned)gx, 1, fold ? 1u : (unsigned)P);
-  if (rt2) {
-    switch (cur_opt().wgemm_nt) {
-      case 1: hipLaunchKernelGGL(wgemm_f16x2_rt2_kernel<1>, grid, dim3(WNT), 0, st, a); break;
-      case 2: hipLaunchKernelGGL(wgemm_f16x2_rt2_kernel<2>, grid, dim3(WNT), 0, st, a); break;
-      case 3: hipLaunchKernelGGL(wgemm_f16x2_rt2_kernel<3>, grid, dim3(WNT), 0, st, a); break;
-      default: hipLaunchKernelGGL(wgemm_f16x2_rt2_kernel<0>, grid, dim3(WNT), 0, st, a);
-    }
-  }
-  else if (cur_opt().wgemm_epi == 0) hipLaunchKernelGGL((wgemm_f16x2_kernel<false>), grid, dim3(WNT), 0, st, a);
-  else hipLaunchKernelGGL((wgemm_f16x2_kernel<true>), grid, dim3(WNT), 0, st, a);
+  if (rt2) hipLaunchKernelGGL(wgemm_f16x2_rt2_kernel, grid, dim3(WNT), 0, st, a);
+  else hipLaunchKernelGGL(wgemm_f16x2_kernel, grid, dim3(WNT), 0, st, a);
 }
 
 }  // namespace buddy

@@ -216,7 +216,7 @@ void launch_wgemm_f16(const void* V16, const signed char* vexp, const void* U1, 
   a.Mt = (int)Mt; a.Cin = Cin; a.Cout = Cout; a.S = Cin / KS; a.NB = Cout / BN;
   a.sV = Mt * Cin; a.sM = Mt * Cout;
   const int gx = (int)((Mt + 2 * BM - 1) / (2 * BM)) * a.NB;
-  const bool fold = cur_opt().wgemm_xcdpos != 0 && P % 8 == 0 && (long long)gx * P < (1LL << 31);
+  const bool fold = P % 8 == 0 && (long long)gx * P < (1LL << 31);
   a.pz = fold ? P : 0; a.gx = gx;
   const dim3 grid(fold ? (unsigned)(gx * P) : (unsigned)gx, 1, fold ? 1u : (unsigned)P);
   hipLaunchKernelGGL(wgemm_f16_kernel, grid, dim3(NT), 0, st, a);

@@ -38,7 +38,7 @@ constexpr int BTX = 16, RC = 2 * BTX + 2;
 constexpr int V3_WK = 8;
 constexpr int V3_USZ = 16 * WN * V3_WK;      // floats per weight buffer
 
-template <int ABL, int NW, int NBUF>
+constexpr int NW = 4, NBUF = 2;      // 4-wave workgroups, two LDS buffers (the 8-wave geometry lost the A/B and was retired)
 __global__ __launch_bounds__(64 * NW, 2) void wino3_kernel(const IgemmParams p, const float* __restrict__ Uw, const float* __restrict__ zeros) {
   constexpr int V3_BTY = NW, V3_RR = 2 * V3_BTY + 2, V3_RPIX = V3_RR * RC, V3_RPL = (V3_RPIX + 127) / 128 * 128;   // pixels covered by the load rounds
   // LDS images are built for ds_read_b64: a half-wave (16 tiles x 2 k-pairs) must cover 32 distinct 8-B slots of the 256-B bank row.
@@ -136,25 +136,21 @@ __global__ __launch_bounds__(64 * NW, 2) void wino3_kernel(const IgemmParams p, 
 #pragma unroll
     for (int r = 0; r < 4; ++r)
 #pragma unroll
-      for (int c = 0; c < 4; ++c) d[r][c] = (ABL == 2) ? make_float2(1.f + r, 2.f + c + kc) : *reinterpret_cast<const float2*>(Rb + (r * RC + c) * 2);
-    if (ABL != 2) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float2 a0 = d[0][c], a1 = d[1][c], a2 = d[2][c], a3 = d[3][c];
-        d[0][c] = make_float2(a0.x - a2.x, a0.y - a2.y); d[1][c] = make_float2(a1.x + a2.x, a1.y + a2.y);
-        d[2][c] = make_float2(a2.x - a1.x, a2.y - a1.y); d[3][c] = make_float2(a1.x - a3.x, a1.y - a3.y);
+      for (int c = 0; c < 4; ++c) {     // through a named temporary: assigned directly hipcc allocates registers differently (251 VGPRs, +36 instructions; not measured)
+        const float2 t = *reinterpret_cast<const float2*>(Rb + (r * RC + c) * 2);
+        d[r][c] = t;
       }
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float2 a0 = d[r][0], a1 = d[r][1], a2 = d[r][2], a3 = d[r][3];
-        d[r][0] = make_float2(a0.x - a2.x, a0.y - a2.y); d[r][1] = make_float2(a1.x + a2.x, a1.y + a2.y);
-        d[r][2] = make_float2(a2.x - a1.x, a2.y - a1.y); d[r][3] = make_float2(a1.x - a3.x, a1.y - a3.y);
-      }
+    for (int c = 0; c < 4; ++c) {
+      const float2 a0 = d[0][c], a1 = d[1][c], a2 = d[2][c], a3 = d[3][c];
+      d[0][c] = make_float2(a0.x - a2.x, a0.y - a2.y); d[1][c] = make_float2(a1.x + a2.x, a1.y + a2.y);
+      d[2][c] = make_float2(a2.x - a1.x, a2.y - a1.y); d[3][c] = make_float2(a1.x - a3.x, a1.y - a3.y);
     }
-    if (ABL == 1) {
 #pragma unroll
-      for (int pos = 0; pos < 16; ++pos) asm volatile("" :: "v"(d[pos >> 2][pos & 3].x), "v"(d[pos >> 2][pos & 3].y));
-      return;
+    for (int r = 0; r < 4; ++r) {
+      const float2 a0 = d[r][0], a1 = d[r][1], a2 = d[r][2], a3 = d[r][3];
+      d[r][0] = make_float2(a0.x - a2.x, a0.y - a2.y); d[r][1] = make_float2(a1.x + a2.x, a1.y + a2.y);
+      d[r][2] = make_float2(a2.x - a1.x, a2.y - a1.y); d[r][3] = make_float2(a1.x - a3.x, a1.y - a3.y);
     }
 #pragma unroll
     for (int pos = 0; pos < 16; ++pos) {
@@ -175,12 +171,12 @@ __global__ __launch_bounds__(64 * NW, 2) void wino3_kernel(const IgemmParams p, 
   if (nchunks > 1) gload(1, rB, uB);
   __syncthreads();
   for (int kc = 0; kc < nchunks; kc += 2) {
-    if (ABL != 3 && kc + 2 < nchunks) gload(kc + 2, rA, uA);
+    if (kc + 2 < nchunks) gload(kc + 2, rA, uA);
     compute(kc, 0);
     if (kc + 1 < nchunks) lstore(1, rB, uB);
     __syncthreads();
     if (kc + 1 < nchunks) {
-      if (ABL != 3 && kc + 3 < nchunks) gload(kc + 3, rB, uB);
+      if (kc + 3 < nchunks) gload(kc + 3, rB, uB);
       compute(kc + 1, 1);
       if (kc + 2 < nchunks) lstore(0, rA, uA);
       __syncthreads();
@@ -279,25 +275,13 @@ void launch_wino(const IgemmParams& p_in, const float* Uw, hipStream_t st) {
     if (p.bias_n) wide = wide && al16(p.bias_n);
     if (p.bias_bn) wide = wide && al16(p.bias_bn) && (p.ld_bias_bn % 4 == 0);
     if (p.res_mode) wide = wide && al16(p.res) && (p.ldRes % 4 == 0);
-    const bool force_scalar = cur_opt().wino_epi == 0;     // A/B switch
-    p.wide_epi = (wide && !force_scalar) ? 1 : 0;
+    p.wide_epi = wide ? 1 : 0;     // the scalar epilogue is the fallback for an unaligned tile
   }
   if (!g_zero_page) { (void)hipMalloc(&g_zero_page, 256); (void)hipMemset(g_zero_page, 0, 256); }
   const int B = p.M / (p.H * p.W);
   const int TH = p.H / 2, TW = p.W / 2;
-  const int abl = cur_opt().wino_abl;     // timing ablations (wrong results): 1 no MFMA, 2 no patch reads, 3 no DMA
-  const int geo = cur_opt().wino_geo;    // 42: 4-wave workgroups, 2 per CU (default, fastest); 82: 8-wave workgroups
-  const float* z = g_zero_page;
-  if (TH % 8 == 0 && geo / 10 == 8) {
-    const int grid = B * (TH / 8) * (TW / BTX) * (p.N / WN);
-    if (abl == 1) hipLaunchKernelGGL((wino3_kernel<1, 8, 2>), dim3(grid), dim3(512), 0, st, p, Uw, z);
-    else if (abl == 2) hipLaunchKernelGGL((wino3_kernel<2, 8, 2>), dim3(grid), dim3(512), 0, st, p, Uw, z);
-    else if (abl == 3) hipLaunchKernelGGL((wino3_kernel<3, 8, 2>), dim3(grid), dim3(512), 0, st, p, Uw, z);
-    else hipLaunchKernelGGL((wino3_kernel<0, 8, 2>), dim3(grid), dim3(512), 0, st, p, Uw, z);
-  } else {
-    const int grid = B * (TH / 4) * (TW / BTX) * (p.N / WN);
-    hipLaunchKernelGGL((wino3_kernel<0, 4, 2>), dim3(grid), dim3(256), 0, st, p, Uw, z);
-  }
+  const int grid = B * (TH / NW) * (TW / BTX) * (p.N / WN);     // 4-wave workgroups, 2 per CU
+  hipLaunchKernelGGL(wino3_kernel, dim3(grid), dim3(64 * NW), 0, st, p, Uw, g_zero_page);
 }
 
 // host: U[Cin/8][pos][cout][8] from tap-major packed weights wt[cout][(dy*3+dx)*Cin + cin]

@@ -68,7 +68,7 @@ __device__ __forceinline__ void at8(const float4 (&m)[8], float4 (&y)[7]) {
   y[6] = s12 + 64.f * s34 + 0.015625f * s56 + m[7];
 }
 
-struct W6Geo { int B, H, W, TH, TW, QC, TPB; long long Mt; int xcd; int Cl; };   // TH x TW tiles per utterance, Mt = B * TH * TW; Cl: see S2D / UP
+struct W6Geo { int B, H, W, TH, TW, QC, TPB; long long Mt; int Cl; };   // TH x TW tiles per utterance, Mt = B * TH * TW; Cl: see S2D / UP
 
 // grid (ceil(Mt / TPB), ceil(q / QC)); V[(pos * Mt + tile) * Cin + c]
 // GN 1: the input is act(GroupNorm(x)) of a (channel-concatenated) view, applied while loading (zero padding applies to the ACTIVATED tensor)
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256) void w6_input_kernel(const float* __restrict__
   const int tid = threadIdx.x, QC = geo.QC;
   const int ql = tid % QC, col = (tid / QC) & 7, tl = tid / (QC * 8);
   int bx = blockIdx.x, by = blockIdx.y;
-  if (geo.xcd) w6_xcd_order(bx, by);
+  w6_xcd_order(bx, by);
   const int quad = by * QC + ql, c = quad * 4;
   const long long tile = (long long)bx * geo.TPB + tl;
   const bool live = tile < geo.Mt && c < Cin;
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256) void w6_input_f16_kernel(const float* __restri
   const int tid = threadIdx.x, QC = geo.QC;
   const int ql = tid % QC, col = (tid / QC) & 7, tl = tid / (QC * 8);
   int bx = blockIdx.x, by = 0;
-  if (geo.xcd) w6_xcd_order(bx, by);
+  w6_xcd_order(bx, by);
   const long long tile = (long long)bx * geo.TPB + tl;
   const bool tile_live = tile < geo.Mt;
   int b = 0, ty = 0, tx = 0;
@@ -310,11 +310,11 @@ __global__ __launch_bounds__(256) void w6_input_f16_kernel(const float* __restri
 // ph = 2 py + px; tile pixel (y, x) of phase ph is pixel (2 y + py, 2 x + px) of the (2H, 2W, N) output (depth-to-space).  The statistics partials
 // of phase ph are chunks [ph * chunks, (ph + 1) * chunks) of 4 * chunks per utterance.  No residual.  TS = 7: tile row r of phase py is row
 // 7 ty + r - py of the phase image (the patch starts at low-resolution row 7 ty - 1 for both phases).
-// NTM (A/B switch w6_nt): M is read with non-temporal loads -- every 16-byte piece is read exactly once, in whole 512-byte rows per instruction (the
+// M is read with non-temporal loads -- every 16-byte piece is read exactly once, in whole 512-byte rows per instruction (the
 // streaming ubench: reads 6.3 -> 7.1 TB/s with them, tools/hbm_bw.py; the GEMM's V rows, read in four partial-line pieces, lost 45 % with them).
 typedef float f32x4w __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 ld4nt(const float* p) { const f32x4w v = __builtin_nontemporal_load(reinterpret_cast<const f32x4w*>(p)); return make_float4(v.x, v.y, v.z, v.w); }
-template <int STAT, bool UP = false, int TS = 6, bool NTM = false>
+template <int STAT, bool UP = false, int TS = 6>
 __global__ __launch_bounds__(256) void w6_output_kernel(const float* __restrict__ Mb, const IgemmParams p, const W6Geo geo, int chunks, int TL,
                                                         double* __restrict__ stat, const W4Gn bg) {
   __shared__ float4 lds[32 * TS * 8];
@@ -368,7 +368,7 @@ __global__ __launch_bounds__(256) void w6_output_kernel(const float* __restrict_
       const float* src = Mb + tile * NM + nq;
       float4 m[8], s[TS];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) m[i] = NTM ? ld4nt(src + (long long)(i * 8 + col) * ps) : ld4(src + (long long)(i * 8 + col) * ps);
+      for (int i = 0; i < 8; ++i) m[i] = ld4nt(src + (long long)(i * 8 + col) * ps);
       at8(m, s);                                             // column: s[:, col] = A^T m[:, col]
 #pragma unroll
       for (int r = 0; r < TS; ++r) lds[(tl * (TS * 8) + r * 8 + col) * QC + ql] = s[r];
@@ -448,8 +448,6 @@ W6Geo geometry(const IgemmParams& p, int C, int up = 0) {
   const int q = C / 4;
   g.QC = q >= 32 ? 32 : (q > 16 ? 32 : (q > 8 ? 16 : (q > 4 ? 8 : (q > 2 ? 4 : (q > 1 ? 2 : 1)))));
   g.TPB = 32 / g.QC;
-  const int xcd = cur_opt().w6_xcd != 0;     // A/B switch of the XCD-aware tile order of the input transform
-  g.xcd = xcd;
   g.Cl = C;
   return g;
 }
@@ -546,23 +544,12 @@ void launch_wino6(const IgemmParams& p, const float* U6, float* V, float* Mb, hi
   if (prof || prof_gemm) (void)hipEventRecord(ev[2], st);
   const int TL = out_walk(go, up), per = go.TPB * TL, chunks = (go.TH * go.TW + per - 1) / per;
   const dim3 grid_out((unsigned)(go.B * chunks), (unsigned)((NG / 4 + go.QC - 1) / go.QC));
-  if (up == 1 && cur_opt().w6_nt) {
-    if (stat) hipLaunchKernelGGL((w6_output_kernel<1, true, 7, true>), grid_out, dim3(256), 0, st, (const float*)Mb, p, go, chunks, TL, stat, W4Gn{});
-    else hipLaunchKernelGGL((w6_output_kernel<0, true, 7, true>), grid_out, dim3(256), 0, st, (const float*)Mb, p, go, chunks, TL, (double*)nullptr, W4Gn{});
-  } else if (up == 1) {
+  if (up == 1) {
     if (stat) hipLaunchKernelGGL((w6_output_kernel<1, true, 7>), grid_out, dim3(256), 0, st, (const float*)Mb, p, go, chunks, TL, stat, W4Gn{});
     else hipLaunchKernelGGL((w6_output_kernel<0, true, 7>), grid_out, dim3(256), 0, st, (const float*)Mb, p, go, chunks, TL, (double*)nullptr, W4Gn{});
-  } else if (up == 2 && cur_opt().w6_nt) {
-    if (stat && bwd_gn) hipLaunchKernelGGL((w6_output_kernel<2, false, 7, true>), grid_out, dim3(256), 0, st, (const float*)Mb, p, go, chunks, TL, stat, *bwd_gn);
-    else hipLaunchKernelGGL((w6_output_kernel<0, false, 7, true>), grid_out, dim3(256), 0, st, (const float*)Mb, p, go, chunks, TL, (double*)nullptr, W4Gn{});
   } else if (up == 2) {
     if (stat && bwd_gn) hipLaunchKernelGGL((w6_output_kernel<2, false, 7>), grid_out, dim3(256), 0, st, (const float*)Mb, p, go, chunks, TL, stat, *bwd_gn);
     else hipLaunchKernelGGL((w6_output_kernel<0, false, 7>), grid_out, dim3(256), 0, st, (const float*)Mb, p, go, chunks, TL, (double*)nullptr, W4Gn{});
-  }
-  else if (cur_opt().w6_nt) {
-    if (stat && bwd_gn) hipLaunchKernelGGL((w6_output_kernel<2, false, 6, true>), grid_out, dim3(256), 0, st, (const float*)Mb, p, go, chunks, TL, stat, *bwd_gn);
-    else if (stat) hipLaunchKernelGGL((w6_output_kernel<1, false, 6, true>), grid_out, dim3(256), 0, st, (const float*)Mb, p, go, chunks, TL, stat, W4Gn{});
-    else hipLaunchKernelGGL((w6_output_kernel<0, false, 6, true>), grid_out, dim3(256), 0, st, (const float*)Mb, p, go, chunks, TL, (double*)nullptr, W4Gn{});
   }
   else if (stat && bwd_gn) hipLaunchKernelGGL(w6_output_kernel<2>, grid_out, dim3(256), 0, st, (const float*)Mb, p, go, chunks, TL, stat, *bwd_gn);
   else if (stat) hipLaunchKernelGGL(w6_output_kernel<1>, grid_out, dim3(256), 0, st, (const float*)Mb, p, go, chunks, TL, stat, W4Gn{});

@@ -282,12 +282,12 @@ int buddy_groupnorm_act_bwd(const float* x, const float* gamma, const float* bet
 int buddy_fir_resample2(const float* x, float* y, int B, int H, int W, int C, int up, float scale, int accumulate, void* stream);
 int buddy_ncsnpp_set_fir(void* handle, int fir);
 /* Per-handle launcher options -- "no hidden global state" (SURVEY.md 8(b)): every switch a launcher consults (attention core, GEMM arithmetic, the
- * fusion / layout A/B switches) is a field of the handle's option struct; two handles in one process may differ.  Keys (csrc/options.hip): conv, gemm,
- * attention, gn_fuse, gn_fuse_bwdin, gn_fuse_bwd, upconv, c2_fuse, attn_tr, attn_split, attn_nw, igemm_epi, igemm_variant, wgemm_gen_epi, wgemm_xcdpos,
- * wgemm_epi, wgemm_rt, wgemm_nt, gen_f16x2, gen_rows, gen_cp, gnb_nt, wino_epi, wino_abl, wino_geo, w6_xcd, w6_nt, gn_fast, gn_trips, ew_grid, c2in4, c2out_tiled, fir_lds, op_graph.  An unknown key or a value out of range is
- * BUDDY_ERR_ARG.  A handle starts from the process defaults = the BUDDY_<KEY> environment variables, parsed and validated in ONE place at handle
+ * fusions and kernel forms the tests compare) is a field of the handle's option struct; two handles in one process may differ.  Keys (csrc/options.hip): conv, gemm,
+ * attention, gn_fuse, upconv, c2_fuse, attn_split, attn_nw, wgemm_rt, gen_f16x2, gen_rows, gen_cp, gnb_nt, c2out_tiled, op_graph.  An unknown key (the
+ * retired A/B switches included) or a value out of range is BUDDY_ERR_ARG.  A handle starts from the process defaults = the BUDDY_<KEY> environment variables, parsed and validated in ONE place at handle
  * creation: a bad value, or an unknown BUDDY_* name within edit distance 2 of a switch (a misspelling), makes buddy_ncsnpp_create fail with a message naming it;
- * BUDDY_* names that resemble no switch are not this library's and are left alone.  Set options before the first forward or between calls: the
+ * the environment name of a retired A/B switch fails the same way ("... has been retired; unset it"); BUDDY_* names that resemble no switch are not this
+ * library's and are left alone.  Set options before the first forward or between calls: the
  * activation arena is sized again and a saved forward is dropped (buddy_ncsnpp_vjp returns BUDDY_ERR_STATE until the next forward with save = 1). */
 int buddy_options_check(void);   /* the environment check alone (no GPU needed): BUDDY_OK, or BUDDY_ERR_ARG with buddy_last_error() naming the variable */
 int buddy_option_validate(const char* key, int value);   /* would buddy_ncsnpp_set_option accept (key, value)?  no handle, no GPU, nothing changed */

@@ -112,6 +112,8 @@ def test_environment_switches_are_validated_in_one_place():
     assert bad.returncode != 0 and "bad value 'fp16' for BUDDY_ATTN" in bad.stderr
     bad = run(BUDDY_GN_FUSE="2")
     assert bad.returncode != 0 and "BUDDY_GN_FUSE" in bad.stderr
+    bad = run(BUDDY_W6_NT="0")                                 # a settled A/B switch: retired, and a script that still sets it must hear about it
+    assert bad.returncode != 0 and "BUDDY_W6_NT was an A/B switch and has been retired; unset it" in bad.stderr, bad.stderr[-800:]
     import glob
     n = sum(open(f).read().count("getenv(") for f in glob.glob(os.path.join(ROOT, "buddy_amd", "csrc", "*.hip")))
     assert n <= 3, n
@@ -125,7 +127,7 @@ def test_set_option_validates_before_remembering():
     from buddy_amd.networks.ncsnpp import NCSNppTime
     net = NCSNppTime(stft={"n_fft": 126, "hop_length": 32, "center": True}, nf=32, ch_mult=(1, 2), num_res_blocks=1)
     net.set_option("upconv", 0).set_option("gemm", 1)
-    for key, val in (("upconvv", 0), ("attention", 9), ("gemm", -1)):
+    for key, val in (("upconvv", 0), ("attention", 9), ("gemm", -1), ("wino_abl", 0)):
         with _pt.raises(_lib.BuddyHipError):
             net.set_option(key, val)
     assert net._options == {"upconv": 0, "gemm": 1}
