@@ -38,6 +38,11 @@ _SIGS = {
     "buddy_ncsnpp_vjp": (C.c_int, [C.c_void_p, _f32p, _f32p, C.c_void_p]),
     "buddy_ncsnpp_vjp_params": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_int, C.c_void_p]),
     "buddy_ncsnpp_update_params": (C.c_int, [C.c_void_p, _f32p, C.c_void_p]),
+    "buddy_optim_sqnorm_chunk": (C.c_longlong, []),
+    "buddy_optim_sqnorm": (C.c_int, [_f32p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "buddy_optim_step": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, C.c_longlong, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double,
+                                   C.c_double, C.c_double, C.c_double, C.POINTER(C.c_longlong), C.c_int, C.c_void_p]),
+    "buddy_optim_ema": (C.c_int, [_f32p, _f32p, C.c_longlong, C.c_double, C.c_void_p]),
     "buddy_ncsnpp_tap": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int * 4)]),
     "buddy_prof_enable": (C.c_int, [C.c_int]),
     "buddy_wpe": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -107,3 +107,19 @@ def compose(tester="blind_dereverberation_BUDDy", network="ncsnpp", diff_params=
         k = k.lstrip("+")
         set_by_path(args, k, yaml.safe_load(v))
     return args
+
+
+def compose_train(tester="only_unconditional", network="ncsnpp", diff_params="edm_VCTK", exp="VCTK_16k_4s_time", dset="vctk_16k_4s",
+                  logging="base_logging", overrides=(), conf_dir=None):
+    """The tree ``train.py`` runs on (reference ``conf/conf_VCTK.yaml`` with its ``dset`` and ``logging`` groups): ``compose()`` plus the training
+    keys of the experiment (``conf/train/<exp>.yaml`` merged over ``args.exp``), ``args.logging`` and ``args.dset``.  ``compose()`` itself -- the
+    sampler path -- reads none of these files."""
+    conf_dir = conf_dir or CONF_DIR
+    args = compose(tester=tester, network=network, diff_params=diff_params, exp=exp, conf_dir=conf_dir)
+    args.exp = merge(args.exp, load_yaml(os.path.join(conf_dir, "train", exp + ".yaml")))
+    args.logging = load_yaml(os.path.join(conf_dir, "logging", logging + ".yaml"))
+    args.dset = load_yaml(os.path.join(conf_dir, "dset", dset + ".yaml"))
+    for ov in overrides:
+        k, v = ov.split("=", 1)
+        set_by_path(args, k.lstrip("+"), yaml.safe_load(v))
+    return args

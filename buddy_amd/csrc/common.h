@@ -223,6 +223,9 @@ long long wgrad_ws_floats(long long M, int N, int K);
 void launch_wgrad(const WgY& y, const WgA& a, long long M, int N, int layout, float alpha, float* ws, float* out, hipStream_t st);
 long long colsum_ws_floats(int B, long long T, int N);
 void launch_colsum(const WgY& y, int B, int N, float alpha, float* ws, float* bc, int ld_bc, float* out, float* out2, hipStream_t st);
+// out[c] += sum_k bsum[c][k] * (sum over the B * T rows of x[row][k]), c = 0, 1, all in double; x [B * T][K] fp32, bsum [2][K]; ws: basis_bias_ws_floats
+long long basis_bias_ws_floats(int B, long long T, int K);
+void launch_basis_bias(const float* x, int K, int B, long long T, const double* bsum, float* ws, float* out, hipStream_t st);
 long long gn_pgrad_ws_floats(int B, int H, int W, int C);
 void launch_gn_pgrad(const Src2& x, const float* stats, const float* gamma, const float* beta, int G, int silu, const float* da, int da_mode, int B,
                      int H, int W, int C, float* ws, float* dgamma, float* dbeta, hipStream_t st);

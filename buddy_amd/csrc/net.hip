@@ -157,6 +157,7 @@ struct Weights {
   std::vector<GNW> pyr_gn; std::vector<ConvW> pyr_conv;   // C -> 2 heads, top level first
   float* out_w = nullptr; float* out_b = nullptr;
   float* basisF = nullptr; float* basisI = nullptr;      // [2Fb][Kp], [Kp][2Fb]
+  double* basisI_sum = nullptr;        // [2][Kp]: sum over the bins f of basisI[k][2 f + c], in double from the exact entries (output_layer.bias gradient)
   unsigned char* dpacked3 = nullptr;   // bf16x3 stage images of the 1x1 / NIN weights
   std::unordered_map<const float*, W3Img> w3;   // 1x1 / NIN weights [N][K] (fp32, device) -> their bf16x3 stage image and the shape it was packed for
   // lazily prepared 3x3 operand forms
@@ -167,6 +168,7 @@ struct Weights {
     if (dparams) (void)hipFree(dparams);
     if (dpacked) (void)hipFree(dpacked);
     if (dpacked3) (void)hipFree(dpacked3);
+    if (basisI_sum) (void)hipFree(basisI_sum);
     if (prep_tmp) (void)hipFree(prep_tmp);
     for (void* q : lazy_allocs) (void)hipFree(q);
   }
@@ -438,6 +440,7 @@ static int weights_create(const float* hp, long long n, const NetCfg& cfg, std::
   {
     const int nfft = cfg.n_fft;
     std::vector<float> bf((size_t)2 * Fb * Kp, 0.f), bi((size_t)Kp * 2 * Fb, 0.f);
+    std::vector<double> bis((size_t)2 * Kp, 0.0);
     const double PI = 3.14159265358979323846;
     std::vector<double> ct(nfft), sn(nfft);                   // cos / sin of 2 pi j / nfft: one evaluation per angle instead of Fb per angle
     for (int j = 0; j < nfft; ++j) { ct[j] = std::cos(2.0 * PI * (double)j / nfft); sn[j] = std::sin(2.0 * PI * (double)j / nfft); }
@@ -450,9 +453,13 @@ static int weights_create(const float* hp, long long n, const NetCfg& cfg, std::
         const double cf = (f == 0 || f == nfft / 2) ? 1.0 : 2.0;
         bi[(size_t)k * 2 * Fb + f * 2 + 0] = (float)(cf / nfft * ct[j] * w);
         bi[(size_t)k * 2 * Fb + f * 2 + 1] = (float)(-cf / nfft * sn[j] * w);
+        bis[k] += cf / nfft * ct[j] * w;
+        bis[(size_t)Kp + k] += -cf / nfft * sn[j] * w;
       }
     }
     packed(&N->basisF, bf); packed(&N->basisI, bi);
+    HIPCHK(hipMalloc(&N->basisI_sum, bis.size() * 8));
+    HIPCHK(hipMemcpy(N->basisI_sum, bis.data(), bis.size() * 8, hipMemcpyHostToDevice));
   }
   HIPCHK(hipMalloc(&N->dpacked, pk.buf.size() * 4));
   HIPCHK(hipMemcpyAsync(N->dpacked, pk.buf.data(), pk.buf.size() * 4, hipMemcpyHostToDevice, nullptr));
@@ -1481,7 +1488,11 @@ static void run_vjp(Net* N, const float* cot, float* gx) {
   if (N->pg_run) {                  // output_layer (1x1, 2 -> 2)
     const WgY y2 = wy(do2, (long long)Tp * Fb, 2);
     pg_weight(N, y2, wa(single(N->pyr0->p, 2), Tp, Fb, 2, 1, 0), (long long)B * Tp * Fb, 2, 0, 1.f, N->W->out_go);
-    pg_colsum(N, y2, B, 2, 1.f, nullptr, 0, N->W->out_go + 4, -1);
+    // the bias: sum over frames and bins of do2 = dframes x basisI.  Summed over the bins first, the real column of the inverse DFT is w[k] delta[k] = 0
+    // (periodic Hann): the exact gradient of bias[0] is 0, and a column sum of the fp32 do2 leaves rounding noise of the size of Adam's eps, which
+    // Adam then steps on.  Column sums of dframes in double, times the basis' bin sums in double, keep the cancellation exact
+    float* wsb = N->tmp(basis_bias_ws_floats(B, Tp, Kp));
+    if (!N->dry()) launch_basis_bias(dframes, Kp, B, Tp, N->W->basisI_sum, wsb, N->pg + N->W->out_go + 4, st);
   }
   for (int i = (int)N->tape.size() - 1; i >= 0; --i) N->tape[i]();
   if (N->pg_run) {                  // time embedding: Dense_0 of every ResBlock, then the two MLP layers (the Fourier projection W has no gradient)

@@ -163,6 +163,28 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const double* __restr
   if (out2) out2[n] += (float)(alpha * tot);
 }
 
+// output_layer.bias: the column sums of the frame gradient (colsum_part_kernel's partials) against the inverse DFT's bin sums, in double; one
+// workgroup, thread n takes the columns n, n + 256, ... and the 256 results are added in a fixed tree
+__global__ __launch_bounds__(256) void basis_bias_final_kernel(const double* __restrict__ part, int B, int K, int chunks, const double* __restrict__ bsum,
+                                                               float* out) {
+  __shared__ double red[2][256];
+  double a0 = 0.0, a1 = 0.0;
+  for (int k = threadIdx.x; k < K; k += 256) {
+    double tot = 0.0;
+    for (int b = 0; b < B; ++b)
+      for (int ch = 0; ch < chunks; ++ch) tot += part[((long long)b * chunks + ch) * K + k];
+    a0 += tot * bsum[k];
+    a1 += tot * bsum[K + k];
+  }
+  red[0][threadIdx.x] = a0; red[1][threadIdx.x] = a1;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { out[0] += (float)red[0][0]; out[1] += (float)red[1][0]; }
+}
+
 // GroupNorm affine gradients: per channel sum dz * xhat and sum dz, dz = da_eff * act'(z), z = xhat * gamma + beta.  x at (H, W); da at (H, W)
 // (da_mode 0), at (H/2, W/2) scaled by 1/4 (1: the box-downsample's adjoint) or at (2H, 2W) summed over the four children (2: nearest-upsample's)
 // (accumulated in double, like the column sums)
@@ -261,6 +283,14 @@ void launch_wgrad(const WgY& y, const WgA& a, long long M, int N, int layout, fl
 }
 
 long long colsum_ws_floats(int B, long long T, int N) { return 2LL * B * ((T + CS_ROWS - 1) / CS_ROWS) * N; }   // doubles
+long long basis_bias_ws_floats(int B, long long T, int K) { return colsum_ws_floats(B, T, K); }
+void launch_basis_bias(const float* x, int K, int B, long long T, const double* bsum, float* ws, float* out, hipStream_t st) {
+  WgY y; y.p = x; y.T = T; y.sb = T * K; y.sm = K; y.sn = 1;
+  const int chunks = (int)((T + CS_ROWS - 1) / CS_ROWS);
+  double* wd = (double*)ws;
+  hipLaunchKernelGGL(colsum_part_kernel, dim3(chunks, (K + 63) / 64, B), dim3(256), 0, st, y, K, chunks, wd);
+  hipLaunchKernelGGL(basis_bias_final_kernel, dim3(1), dim3(256), 0, st, (const double*)wd, B, K, chunks, bsum, out);
+}
 void launch_colsum(const WgY& y, int B, int N, float alpha, float* ws, float* bc, int ld_bc, float* out, float* out2, hipStream_t st) {
   const int chunks = (int)((y.T + CS_ROWS - 1) / CS_ROWS);
   double* wd = reinterpret_cast<double*>(ws);

@@ -11,6 +11,8 @@ _ALIASES = {
     "testing.EulerHeunSamplerDPS.EulerHeunSamplerDPS": "buddy_amd.testing.EulerHeunSamplerDPS.EulerHeunSamplerDPS",
     "testing.tester.Tester": "buddy_amd.testing.tester.Tester",
     "datasets.vctk.VCTKTestPaired": "buddy_amd.datasets.vctk.VCTKTestPaired",
+    "datasets.vctk.VCTKTrain": "buddy_amd.datasets.vctk.VCTKTrain",
+    "training.trainer.Trainer": "buddy_amd.training.trainer.Trainer",
 }
 
 

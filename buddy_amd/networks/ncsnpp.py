@@ -69,6 +69,16 @@ class _NetFn(torch.autograd.Function):
             _lib.check(_lib.load().buddy_ncsnpp_vjp(net._get_handle(), _lib.ptr(g), _lib.ptr(gx), _lib.stream_ptr()))
             return (gx, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 4)
         gx = torch.empty_like(g) if ctx.needs_input_grad[0] else None
+        if net._grad_flat is not None:
+            # an optimizer owns the flat gradient buffer (attach_flat): written in place -- the parameters' .grad are views of it -- and no gradient
+            # goes through autograd's accumulation.  The first backward after zero_grad overwrites, later ones add (torch's accumulate semantics)
+            gp = net._grad_flat
+            if gp.device != g.device:
+                raise _lib.BuddyHipError(f"the attached gradient buffer is on {gp.device}, the backward runs on {g.device}")
+            _lib.check(_lib.load().buddy_ncsnpp_vjp_params(net._get_handle(), _lib.ptr(g), _lib.ptr(gx), _lib.ptr(gp), int(net._grad_filled),
+                                                           _lib.stream_ptr()))
+            net._grad_filled = True
+            return (gx, None, None, None) + (None,) * (len(ctx.needs_input_grad) - 4)
         gp = torch.empty(net._n_params, dtype=torch.float32, device=g.device)
         _lib.check(_lib.load().buddy_ncsnpp_vjp_params(net._get_handle(), _lib.ptr(g), _lib.ptr(gx), _lib.ptr(gp), 0, _lib.stream_ptr()))
         grads = []
@@ -178,6 +188,10 @@ class NCSNppTime(nn.Module):
         self._plist = None          # the parameters in the flat order (built on first use)
         self._watch = False         # set by the first training forward (and in deep copies): forwards check the parameters' versions
         self._synced = None         # the parameters' _version when the library last received them
+        self._flat = None           # attach_flat: ONE device buffer in the library's flat order that every parameter's .data is a view of
+        self._flat_dirty = False    # params_changed: a kernel wrote the flat buffer behind torch's back (no _version moved)
+        self._grad_flat = None      # attach_flat: the optimizer's flat gradient buffer that buddy_ncsnpp_vjp_params writes into
+        self._grad_filled = False   # the gradient buffer holds a gradient since the last zero_grad (the next backward adds to it)
 
     @staticmethod
     def _init(name, shape, kind, init_scale, fourier_scale):
@@ -255,15 +269,60 @@ class NCSNppTime(nn.Module):
         trained, or is a deep copy.  ``device``: the GPU the call runs on (its input's device)."""
         if not self._watch and torch.is_grad_enabled() and any(p.requires_grad for p in self._params()):
             self._watch = True          # before the check: weights changed in place while the module was not yet watched are caught too
+        if self._handle is None:
+            self._flat_dirty = False    # the handle is made from the parameters as they are now
         if not self._watch or self._handle is None:
             return
         v = self._versions()
-        if v == self._synced:
+        if v == self._synced and not self._flat_dirty:
             return
-        with torch.no_grad():
-            flat = torch.cat([p.detach().reshape(-1).float().to(device) for p in self._params()])
+        if self._flat is not None:      # the parameters ARE this buffer: nothing to gather
+            flat = self._flat
+            if flat.device != torch.device(device):
+                raise _lib.BuddyHipError(f"the attached flat parameter buffer is on {flat.device}, the forward runs on {device}")
+        else:
+            with torch.no_grad():
+                flat = torch.cat([p.detach().reshape(-1).float().to(device) for p in self._params()])
         _lib.check(_lib.require_gpu().buddy_ncsnpp_update_params(self._handle, _lib.ptr(flat), _lib.stream_ptr()))
         self._synced = v
+        self._flat_dirty = False
+
+    def attach_flat(self, with_grad=False):
+        """Move the parameters onto ONE flat fp32 device buffer in the library's order (the order of ``buddy_ncsnpp_create`` and of
+        ``grad_params``) and re-point every ``param.data`` at its view; returns the buffer.  From then on the weight push uses it directly
+        (no ``torch.cat``) and a kernel may update all weights in one pass: it then calls ``params_changed()``.  ``with_grad``: also returns a
+        flat gradient buffer; ``buddy_ncsnpp_vjp_params`` writes into it, and the ``.grad`` of every parameter that requires grad is a view
+        of it.  ``.to()`` / ``.cuda()`` afterwards detach both (the module then behaves as before)."""
+        ps = self._params()
+        dev = ps[0].device
+        if dev.type != "cuda" or any(p.device != dev or p.dtype != torch.float32 for p in ps):
+            raise _lib.BuddyHipError("attach_flat: the parameters must be fp32 on one GPU (there is no CPU path): move the module first")
+        if self._flat is None:
+            with torch.no_grad():
+                flat = torch.cat([p.detach().reshape(-1) for p in ps])
+            for p, (off, n) in zip(ps, self._offsets):
+                p.data = flat[off:off + n].view(p.shape)
+            self._flat = flat
+            self._watch = True
+            self._synced = None         # the data is the same, the tensors are not: the next forward pushes once
+        if with_grad and self._grad_flat is None:
+            self._grad_flat = torch.zeros(self._n_params, dtype=torch.float32, device=dev)
+            self._grad_filled = False
+            for p, (off, n) in zip(ps, self._offsets):
+                if p.requires_grad:
+                    p.grad = self._grad_flat[off:off + n].view(p.shape)
+        return (self._flat, self._grad_flat) if with_grad else self._flat
+
+    def params_changed(self):
+        """A kernel wrote the attached flat parameter buffer (no ``_version`` moved): the next forward pushes the weights to the library"""
+        if self._flat is None:
+            raise _lib.BuddyHipError("params_changed without attach_flat: the parameters are separate tensors, torch tracks their versions")
+        self._watch = True
+        self._flat_dirty = True
+
+    def grads_zeroed(self):
+        """The optimizer's ``zero_grad``: the next backward overwrites the attached gradient buffer instead of adding to it"""
+        self._grad_filled = False
 
     def _train_params(self):
         """The parameters as autograd inputs when any of them requires grad (training), else ()"""
@@ -281,12 +340,13 @@ class NCSNppTime(nn.Module):
         new = cls.__new__(cls)
         memo[id(self)] = new
         for k, v in self.__dict__.items():
-            if k in ("_handle", "_parent", "_plist", "_synced"):
+            if k in ("_handle", "_parent", "_plist", "_synced", "_flat", "_grad_flat"):
                 new.__dict__[k] = None
             else:
                 new.__dict__[k] = copy.deepcopy(v, memo)
         new._fwd_id = 0
         new._watch = True
+        new._flat_dirty = new._grad_filled = False      # the copy's parameters are separate tensors again (attach_flat gives it its own buffer)
         return new
 
     def set_option(self, key, value):
@@ -330,6 +390,9 @@ class NCSNppTime(nn.Module):
     def _apply(self, fn, *a, **k):
         r = super()._apply(fn, *a, **k)
         self._plist = None
+        if self._flat is not None and any(p.data_ptr() != self._flat.data_ptr() + 4 * off for p, (off, _) in zip(self._params(), self._offsets)):
+            self._flat = self._grad_flat = None      # .to() / .cuda() gave the parameters new tensors: an attached optimizer notices and refuses
+            self._flat_dirty = self._grad_filled = False
         self._drop_handle()
         self._parent = None
         return r

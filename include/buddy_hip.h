@@ -70,6 +70,8 @@ int buddy_ncsnpp_vjp(void* handle, const float* cot, float* grad_x, void* stream
  * save_for_vjp = 2 (the activation arena then also holds the gradient kernels' workspaces): grad_params = (d y / d params)^T cot, ONE device
  * buffer of buddy_ncsnpp_param_count(_attn) floats in the flat parameter order that buddy_ncsnpp_create(_attn) takes (attention sites included).
  * accumulate = 0 overwrites it, 1 adds to it.  The Fourier projection W gets zero (the reference registers it with requires_grad=False).
+ * output_layer.bias is formed from the column sums of the frame gradient and the bin sums of the inverse-DFT basis, both in double (its real
+ * component is exactly 0 for the periodic Hann window; a column sum of the fp32 spectrum gradient leaves rounding noise there).
  * grad_x (nullable) receives the same input gradient as buddy_ncsnpp_vjp, bit for bit.  Exact fp32 arithmetic in every GEMM mode; deterministic
  * (split-K over fixed pixel chunks, reduced in a fixed order, no atomics).  BUDDY_ERR_STATE after a forward with save_for_vjp = 0 / 1. */
 int buddy_ncsnpp_vjp_params(void* handle, const float* cot, float* grad_x, float* grad_params, int accumulate, void* stream);
@@ -80,6 +82,31 @@ int buddy_ncsnpp_vjp_params(void* handle, const float* cot, float* grad_x, float
  * saved by any of them before the update is refused by buddy_ncsnpp_vjp / _vjp_params (BUDDY_ERR_STATE).  No handle on the store may have work in
  * flight on another stream while it runs. */
 int buddy_ncsnpp_update_params(void* handle, const float* dev_params, void* stream);
+
+/* ---- the optimizer step of training (optim.hip; reference training/trainer.py:225-258: clip_grad_norm_, Adam.step, update_ema) on flat fp32
+ * device buffers in the flat parameter order of buddy_ncsnpp_create / grad_params.  Two launches per step, none per parameter tensor.
+ *
+ * Sum of squares of n floats (the squared global gradient norm), accumulated in double: workgroup c sums the fixed chunk
+ * [c, c + 1) * buddy_optim_sqnorm_chunk() floats into partials[c]; one finalising workgroup adds the partials in a fixed order (thread t takes
+ * t, t + 256, ... in chunk order, then a fixed tree).  No atomics: two runs on the same input give the same bits.  partials: at least
+ * ceil(n / chunk) doubles of workspace.  The result stays on the device: out[0] is one double that buddy_optim_step reads there. */
+long long buddy_optim_sqnorm_chunk(void);
+int buddy_optim_sqnorm(const float* g, long long n, double* partials, double* out, void* stream);
+/* One pass over p, g, m, v, ema (n floats each, 16-byte aligned; 36 bytes per parameter):
+ *   clip  coef = min(1, max_norm / (sqrt(*sqnorm) + 1e-6)) as torch.nn.utils.clip_grad_norm_ (max_norm <= 0: coef = 1, sqnorm may be NULL);
+ *         the gradient used is coef * g.  g is NOT written: after the call it still holds the unclipped gradient.
+ *   Adam  torch.optim.Adam's defaults (no amsgrad, no weight decay) in the order of its single-tensor form: m = beta1 m + (1 - beta1) g,
+ *         v = beta2 v + (1 - beta2) g g, denom = sqrt(v) / bias2_sqrt + eps, p -= step_size * m / denom, with the host's
+ *         step_size = lr / (1 - beta1^t) and bias2_sqrt = sqrt(1 - beta2^t).  Every element is computed in double from the fp32 inputs and
+ *         rounded to fp32 once per stored value; the p update reads the stored (rounded) m and v.
+ *   EMA   ema = ema * ema_s + p_new * (1 - ema_s) (trainer.py:245-258); ema == NULL skips it.
+ * frozen: n_frozen <= 8 half-open element ranges [frozen[2 i], frozen[2 i + 1]) (host array; any alignment) inside which p, m, v are left
+ * untouched bit for bit -- the Fourier projection W, which torch's Adam never sees -- while the EMA still runs there. */
+int buddy_optim_step(float* p, const float* g, float* m, float* v, float* ema, long long n, const double* sqnorm, double max_norm, double beta1,
+                     double beta2, double eps, double step_size, double bias2_sqrt, double ema_s, const long long* frozen, int n_frozen,
+                     void* stream);
+/* the EMA on its own (Trainer.update_ema outside a fused step): ema = ema * ema_s + p * (1 - ema_s), n floats, 16-byte aligned */
+int buddy_optim_ema(float* ema, const float* p, long long n, double ema_s, void* stream);
 
 /* debugging / per-module parity: device pointer + NHWC dims ([B][frames][bins][C]) of the output of all_modules[idx]. */
 int buddy_ncsnpp_tap(void* handle, int module_idx, const float** ptr, int dims[4]);

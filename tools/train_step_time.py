@@ -1,11 +1,14 @@
 """Time one training step of the score network on one MI355X: EDM loss_fn + forward + parameter VJP + clip_grad_norm_ + Adam, at the reference's
 training segment (conf/exp/VCTK_16k_4s_time.yaml: 65 536 samples) and batch B = 8, nf = 128 (conf/network/ncsnpp.yaml).
 
-    python tools/train_step_time.py [--B 8] [--L 65536] [--steps 10] [--warmup 3] [--gemm f16x2]
+    python tools/train_step_time.py [--B 8] [--L 65536] [--steps 10] [--warmup 3] [--gemm f16x2] [--path torch|fused|both] [--rounds 3]
     python tools/train_step_time.py --stats kernel_stats.csv   # weight-gradient kernels' share and TFLOP/s from a rocprofv3 --stats run
 
 The weight-gradient FLOPs of a step (2 M N K of every GEMM wgrad_kernel runs, from the grid of each layer) are printed so that the stats
 summary can turn kernel time into TFLOP/s.  The figure is approximate: it counts useful FLOPs, not the padded tiles of the thin layers.
+--path torch is torch's clip_grad_norm_ + Adam on the separate parameter tensors; --path fused is buddy_amd.training.fused.FusedAdam (two library calls
+on flat buffers); --path both alternates the two in --rounds rounds in one process, each on its own network with the same weights, and also reports
+for each the time from the end of the parameter VJP to the point where the next forward can start (optimizer + weight push), synchronised.
 The time of one buddy_ncsnpp_update_params (the weight push after each optimizer step) is measured on its own.  Yardstick: the fp32 matrix peak, 64 FLOP/clk/SIMD x 1024 SIMDs x 2.4 GHz = 157 TFLOP/s."""
 from __future__ import annotations
 
@@ -83,6 +86,9 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--gemm", default=None)
+    ap.add_argument("--nf", type=int, default=None, help="network width (default: conf/network/ncsnpp.yaml)")
+    ap.add_argument("--path", default="torch", choices=("torch", "fused", "both"))
+    ap.add_argument("--rounds", type=int, default=3, help="--path both: alternating rounds")
     ap.add_argument("--stats", default=None, help="rocprofv3 kernel_stats.csv of a run of this tool: summarise it")
     ap.add_argument("--flops", type=float, default=0.0, help="weight-gradient FLOPs per step (printed by a timing run) for --stats")
     ap.add_argument("--stats-steps", type=int, default=1, help="training steps the profiled run executed (warmup included)")
@@ -98,32 +104,82 @@ def main():
     cfg = load_yaml(os.path.join(CONF_DIR, "network", "ncsnpp.yaml"))
     cfg.pop("_target_")
     cfg["gemm"] = a.gemm
+    if a.nf:
+        cfg["nf"] = a.nf
     cfg["stft"] = AttrDict(n_fft=cfg["stft"]["n_fft"], hop_length=cfg["stft"]["hop_length"], center=True)
-    net = NCSNppTime(**cfg)
-    net.load_state_dict({k: torch.from_numpy(v) for k, v in synth_state_dict(0, net.nf, net.ch_mult, net.num_res_blocks).items()})
-    net = net.cuda().requires_grad_(True)
     edm = EDM("ve_karras", SimpleNamespace(sigma_data=0.05, sigma_min=1e-5, sigma_max=10.0, rho=10.0))
-    opt = torch.optim.Adam(net.parameters(), lr=2e-4)
     torch.manual_seed(0)
     x = 0.05 * torch.randn(a.B, a.L, device="cuda")
 
-    def step():
-        loss, _ = edm.loss_fn(net, x)
-        loss = loss.mean()
-        opt.zero_grad(set_to_none=True)
-        loss.backward()
-        torch.nn.utils.clip_grad_norm_(net.parameters(), 1.0)
-        opt.step()
-        return loss
+    def make(path):
+        net = NCSNppTime(**cfg)
+        net.load_state_dict({k: torch.from_numpy(v) for k, v in synth_state_dict(0, net.nf, net.ch_mult, net.num_res_blocks).items()})
+        net = net.cuda().requires_grad_(True)
+        if path == "fused":
+            from buddy_amd.training.fused import FusedAdam
+            net.all_modules[0].W.requires_grad_(False)      # the Fourier projection gets no gradient: frozen range of the fused pass
+            opt = FusedAdam(net.parameters(), lr=2e-4, network=net)
+            update = lambda: opt.step(max_norm=1.0)
+        else:
+            opt = torch.optim.Adam(net.parameters(), lr=2e-4)
 
+            def update():
+                torch.nn.utils.clip_grad_norm_(net.parameters(), 1.0)
+                opt.step()
+
+        def backward():
+            loss, _ = edm.loss_fn(net, x)
+            loss = loss.mean()
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            return loss
+
+        def step():
+            loss = backward()
+            update()
+            return loss
+
+        def window():
+            """ms from the end of the parameter VJP until the next forward could start: optimizer + weight push, synchronised on both sides"""
+            backward()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            update()
+            net._sync_params(x.device)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+        return net, step, window
+
+    def timed(step, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            loss = step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / max(n, 1), loss
+
+    if a.path == "both":
+        legs = {p: make(p) for p in ("torch", "fused")}
+        for p in legs:
+            for _ in range(a.warmup):
+                legs[p][1]()
+        ms = {p: [] for p in legs}
+        win = {p: [] for p in legs}
+        for _ in range(a.rounds):
+            for p in legs:
+                ms[p].append(timed(legs[p][1], a.steps)[0])
+                win[p].append(float(np.median([legs[p][2]() for _ in range(3)])))
+        out = {"B": a.B, "L": a.L, "nf": legs["torch"][0].nf, "gemm": a.gemm or "default", "steps_per_round": a.steps, "rounds": a.rounds,
+               "n_params": legs["torch"][0]._n_params}
+        for p in legs:
+            out[p] = {"ms_per_step_rounds": [round(v, 2) for v in ms[p]], "ms_per_step": round(float(np.median(ms[p])), 2),
+                      "spread_ms": round(max(ms[p]) - min(ms[p]), 2), "vjp_end_to_next_forward_ms": round(float(np.median(win[p])), 2)}
+        print(json.dumps(out))
+        return
+    net, step, window = make(a.path)
     for _ in range(a.warmup):
         step()
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        loss = step()
-    torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) * 1e3 / max(a.steps, 1)
+    ms, loss = timed(step, a.steps)
     flops = wgrad_flops(net, a.B)
     # the weight push of one optimizer step on its own (NCSNppTime._sync_params -> buddy_ncsnpp_update_params)
     upd = []
@@ -135,7 +191,7 @@ def main():
         net._sync_params(x.device)
         torch.cuda.synchronize()
         upd.append((time.perf_counter() - t1) * 1e3)
-    print(json.dumps({"B": a.B, "L": a.L, "nf": net.nf, "gemm": a.gemm or "default", "steps": a.steps, "ms_per_step": round(ms, 2),
+    print(json.dumps({"B": a.B, "L": a.L, "nf": net.nf, "gemm": a.gemm or "default", "path": a.path, "steps": a.steps, "ms_per_step": round(ms, 2),
                       "loss": float(loss.detach()), "wgrad_flops_per_step": flops, "update_params_ms": round(float(np.median(upd)), 2),
                       "n_params": net._n_params}))
 
