@@ -43,6 +43,20 @@ _SIGS = {
     "buddy_optim_step": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, C.c_longlong, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double,
                                    C.c_double, C.c_double, C.c_double, C.POINTER(C.c_longlong), C.c_int, C.c_void_p]),
     "buddy_optim_ema": (C.c_int, [_f32p, _f32p, C.c_longlong, C.c_double, C.c_void_p]),
+    "buddy_weight_grad_workspace": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
+    "buddy_weight_grad_chunks": (C.c_int, [C.c_longlong, C.c_int, C.c_int]),
+    "buddy_weight_grad": (C.c_int, [_f32p, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, _f32p, _f32p, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_float, _f32p, _f32p, C.c_void_p]),
+    "buddy_colsum_workspace": (C.c_longlong, [C.c_int, C.c_longlong, C.c_int]),
+    "buddy_colsum": (C.c_int, [_f32p, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int, C.c_int, C.c_float, _f32p, _f32p, C.c_int,
+                               _f32p, _f32p, C.c_void_p]),
+    "buddy_basis_bias": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, _f32p, _f32p, C.c_void_p]),
+    "buddy_gn_param_grads_workspace": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "buddy_gn_param_grads": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_int, _f32p, C.c_int, C.c_int,
+                                       C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_void_p]),
+    "buddy_linear_bwd_w": (C.c_int, [_f32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_void_p]),
+    "buddy_linear_bwd_x": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.c_void_p]),
     "buddy_ncsnpp_tap": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int * 4)]),
     "buddy_prof_enable": (C.c_int, [C.c_int]),
     "buddy_wpe": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),

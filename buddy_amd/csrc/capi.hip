@@ -730,4 +730,78 @@ int buddy_blindop_optimize(void* h, const float* x_den, const float* noise, floa
   return blindop_optimize((BlindOp*)h, x_den, noise, t_op, n_iters, w_rec, w_reg, lr, beta1, beta2, weight_decay, (hipStream_t)stream);
 }
 
+// ---- parameter-gradient kernels (wgrad.hip) on their own: thin, argument-checked entries for the unit tests; net.hip calls the launchers directly
+long long buddy_weight_grad_workspace(long long M, int N, int K) { return (M < 1 || N < 1 || K < 1) ? 0 : wgrad_ws_floats(M, N, K); }
+int buddy_weight_grad_chunks(long long M, int N, int K) { return (M < 1 || N < 1 || K < 1) ? 0 : wgrad_chunks(M, N, K); }
+static bool src2_ok(const float* x0, const float* x1, int C0, int ld0, int ld1, int C) {
+  if (!x0 || C < 1) return false;
+  if (!x1) return ld0 >= C;
+  return C0 > 0 && C0 < C && ld0 >= C0 && ld1 >= C - C0;
+}
+static Src2 mk_src2(const float* x0, const float* x1, int C0, int ld0, int ld1, int C) {
+  Src2 s; s.p0 = x0; s.p1 = x1; s.C0 = x1 ? C0 : C; s.ld0 = ld0; s.ld1 = x1 ? ld1 : 0;
+  return s;
+}
+int buddy_weight_grad(const float* dy, long long T, long long sb, long long sm, long long sn, const float* x0, const float* x1, int C0, int ld0, int ld1,
+                      int H, int W, int Cin, int taps, int rs, const float* stats, const float* gamma, const float* beta, int G, int silu, int B, int N,
+                      int layout, float alpha, float* ws, float* out, void* stream) {
+  if (!dy || !ws || !out || B < 1 || H < 1 || W < 1 || N < 1 || T < 1 || !src2_ok(x0, x1, C0, ld0, ld1, Cin)) {
+    set_error("bad weight-gradient arguments (null pointer, empty shape, or a two-source split outside (0, Cin) / a row stride below its channel count)");
+    return BUDDY_ERR_ARG;
+  }
+  const long long M = (long long)B * H * W;
+  if (M % T != 0) { set_error("weight gradient: the dY view's rows per utterance T must divide B * H * W"); return BUDDY_ERR_ARG; }
+  if (taps != 1 && taps != 9) { set_error("weight gradient: taps must be 1 or 9"); return BUDDY_ERR_ARG; }
+  if (rs < 0 || rs > 2 || (rs == 2 && ((H | W) & 1))) { set_error("weight gradient: rs must be 0, 1 (box, source at 2H x 2W) or 2 (nearest, source at H/2 x W/2: even H, W)"); return BUDDY_ERR_ARG; }
+  if (layout < 0 || layout > 2 || (layout == 1 && taps != 9)) { set_error("weight gradient: layout must be 0 [N][K], 1 (torch OIHW, taps = 9 only) or 2 [K][N]"); return BUDDY_ERR_ARG; }
+  if (stats && (!gamma || !beta || G < 1 || Cin % G != 0)) { set_error("weight gradient: GroupNorm needs gamma, beta and a group count that divides Cin"); return BUDDY_ERR_ARG; }
+  WgY y; y.p = dy; y.T = T; y.sb = sb; y.sm = sm; y.sn = sn;
+  WgA a; a.x = mk_src2(x0, x1, C0, ld0, ld1, Cin); a.H = H; a.W = W; a.Cin = Cin; a.taps = taps; a.rs = rs;
+  a.stats = stats; a.gamma = stats ? gamma : nullptr; a.beta = stats ? beta : nullptr; a.G = stats ? G : 1; a.silu = silu ? 1 : 0;
+  launch_wgrad(y, a, M, N, layout, alpha, ws, out, (hipStream_t)stream);
+  return finish();
+}
+
+long long buddy_colsum_workspace(int B, long long T, int N) { return (B < 1 || T < 1 || N < 1) ? 0 : colsum_ws_floats(B, T, N); }
+int buddy_colsum(const float* dy, long long T, long long sb, long long sm, long long sn, int B, int N, float alpha, float* ws, float* bc, int ld_bc,
+                 float* out, float* out2, void* stream) {
+  if (!dy || !ws || B < 1 || T < 1 || N < 1 || (!bc && !out && !out2) || (bc && ld_bc < N)) {
+    set_error("bad column-sum arguments (null pointer, empty shape, no output, or ld_bc < N)"); return BUDDY_ERR_ARG;
+  }
+  WgY y; y.p = dy; y.T = T; y.sb = sb; y.sm = sm; y.sn = sn;
+  launch_colsum(y, B, N, alpha, ws, bc, ld_bc, out, out2, (hipStream_t)stream);
+  return finish();
+}
+int buddy_basis_bias(const float* x, int K, int B, long long T, const double* bsum, float* ws, float* out, void* stream) {
+  if (!x || !bsum || !ws || !out || K < 1 || B < 1 || T < 1) { set_error("bad basis-bias arguments (null pointer or empty shape)"); return BUDDY_ERR_ARG; }
+  launch_basis_bias(x, K, B, T, bsum, ws, out, (hipStream_t)stream);
+  return finish();
+}
+
+long long buddy_gn_param_grads_workspace(int B, int H, int W, int C) { return (B < 1 || H < 1 || W < 1 || C < 1) ? 0 : gn_pgrad_ws_floats(B, H, W, C); }
+int buddy_gn_param_grads(const float* x0, const float* x1, int C0, int ld0, int ld1, const float* stats, const float* gamma, const float* beta, int G,
+                         int silu, const float* da, int da_mode, int B, int H, int W, int C, float* ws, float* dgamma, float* dbeta, void* stream) {
+  if (!stats || !gamma || !beta || !da || !ws || !dgamma || !dbeta || B < 1 || H < 1 || W < 1 || !src2_ok(x0, x1, C0, ld0, ld1, C)) {
+    set_error("bad GroupNorm parameter-gradient arguments (null pointer, empty shape, or a two-source split outside (0, C) / a row stride below its channel count)");
+    return BUDDY_ERR_ARG;
+  }
+  if (G < 1 || C % G != 0) { set_error("GroupNorm parameter gradients: the group count must divide C"); return BUDDY_ERR_ARG; }
+  if (da_mode < 0 || da_mode > 2 || (da_mode == 1 && ((H | W) & 1))) {
+    set_error("GroupNorm parameter gradients: da_mode must be 0, 1 (da at H/2 x W/2: even H, W) or 2 (da at 2H x 2W)"); return BUDDY_ERR_ARG;
+  }
+  launch_gn_pgrad(mk_src2(x0, x1, C0, ld0, ld1, C), stats, gamma, beta, G, silu ? 1 : 0, da, da_mode, B, H, W, C, ws, dgamma, dbeta, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_linear_bwd_w(const float* dy, int ld_dy, const float* x, int silu_in, int B, int N, int K, float* gw, float* gb, float* gb2, void* stream) {
+  if (!dy || !x || !gw || B < 1 || N < 1 || K < 1 || ld_dy < N) { set_error("bad linear-backward arguments (null pointer, empty shape, or ld_dy < N)"); return BUDDY_ERR_ARG; }
+  launch_linear_bwd_w(dy, ld_dy, x, silu_in ? 1 : 0, B, N, K, gw, gb, gb2, (hipStream_t)stream);
+  return finish();
+}
+int buddy_linear_bwd_x(const float* dy, const float* Wm, const float* x, int silu_in, int B, int N, int K, float* dx, void* stream) {
+  if (!dy || !Wm || !dx || (silu_in && !x) || B < 1 || N < 1 || K < 1) { set_error("bad linear-backward arguments (null pointer or empty shape)"); return BUDDY_ERR_ARG; }
+  launch_linear_bwd_x(dy, Wm, x, silu_in ? 1 : 0, B, N, K, dx, (hipStream_t)stream);
+  return finish();
+}
+
 }  // extern "C"

@@ -5,6 +5,8 @@
 // Weight gradient: G[n][k] = sum_m dY[m][n] * A[m][k] with m = pixel (K of the GEMM, ~1 M at B = 8), n = output channel, k = tap * Cin + c.
 // A is never in HBM: the loader evaluates act(GroupNorm(x)) (and the box / nearest resampling of the down / up blocks) per element, from x,
 // the statistics, gamma and beta, like the fused input transforms of the forward.  Exact fp32 on the matrix cores (v_mfma_f32_32x32x2_f32).
+// (Exact means the products and their accumulation; the loader's normalisation and expf are fp32 evaluations.  Measured against float64 the whole
+// kernel stays at or below 5.1e-7 of the abs-max, beside 8.6e-7 for torch's own fp32 autograd: tests/test_hip_param_grad_kernels.py.)
 // Split-K over fixed pixel chunks: every workgroup writes its chunk's partial tile, a second pass sums the chunks in chunk order.  No atomics:
 // the result is bit-identical from run to run.
 #include "common.h"

@@ -108,6 +108,48 @@ int buddy_optim_step(float* p, const float* g, float* m, float* v, float* ema, l
 /* the EMA on its own (Trainer.update_ema outside a fused step): ema = ema * ema_s + p * (1 - ema_s), n floats, 16-byte aligned */
 int buddy_optim_ema(float* ema, const float* p, long long n, double ema_s, void* stream);
 
+/* ---- the parameter-gradient kernels of training on their own (wgrad.hip; the network reaches them through buddy_ncsnpp_vjp_params).  Every
+ * result is ADDED into its output, as gradients accumulate over micro-batches; no atomics, so two runs give the same bits.  All tensors are
+ * fp32 device buffers unless stated; workspaces are in floats (4 bytes) and need no initialisation.
+ *
+ * dY view (weight gradient and column sums): dY[m][n] = dy[(m / T) * sb + (m % T) * sm + n * sn], m < M.  A row-major [M][ld] gradient is
+ * T = rows per utterance, sb = T * ld, sm = ld, sn = 1; a per-utterance transposed one [B][N][T] (the attention's dV^T) is sb = T * N, sm = 1, sn = T.
+ *
+ * Weight gradient G[n][k] = sum_m dY[m][n] A[m][k], M = B * H * W pixels on the (H, W) grid of the convolution's output (NHWC, H = time = kx,
+ * W = frequency = ky), k = tap * Cin + c, tap = 3 (dh + 1) + (dw + 1) over the zero-padded 3 x 3 neighbourhood (taps = 9) or the pixel itself
+ * (taps = 1).  A is evaluated by the loader from the channel concatenation x = cat[x0 (C0 channels, row stride ld0), x1 (Cin - C0, ld1)] (x1 NULL:
+ * x0 alone, Cin channels): act(GroupNorm(x)) with stats [B][G][2] = (mean, rstd), gamma, beta [Cin] and SiLU if silu (stats NULL: no
+ * normalisation), then rs = 0: x on the (H, W) grid; rs = 1: x at (2H, 2W), the 2 x 2 box mean of the activated values; rs = 2: x at (H/2, W/2),
+ * nearest (H, W even).  out += alpha * G in layout 0 = [N][K], 1 = torch OIHW of a 3 x 3 convolution [N][Cin][ky = dw + 1][kx = dh + 1]
+ * (taps = 9), 2 = [K][N].  Exact fp32 products on the matrix cores; split over fixed pixel chunks (buddy_weight_grad_chunks of them, each a
+ * multiple of 32 pixels) that a second pass adds in chunk order.  ws: buddy_weight_grad_workspace(M, N, K = taps * Cin) floats. */
+long long buddy_weight_grad_workspace(long long M, int N, int K);
+int buddy_weight_grad_chunks(long long M, int N, int K);
+int buddy_weight_grad(const float* dy, long long T, long long sb, long long sm, long long sn, const float* x0, const float* x1, int C0, int ld0, int ld1,
+                      int H, int W, int Cin, int taps, int rs, const float* stats, const float* gamma, const float* beta, int G, int silu, int B, int N,
+                      int layout, float alpha, float* ws, float* out, void* stream);
+/* Column sums of a dY view of B utterances of T rows, accumulated in double: bc[b * ld_bc + n] = sum_t dY[b T + t][n] (overwritten, ld_bc >= N);
+ * out[n] and out2[n] += alpha * the sum over all rows.  bc, out, out2 are each optional (NULL), at least one is given.
+ * ws: buddy_colsum_workspace(B, T, N) floats, 8-byte aligned. */
+long long buddy_colsum_workspace(int B, long long T, int N);
+int buddy_colsum(const float* dy, long long T, long long sb, long long sm, long long sn, int B, int N, float alpha, float* ws, float* bc, int ld_bc,
+                 float* out, float* out2, void* stream);
+/* output_layer.bias: out[c] += sum_k bsum[c][k] * (sum over the B * T rows of x[row][k]), c = 0, 1; x [B * T][K] fp32, bsum [2][K] double (device);
+ * all in double, rounded once.  ws: buddy_colsum_workspace(B, T, K) floats, 8-byte aligned. */
+int buddy_basis_bias(const float* x, int K, int B, long long T, const double* bsum, float* ws, float* out, void* stream);
+/* GroupNorm affine gradients of a = act(GroupNorm(x)) given da: dgamma[c] += sum dz * xhat, dbeta[c] += sum dz, dz = da_eff * act'(z),
+ * z = xhat * gamma + beta, over the B * H * W pixels of x = cat[x0, x1] (as above) at (H, W); accumulated in double.  da [.][C] dense NHWC at
+ * (H, W) (da_mode 0), at (H/2, W/2) and scaled by 1/4 (da_mode 1: the box downsample's adjoint; H, W even) or at (2H, 2W) and summed over the four
+ * children (da_mode 2: the nearest upsample's).  ws: buddy_gn_param_grads_workspace(B, H, W, C) floats, 8-byte aligned. */
+long long buddy_gn_param_grads_workspace(int B, int H, int W, int C);
+int buddy_gn_param_grads(const float* x0, const float* x1, int C0, int ld0, int ld1, const float* stats, const float* gamma, const float* beta, int G,
+                         int silu, const float* da, int da_mode, int B, int H, int W, int C, float* ws, float* dgamma, float* dbeta, void* stream);
+/* Backward of y[b][j] = sum_k act(x[b][k]) W[j][k] + bias[j] (the time-embedding MLP; act = SiLU if silu_in, else the identity), B utterances:
+ * gw[j][k] += sum_b dy[b * ld_dy + j] act(x[b][k]); gb[j] and gb2[j] += sum_b dy[b * ld_dy + j] (each optional);
+ * dx[b][k] = act'(x[b][k]) * sum_j dy[b * N + j] W[j][k] (overwritten; dy dense).  x [B][K], W [N][K]. */
+int buddy_linear_bwd_w(const float* dy, int ld_dy, const float* x, int silu_in, int B, int N, int K, float* gw, float* gb, float* gb2, void* stream);
+int buddy_linear_bwd_x(const float* dy, const float* W, const float* x, int silu_in, int B, int N, int K, float* dx, void* stream);
+
 /* debugging / per-module parity: device pointer + NHWC dims ([B][frames][bins][C]) of the output of all_modules[idx]. */
 int buddy_ncsnpp_tap(void* handle, int module_idx, const float** ptr, int dims[4]);
 

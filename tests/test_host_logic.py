@@ -454,3 +454,38 @@ def test_longform_chunk_plan_and_crossfade():
             assert float((tot - 1).abs().max()) < 1e-6 and float(w.min()) >= 0.0
         out = lf.predict_chunked(lambda p: p, y, chunk, ov)
         assert out.shape == (L,) and float((out - y).abs().max()) < 1e-6
+
+
+def test_param_grad_entries_check_arguments():
+    """the unit entries of the parameter-gradient kernels refuse what the kernels cannot handle before anything is launched (no GPU needed), and
+    their size queries follow the split the kernels use: chunks of a multiple of 32 pixels, at least 256 pixels per chunk"""
+    from buddy_amd import _lib
+    lib = _lib.load()
+    ERR_ARG = 2          # BUDDY_ERR_ARG
+    assert lib.buddy_weight_grad_chunks(720, 64, 288) == 3 and lib.buddy_weight_grad_workspace(720, 64, 288) == 3 * 64 * 288
+    assert lib.buddy_weight_grad_chunks(30, 4, 72) == 1 and lib.buddy_weight_grad_chunks(576, 256, 3456) == 3
+    assert lib.buddy_weight_grad_workspace(0, 64, 288) == 0
+    assert lib.buddy_colsum_workspace(3, 2085, 100) == 2 * 3 * 2 * 100 and lib.buddy_gn_param_grads_workspace(2, 2, 331, 96) == 2 * 96 * 4
+    p = 4096          # a non-null address that is never dereferenced: every call below must fail its checks
+
+    def wg(dy=p, T=12, x0=p, x1=None, C0=0, ld0=8, ld1=0, H=3, W=4, Cin=8, taps=9, rs=0, stats=None, gamma=None, beta=None, G=1, B=2, N=4, layout=1,
+           ws=p, out=p):
+        return lib.buddy_weight_grad(dy, T, T * N, N, 1, x0, x1, C0, ld0, ld1, H, W, Cin, taps, rs, stats, gamma, beta, G, 0, B, N, layout, 1.0, ws, out, None)
+    for bad in (dict(dy=None), dict(x0=None), dict(ws=None), dict(out=None), dict(taps=3), dict(rs=3), dict(rs=-1), dict(rs=2), dict(layout=3),
+                dict(layout=1, taps=1), dict(stats=p), dict(stats=p, gamma=p, beta=p, G=3), dict(T=5), dict(ld0=7), dict(x1=p, C0=8, ld1=4),
+                dict(x1=p, C0=4, ld0=4, ld1=3), dict(B=0)):
+        assert wg(**bad) == ERR_ARG, bad
+        assert lib.buddy_last_error()
+
+    def gn(x1=None, C0=0, ld0=8, ld1=0, stats=p, G=2, da=p, da_mode=0, H=3, W=4, C=8, ws=p, dg=p, db=p):
+        return lib.buddy_gn_param_grads(p, x1, C0, ld0, ld1, stats, p, p, G, 1, da, da_mode, 2, H, W, C, ws, dg, db, None)
+    for bad in (dict(stats=None), dict(da=None), dict(ws=None), dict(dg=None), dict(G=3), dict(da_mode=3), dict(da_mode=-1), dict(da_mode=1),
+                dict(ld0=4), dict(x1=p, C0=0)):
+        assert gn(**bad) == ERR_ARG, bad
+    assert lib.buddy_colsum(None, 8, 32, 4, 1, 2, 4, 1.0, p, None, 0, p, None, None) == ERR_ARG
+    assert lib.buddy_colsum(p, 8, 32, 4, 1, 2, 4, 1.0, p, None, 0, None, None, None) == ERR_ARG          # no output
+    assert lib.buddy_colsum(p, 8, 32, 4, 1, 2, 4, 1.0, p, p, 3, None, None, None) == ERR_ARG             # ld_bc < N
+    assert lib.buddy_basis_bias(p, 130, 2, 8, None, p, p, None) == ERR_ARG
+    assert lib.buddy_linear_bwd_w(p, 3, p, 1, 2, 4, 8, p, None, None, None) == ERR_ARG                   # ld_dy < N
+    assert lib.buddy_linear_bwd_w(p, 4, p, 1, 2, 4, 8, None, None, None, None) == ERR_ARG
+    assert lib.buddy_linear_bwd_x(p, p, None, 1, 2, 4, 8, p, None) == ERR_ARG                            # SiLU needs x
