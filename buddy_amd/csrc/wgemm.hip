@@ -118,22 +118,11 @@ template <bool GEN, bool GNB = false>
 __global__ __launch_bounds__(WNT, 3) void wgemm_bf16x3_kernel(const WgemmArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE_BYTES];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  // XCD-aware order (hardware places workgroup b of the flattened grid on XCD b % 8, each XCD with its own L2).
-  //  * batched form, positions a multiple of 8 (a.pz > 0: 1-D grid of pz * tiles * NB workgroups): XCD x takes the positions x, x + 8, ... and walks
-  //    all their tiles, so a position's weight panel (K x 128 x 6 B per column block) is fetched into ONE L2 instead of all eight (r03 PMC:
-  //    the GEMM fetched 1.42x its V bytes; 8 x 25 MB of panels per 256 -> 256 convolution were most of the excess);
-  //  * otherwise (blockIdx.z = position): each XCD gets a contiguous range of logical tiles.
-  // In both, the column blocks of one row tile are adjacent, so the second column block finds its V rows in the same L2.
+  // XCD-aware order (xcd_tile_position, common.h): folded, a position's weight panel is K x 128 x 6 B per column block (r03 PMC: the GEMM fetched
+  // 1.42x its V bytes; 8 x 25 MB of panels per 256 -> 256 convolution were most of the excess).  In both forms the column blocks of one row tile
+  // are adjacent, so the second column block finds its V rows in the same L2.
   int lid, p;
-  if (a.pz > 0) {
-    const int orig = blockIdx.x, xcd = orig & 7, k = orig >> 3;     // k-th workgroup of this XCD: gx * pz / 8 of them
-    lid = k % a.gx; p = xcd + 8 * (k / a.gx);
-  } else {
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7, k = orig >> 3;
-    lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    p = blockIdx.z;
-  }
+  xcd_tile_position(a.pz, a.gx, lid, p);
   const int nb = lid % a.NB, m0 = (lid / a.NB) * WBM;
   const float* __restrict__ V = a.V + (long long)p * a.sV;
   const unsigned char* __restrict__ U3 = a.U3 + ((long long)p * a.NB + nb) * a.S * STAGE_BYTES;
@@ -401,19 +390,50 @@ __global__ __launch_bounds__(256) void wgemm_pack2_kernel(const float* __restric
   out[i] = (u32x4)sp.p[q];
 }
 
-__global__ __launch_bounds__(WNT, 3) void wgemm_f16x2_kernel(const WgemmArgs a) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[(2 * STAGE2_BYTES > 4 * 32 * 68 * 4) ? 2 * STAGE2_BYTES : 4 * 32 * 68 * 4];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  int lid, p;                                                 // XCD-aware order: see wgemm_bf16x3_kernel
-  if (a.pz > 0) {
-    const int orig = blockIdx.x, xcd = orig & 7, k = orig >> 3;
-    lid = k % a.gx; p = xcd + 8 * (k / a.gx);
-  } else {
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7, k = orig >> 3;
-    lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    p = blockIdx.z;
+// ---- the pieces every f16x2 kernel of this file is written on
+// LDS of a workgroup with one column block: two weight stages, or the four waves' epilogue slabs (32 rows x 68 floats each) where those are larger
+constexpr int LDS2_BYTES = (2 * STAGE2_BYTES > 4 * 32 * 68 * 4) ? 2 * STAGE2_BYTES : 4 * 32 * 68 * 4;
+
+// The weights of K-stage s of CB column blocks, global -> LDS by LDS-DMA: 4 x 16 B per thread and column block.  Ub = the first column block's stage images
+// (the next block's follow S images later), lds0 = this wave's 1 KB of LDS buffer 0, boff = 16 * tid; buffer s & 1 holds the CB images side by side.
+template <int CB>
+__device__ __forceinline__ void f16x2_dma_stage(const char* Ub, int S, int s, unsigned lds0, unsigned boff) {
+#pragma unroll
+  for (int t = 0; t < CB; ++t) {
+    const void* base = uniform_ptr(Ub + ((long long)t * S + s) * STAGE2_BYTES);
+    const unsigned l = lds0 + ((s & 1) * CB + t) * STAGE2_BYTES;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) glds16_asm(base, boff + j * (WNT * 16), l + j * (WNT * 16));
   }
+}
+
+// The 24 RT MFMAs of one 16 KB stage image (Bcur = image + 16 * lane) on the split rows av[row tile][k chunk] of RT 32-row tiles, into acc[row tile][4].
+// Per k chunk: the eight weight fragments, then one product term at a time over all row tiles and the four 32-column blocks, smallest terms first
+// (lo*hi, hi*lo, hi*hi: B plane, A plane), so that consecutive MFMAs never share an accumulator.
+template <int RT>
+__device__ __forceinline__ void f16x2_mfma_stage(const unsigned char* Bcur, const Split2 (&av)[RT][2], f32x16 (*acc)[4]) {
+#pragma unroll
+  for (int kc = 0; kc < 2; ++kc) {
+    f16x8 b[4][2];
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+      for (int q = 0; q < 2; ++q) b[cb][q] = *reinterpret_cast<const f16x8*>(Bcur + ((kc * 4 + cb) * 2 + q) * FRAG);
+    constexpr int PB[3] = {1, 0, 0}, PA[3] = {0, 1, 0};
+#pragma unroll
+    for (int tm = 0; tm < 3; ++tm)
+#pragma unroll
+      for (int t = 0; t < RT; ++t)
+#pragma unroll
+        for (int cb = 0; cb < 4; ++cb) acc[t][cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b[cb][PB[tm]], av[t][kc].p[PA[tm]], acc[t][cb], 0, 0, 0);
+  }
+}
+
+__global__ __launch_bounds__(WNT, 3) void wgemm_f16x2_kernel(const WgemmArgs a) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[LDS2_BYTES];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  int lid, p;
+  xcd_tile_position(a.pz, a.gx, lid, p);
   const int nb = lid % a.NB, m0 = (lid / a.NB) * WBM;
   const float* __restrict__ V = a.V + (long long)p * a.sV;
   const unsigned char* __restrict__ U2 = a.U3 + ((long long)p * a.NB + nb) * a.S * STAGE2_BYTES;
@@ -458,36 +478,18 @@ __global__ __launch_bounds__(WNT, 3) void wgemm_f16x2_kernel(const WgemmArgs a) 
 #pragma unroll
     for (int j = 0; j < 4; ++j) r[j] = *reinterpret_cast<const float4*>(base + aoff + 16 * j);
   };
-  auto dmaB = [&](int s) {
-    const void* base = uniform_ptr(Ub + (long long)s * STAGE2_BYTES);
-    const unsigned l = lds0 + (s & 1) * STAGE2_BYTES;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) glds16_asm(base, boff + j * (WNT * 16), l + j * (WNT * 16));
-  };
+  auto dmaB = [&](int s) { f16x2_dma_stage<1>(Ub, S, s, lds0, boff); };
   // NB / NA (compile time): this stage requests the weights of stage s + 1 / the A rows of stage s + 2 (the last two stages are peeled: behind a run-time `if`
   // the wait-count pass must assume the loads were skipped and waits for everything in flight).
   auto stage = [&](int s, float4 (&r)[4], auto nb_, auto na_) {
     constexpr bool NB = decltype(nb_)::value, NA = decltype(na_)::value;
     // the stage's A rows are split FIRST (their registers are then dead and the reload below lands in place: with a copy kept for later, hipcc renames
     // the reload's destination and moves it back at the loop's back edge -- behind a vmcnt(0))
-    const Split2 av[2] = {split2(r[0], r[1], sv), split2(r[2], r[3], sv)};
+    const Split2 av[1][2] = {{split2(r[0], r[1], sv), split2(r[2], r[3], sv)}};
     if (NB) dmaB(s + 1);
     if (NA) loadA(s + 2, r);
     __builtin_amdgcn_sched_barrier(0);
-    const unsigned char* Bcur = smem + (s & 1) * STAGE2_BYTES + lane * 16;
-#pragma unroll
-    for (int kc = 0; kc < 2; ++kc) {
-      f16x8 b[4][2];
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) b[cb][q] = *reinterpret_cast<const f16x8*>(Bcur + ((kc * 4 + cb) * 2 + q) * FRAG);
-      constexpr int PB[3] = {1, 0, 0}, PA[3] = {0, 1, 0};     // smallest terms first: lo*hi, hi*lo, hi*hi (B plane, A plane)
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b[cb][PB[t]], av[kc].p[PA[t]], acc[cb], 0, 0, 0);
-    }
+    f16x2_mfma_stage<1>(smem + (s & 1) * STAGE2_BYTES + lane * 16, av, &acc);
     if (NB) { if (NA) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
     __syncthreads();
   };
@@ -541,8 +543,13 @@ __global__ __launch_bounds__(WNT, 3) void wgemm_f16x2_kernel(const WgemmArgs a) 
 // of the row's 32 values it is about to split; while that stays below 2^15 under the current scale nothing happens, otherwise the row's accumulators are
 // multiplied by the (exact) power of two that takes them to the new scale, which puts the stage's abs-max into [2^12, 2^13).  A row's result depends on
 // nothing but the row, no pre-pass re-reads A (the first version's did, from beyond L2: it took away what the halved MFMA count gave), and the rescale is a
-// wave-uniform branch taken a few times per row.  Structure = wgemm_f16x2_kernel (32-row waves, LDS-DMA weight stages, two K-stages of A in flight)
-// with the two-source A of wgemm_bf16x3_kernel<true, GNB> and its epilogues.
+// wave-uniform branch taken a few times per row.
+// One body in three tilings, all with the two-source A of wgemm_bf16x3_kernel<true, GNB>, LDS-DMA weight stages and f16x2_gen_epilogue, chosen per launch
+// by launch_f16x2_gen (gen_colpair / gen_rows64 below):
+//   wgemm_f16x2_gen_kernel<1, GNB>   32-row waves, one column block   (pipeline of wgemm_f16x2_kernel)       the small launches
+//   wgemm_f16x2_gen_kernel<2, GNB>   32-row waves, two column blocks  (the same; A read and split once)      N % 256 == 0 from 32768 rows on
+//   wgemm_f16x2_gen64_kernel<GNB>    64-row waves, one column block   (pipeline of wgemm_f16x2_rt2_kernel)   the other launches from 32768 rows on
+// They share f16x2_gen_rows, f16x2_row_rescale, f16x2_dma_stage and f16x2_mfma_stage; a row's result is the same bits in all three.
 
 // epilogues of wgemm_bf16x3_kernel<true, GNB> for one 32-row x 128-column accumulator tile of a wave (rows rbase ..., x the rows' inverse scale)
 // through the wave-private LDS slab St, 256-byte row pieces
@@ -642,134 +649,63 @@ __device__ __forceinline__ void f16x2_gen_epilogue(const WgemmArgs& a, const f32
   }
 }
 
-template <bool GNB>
-__global__ __launch_bounds__(WNT, 3) void wgemm_f16x2_gen_kernel(const WgemmArgs a) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[(2 * STAGE2_BYTES > 4 * 32 * 68 * 4) ? 2 * STAGE2_BYTES : 4 * 32 * 68 * 4];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  int lid;
-  {
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7, k = orig >> 3;
-    lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
-  const int nb = lid % a.NB, m0 = (lid / a.NB) * WBM;
-  const unsigned char* __restrict__ U2 = a.U3 + (long long)nb * a.S * STAGE2_BYTES;
-  const int S = a.S;
-  int row = m0 + wid * 32 + (lane & 31);
+// A 32-row tile's pointers into the two-source A: lane (row r = lane & 31, half h = lane >> 5) reads 16 consecutive floats per K-stage, channels >= C0
+// from the second source; rows past M are clamped (never stored)
+__device__ __forceinline__ void f16x2_gen_rows(const WgemmArgs& a, int row, int lane, const float*& p0, const float*& p1) {
   if (row >= a.Mt) row = a.Mt - 1;
-  const float* Ap0 = a.V + (long long)row * a.ldA0 + 16 * (lane >> 5);
-  const float* Ap1 = a.A1 ? a.A1 + (long long)row * a.ldA1 + 16 * (lane >> 5) - a.C0 : Ap0;       // channels >= C0 come from the second source
-  const int s1 = a.A1 ? a.C0 / WKS : S;                                                            // first K-stage of the second source
-  // running per-row power of two (see the header comment): exponent field of the scale's reference magnitude, the scale itself
-  int ecur = 15;
-  float sv = __uint_as_float((unsigned)(266 - 15) << 23);
-  const unsigned boff = (unsigned)tid * 16u;
-  const char* Ub = reinterpret_cast<const char*>(U2);
-
-  f32x16 acc[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
-
-  float4 ra[2][4];
-  const unsigned lds0 = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)(__attribute__((address_space(3))) char*)smem + wid * 1024);
-  auto loadA = [&](int s, float4 (&r)[4]) {
-    const float* q = (s >= s1 ? Ap1 : Ap0) + s * WKS;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) r[j] = *reinterpret_cast<const float4*>(q + 4 * j);
-  };
-  auto dmaB = [&](int s) {
-    const void* base = uniform_ptr(Ub + (long long)s * STAGE2_BYTES);
-    const unsigned l = lds0 + (s & 1) * STAGE2_BYTES;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) glds16_asm(base, boff + j * (WNT * 16), l + j * (WNT * 16));
-  };
-  auto stage = [&](int s, float4 (&r)[4], auto nb_, auto na_) {
-    constexpr bool NB = decltype(nb_)::value, NA = decltype(na_)::value;
-    {
-      float mx = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) mx = fmaxf(fmaxf(mx, fmaxf(fabsf(r[j].x), fabsf(r[j].y))), fmaxf(fabsf(r[j].z), fabsf(r[j].w)));
-      mx = fmaxf(mx, __shfl_xor(mx, 32));                       // the row's other sixteen k of this stage
-      const int es = min((int)(__float_as_uint(mx) >> 23), 253);
-      const bool grow = es > ecur + 2;                          // the stage would leave [0, 2^15) under the current scale
-      if (__any(grow)) {
-        const int d = grow ? ecur - es : 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-          for (int q = 0; q < 16; ++q) acc[c][q] = ldexpf(acc[c][q], d);
-        if (grow) { ecur = es; sv = __uint_as_float((unsigned)(266 - es) << 23); }
-      }
-    }
-    const Split2 av[2] = {split2(r[0], r[1], sv), split2(r[2], r[3], sv)};
-    if (NB) dmaB(s + 1);
-    if (NA) loadA(s + 2, r);
-    __builtin_amdgcn_sched_barrier(0);
-    const unsigned char* Bcur = smem + (s & 1) * STAGE2_BYTES + lane * 16;
-#pragma unroll
-    for (int kc = 0; kc < 2; ++kc) {
-      f16x8 b[4][2];
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) b[cb][q] = *reinterpret_cast<const f16x8*>(Bcur + ((kc * 4 + cb) * 2 + q) * FRAG);
-      constexpr int PB[3] = {1, 0, 0}, PA[3] = {0, 1, 0};
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) acc[cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b[cb][PB[t]], av[kc].p[PA[t]], acc[cb], 0, 0, 0);
-    }
-    if (NB) { if (NA) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-    __syncthreads();
-  };
-  dmaB(0);
-  loadA(0, ra[0]);
-  loadA(1, ra[1]);                                             // S is even (wgemm_f16x2_supported)
-  asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  __syncthreads();
-  int s = 0;
-  for (; s + 2 < S; s += 2) {
-    stage(s, ra[0], std::true_type{}, std::true_type{});
-    stage(s + 1, ra[1], std::true_type{}, std::true_type{});
-  }
-  stage(s, ra[0], std::true_type{}, std::false_type{});
-  stage(s + 1, ra[1], std::false_type{}, std::false_type{});
-  const float inv = __uint_as_float((unsigned)(ecur - 12) << 23) * a.uinv[0];
-
-  f16x2_gen_epilogue<GNB>(a, acc, inv, m0 + wid * 32, nb, reinterpret_cast<float*>(smem) + wid * (32 * 68), lane);
+  p0 = a.V + (long long)row * a.ldA0 + 16 * (lane >> 5);
+  p1 = a.A1 ? a.A1 + (long long)row * a.ldA1 + 16 * (lane >> 5) - a.C0 : p0;
 }
 
-// The same with TWO column blocks per workgroup (128 rows x 256 columns, 32-row waves, 128 accumulators per lane, two workgroups per CU): with N = 256 the
-// two workgroups of a row block each read -- and split -- the same A rows; measured in isolation (tools/gen_gemm_one.py with the stores and the matrix work
-// taken out) that second read costs like a first one.  Here a row block's A is read and split once for both column blocks; the weight stage is 32 KB.
-template <bool GNB>
-__global__ __launch_bounds__(WNT, 2) void wgemm_f16x2_gencp_kernel(const WgemmArgs a) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[4 * STAGE2_BYTES];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  int lid;
-  {
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7, k = orig >> 3;
-    lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
-  const int NP = a.NB >> 1, np = lid % NP, m0 = (lid / NP) * WBM;
-  const unsigned char* __restrict__ U2 = a.U3 + (long long)(2 * np) * a.S * STAGE2_BYTES;       // column block 2 np; 2 np + 1 follows S stage images later
-  const int S = a.S;
-  int row = m0 + wid * 32 + (lane & 31);
-  if (row >= a.Mt) row = a.Mt - 1;
-  const float* Ap0 = a.V + (long long)row * a.ldA0 + 16 * (lane >> 5);
-  const float* Ap1 = a.A1 ? a.A1 + (long long)row * a.ldA1 + 16 * (lane >> 5) - a.C0 : Ap0;
-  const int s1 = a.A1 ? a.C0 / WKS : S;
-  int ecur = 15;
-  float sv = __uint_as_float((unsigned)(266 - 15) << 23);
-  const unsigned boff = (unsigned)tid * 16u;
-  const char* Ub = reinterpret_cast<const char*>(U2);
-
-  f32x16 acc[2][4];
+// The running per-row power of two (see the header comment) of one 32-row tile that owns NS accumulator sets: r = the K-stage about to be split, ecur =
+// the exponent field of the current scale's reference magnitude, sv = the scale itself.
+template <int NS>
+__device__ __forceinline__ void f16x2_row_rescale(const float4 (&r)[4], f32x16 (*acc)[4], int& ecur, float& sv) {
+  float mx = 0.f;
 #pragma unroll
-  for (int t = 0; t < 2; ++t)
+  for (int j = 0; j < 4; ++j) mx = fmaxf(fmaxf(mx, fmaxf(fabsf(r[j].x), fabsf(r[j].y))), fmaxf(fabsf(r[j].z), fabsf(r[j].w)));
+  mx = fmaxf(mx, __shfl_xor(mx, 32));                         // the row's other sixteen k of this stage
+  const int es = min((int)(__float_as_uint(mx) >> 23), 253);
+  const bool grow = es > ecur + 2;                            // the stage would leave [0, 2^15) under the current scale
+  if (__any(grow)) {
+    const int d = grow ? ecur - es : 0;
+#pragma unroll
+    for (int t = 0; t < NS; ++t)
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int q = 0; q < 16; ++q) acc[t][c][q] = ldexpf(acc[t][c][q], d);
+    if (grow) { ecur = es; sv = __uint_as_float((unsigned)(266 - es) << 23); }
+  }
+}
+constexpr int GEN_E0 = 15;                                    // a row's scale before its first stage: exponent field GEN_E0, scale 2^(139 - GEN_E0)
+
+// 32-row waves, CB column blocks per workgroup (workgroup = 128 rows x 128 CB columns); pipeline of wgemm_f16x2_kernel (two K-stages of A in flight,
+// the stage loop unrolled by two, the last two stages peeled).
+//  * CB = 1: three workgroups per CU.
+//  * CB = 2 (128 accumulators per lane, two workgroups per CU, a 32 KB weight stage): with N = 256 the two workgroups of a row block each read -- and
+//    split -- the same A rows; measured in isolation (tools/gen_gemm_one.py with the stores and the matrix work taken out) that second read costs like
+//    a first one.  Here a row block's A is read and split once for both column blocks.
+template <int CB, bool GNB>
+__global__ __launch_bounds__(WNT, CB == 1 ? 3 : 2) void wgemm_f16x2_gen_kernel(const WgemmArgs a) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[CB == 1 ? LDS2_BYTES : 2 * CB * STAGE2_BYTES];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int lid = xcd_tile(blockIdx.x, gridDim.x);
+  static_assert(CB == 1 || CB == 2, "NP below is NB / CB as a shift");
+  const int NP = a.NB >> (CB - 1), np = lid % NP, m0 = (lid / NP) * WBM;                          // column blocks CB np ... CB np + CB - 1
+  const int S = a.S;
+  const char* Ub = reinterpret_cast<const char*>(a.U3) + (long long)(CB * np) * S * STAGE2_BYTES;
+  const float* Ap0;
+  const float* Ap1;
+  f16x2_gen_rows(a, m0 + wid * 32 + (lane & 31), lane, Ap0, Ap1);
+  const int s1 = a.A1 ? a.C0 / WKS : S;                                                            // first K-stage of the second source
+  int ecur = GEN_E0;
+  float sv = __uint_as_float((unsigned)(266 - GEN_E0) << 23);
+  const unsigned boff = (unsigned)tid * 16u;
+
+  f32x16 acc[CB][4];
+#pragma unroll
+  for (int t = 0; t < CB; ++t)
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
@@ -782,56 +718,16 @@ __global__ __launch_bounds__(WNT, 2) void wgemm_f16x2_gencp_kernel(const WgemmAr
 #pragma unroll
     for (int j = 0; j < 4; ++j) r[j] = *reinterpret_cast<const float4*>(q + 4 * j);
   };
-  auto dmaB = [&](int s) {
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const void* base = uniform_ptr(Ub + ((long long)t * S + s) * STAGE2_BYTES);
-      const unsigned l = lds0 + ((s & 1) * 2 + t) * STAGE2_BYTES;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) glds16_asm(base, boff + j * (WNT * 16), l + j * (WNT * 16));
-    }
-  };
+  auto dmaB = [&](int s) { f16x2_dma_stage<CB>(Ub, S, s, lds0, boff); };
   auto stage = [&](int s, float4 (&r)[4], auto nb_, auto na_) {
     constexpr bool NB = decltype(nb_)::value, NA = decltype(na_)::value;
-    {
-      float mx = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) mx = fmaxf(fmaxf(mx, fmaxf(fabsf(r[j].x), fabsf(r[j].y))), fmaxf(fabsf(r[j].z), fabsf(r[j].w)));
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      const int es = min((int)(__float_as_uint(mx) >> 23), 253);
-      const bool grow = es > ecur + 2;
-      if (__any(grow)) {
-        const int d = grow ? ecur - es : 0;
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int c = 0; c < 4; ++c)
-#pragma unroll
-            for (int q = 0; q < 16; ++q) acc[t][c][q] = ldexpf(acc[t][c][q], d);
-        if (grow) { ecur = es; sv = __uint_as_float((unsigned)(266 - es) << 23); }
-      }
-    }
-    const Split2 av[2] = {split2(r[0], r[1], sv), split2(r[2], r[3], sv)};
+    f16x2_row_rescale<CB>(r, acc, ecur, sv);
+    const Split2 av[1][2] = {{split2(r[0], r[1], sv), split2(r[2], r[3], sv)}};
     if (NB) dmaB(s + 1);
     if (NA) loadA(s + 2, r);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const unsigned char* Bcur = smem + ((s & 1) * 2 + t) * STAGE2_BYTES + lane * 16;
-#pragma unroll
-      for (int kc = 0; kc < 2; ++kc) {
-        f16x8 b[4][2];
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-          for (int q = 0; q < 2; ++q) b[cb][q] = *reinterpret_cast<const f16x8*>(Bcur + ((kc * 4 + cb) * 2 + q) * FRAG);
-        constexpr int PB[3] = {1, 0, 0}, PA[3] = {0, 1, 0};
-#pragma unroll
-        for (int tm = 0; tm < 3; ++tm)
-#pragma unroll
-          for (int cb = 0; cb < 4; ++cb) acc[t][cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b[cb][PB[tm]], av[kc].p[PA[tm]], acc[t][cb], 0, 0, 0);
-      }
-    }
+    for (int t = 0; t < CB; ++t) f16x2_mfma_stage<1>(smem + ((s & 1) * CB + t) * STAGE2_BYTES + lane * 16, av, &acc[t]);
     if (NB) { if (NA) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
     __syncthreads();
   };
@@ -848,39 +744,38 @@ __global__ __launch_bounds__(WNT, 2) void wgemm_f16x2_gencp_kernel(const WgemmAr
   stage(s, ra[0], std::true_type{}, std::false_type{});
   stage(s + 1, ra[1], std::false_type{}, std::false_type{});
   const float inv = __uint_as_float((unsigned)(ecur - 12) << 23) * a.uinv[0];
+  float* St = reinterpret_cast<float*>(smem) + wid * (32 * 68);
+  // CB = 1 outside the loop: as the body of a one-trip loop its GNB epilogue compiles to 168 VGPRs and 29 spills instead of 162 and none
+  if constexpr (CB == 1) f16x2_gen_epilogue<GNB>(a, acc[0], inv, m0 + wid * 32, np, St, lane);
+  else {
 #pragma unroll
-  for (int t = 0; t < 2; ++t)
-    f16x2_gen_epilogue<GNB>(a, acc[t], inv, m0 + wid * 32, 2 * np + t, reinterpret_cast<float*>(smem) + wid * (32 * 68), lane);
+    for (int t = 0; t < CB; ++t) f16x2_gen_epilogue<GNB>(a, acc[t], inv, m0 + wid * 32, CB * np + t, St, lane);
+  }
 }
 
-// The same with 64 rows per wave (the tiling of wgemm_f16x2_rt2_kernel below: workgroup = 256 rows x 128 columns, 128 accumulators per lane, two workgroups
-// per CU, one K-stage of A in flight): a weight stage is fetched once per 256 rows instead of once per 128.
+// 64-row waves (the tiling and pipeline of wgemm_f16x2_rt2_kernel below: workgroup = 256 rows x 128 columns, two 32-row tiles per wave each with a
+// running scale of its own, 128 accumulators per lane, two workgroups per CU, ONE K-stage of A in flight, an un-paired stage loop with one peeled stage):
+// a weight stage is fetched once per 256 rows instead of once per 128.
+// Kept as a kernel of its own on the shared pieces, not as a row-tile parameter of wgemm_f16x2_gen_kernel: prefetch distance, loop pairing, peel count
+// and every wait count differ, so the merged body would be the two pipelines side by side under `if constexpr` -- no text shared beyond what the helpers
+// already share.  As written here both instantiations keep the instruction stream they had as a free-standing copy (235 / 245 VGPRs; at 245 of 256 the
+// GNB form has little room for a body that compiles differently, and the CB = 1 epilogue above shows how little it takes).
 template <bool GNB>
-__global__ __launch_bounds__(WNT, 2) void wgemm_f16x2_gen2_kernel(const WgemmArgs a) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[(2 * STAGE2_BYTES > 4 * 32 * 68 * 4) ? 2 * STAGE2_BYTES : 4 * 32 * 68 * 4];
+__global__ __launch_bounds__(WNT, 2) void wgemm_f16x2_gen64_kernel(const WgemmArgs a) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[LDS2_BYTES];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  int lid;
-  {
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7, k = orig >> 3;
-    lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-  }
+  const int lid = xcd_tile(blockIdx.x, gridDim.x);
   const int nb = lid % a.NB, m0 = (lid / a.NB) * (2 * WBM);
-  const unsigned char* __restrict__ U2 = a.U3 + (long long)nb * a.S * STAGE2_BYTES;
   const int S = a.S;
+  const char* Ub = reinterpret_cast<const char*>(a.U3) + (long long)nb * S * STAGE2_BYTES;
   const float* Ap0[2];
   const float* Ap1[2];
 #pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int row = min(m0 + wid * 64 + t * 32 + (lane & 31), a.Mt - 1);
-    Ap0[t] = a.V + (long long)row * a.ldA0 + 16 * (lane >> 5);
-    Ap1[t] = a.A1 ? a.A1 + (long long)row * a.ldA1 + 16 * (lane >> 5) - a.C0 : Ap0[t];
-  }
+  for (int t = 0; t < 2; ++t) f16x2_gen_rows(a, m0 + wid * 64 + t * 32 + (lane & 31), lane, Ap0[t], Ap1[t]);
   const int s1 = a.A1 ? a.C0 / WKS : S;
-  int ecur[2] = {15, 15};
-  float sv[2] = {__uint_as_float((unsigned)(266 - 15) << 23), __uint_as_float((unsigned)(266 - 15) << 23)};
+  int ecur[2] = {GEN_E0, GEN_E0};
+  float sv[2] = {__uint_as_float((unsigned)(266 - GEN_E0) << 23), __uint_as_float((unsigned)(266 - GEN_E0) << 23)};
   const unsigned boff = (unsigned)tid * 16u;
-  const char* Ub = reinterpret_cast<const char*>(U2);
 
   f32x16 acc[2][4];
 #pragma unroll
@@ -901,31 +796,11 @@ __global__ __launch_bounds__(WNT, 2) void wgemm_f16x2_gen2_kernel(const WgemmArg
       for (int j = 0; j < 4; ++j) ra[t][j] = *reinterpret_cast<const float4*>(q + 4 * j);
     }
   };
-  auto dmaB = [&](int s) {
-    const void* base = uniform_ptr(Ub + (long long)s * STAGE2_BYTES);
-    const unsigned l = lds0 + (s & 1) * STAGE2_BYTES;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) glds16_asm(base, boff + j * (WNT * 16), l + j * (WNT * 16));
-  };
+  auto dmaB = [&](int s) { f16x2_dma_stage<1>(Ub, S, s, lds0, boff); };
   auto stage = [&](int s, auto nx_) {
     constexpr bool NX = decltype(nx_)::value;
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      float mx = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) mx = fmaxf(fmaxf(mx, fmaxf(fabsf(ra[t][j].x), fabsf(ra[t][j].y))), fmaxf(fabsf(ra[t][j].z), fabsf(ra[t][j].w)));
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
-      const int es = min((int)(__float_as_uint(mx) >> 23), 253);
-      const bool grow = es > ecur[t] + 2;
-      if (__any(grow)) {
-        const int d = grow ? ecur[t] - es : 0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-          for (int q = 0; q < 16; ++q) acc[t][c][q] = ldexpf(acc[t][c][q], d);
-        if (grow) { ecur[t] = es; sv[t] = __uint_as_float((unsigned)(266 - es) << 23); }
-      }
-    }
+    for (int t = 0; t < 2; ++t) f16x2_row_rescale<1>(ra[t], &acc[t], ecur[t], sv[t]);
     Split2 av[2][2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
@@ -933,22 +808,7 @@ __global__ __launch_bounds__(WNT, 2) void wgemm_f16x2_gen2_kernel(const WgemmArg
       for (int kc = 0; kc < 2; ++kc) av[t][kc] = split2(ra[t][2 * kc], ra[t][2 * kc + 1], sv[t]);
     if (NX) { dmaB(s + 1); loadA(s + 1); }
     __builtin_amdgcn_sched_barrier(0);
-    const unsigned char* Bcur = smem + (s & 1) * STAGE2_BYTES + lane * 16;
-#pragma unroll
-    for (int kc = 0; kc < 2; ++kc) {
-      f16x8 b[4][2];
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) b[cb][q] = *reinterpret_cast<const f16x8*>(Bcur + ((kc * 4 + cb) * 2 + q) * FRAG);
-      constexpr int PB[3] = {1, 0, 0}, PA[3] = {0, 1, 0};
-#pragma unroll
-      for (int tm = 0; tm < 3; ++tm)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int cb = 0; cb < 4; ++cb) acc[t][cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b[cb][PB[tm]], av[t][kc].p[PA[tm]], acc[t][cb], 0, 0, 0);
-    }
+    f16x2_mfma_stage<2>(smem + (s & 1) * STAGE2_BYTES + lane * 16, av, acc);
     if (NX) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     __syncthreads();
   };
@@ -975,18 +835,10 @@ __global__ __launch_bounds__(WNT, 2) void wgemm_f16x2_gen2_kernel(const WgemmArg
 // Also: 8 waves per workgroup (512 rows, one workgroup per CU: a weight stage fetched from L2 once per 512 rows, half the L2 -> LDS traffic): 2-15 % slower on six
 // shapes (0.451 vs 0.431, 1.293 vs 1.263, 0.358 vs 0.310, 0.640 vs 0.594, 0.078 vs 0.075, 0.787 vs 0.713 ms).
 __global__ __launch_bounds__(WNT, 2) void wgemm_f16x2_rt2_kernel(const WgemmArgs a) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[(2 * STAGE2_BYTES > 4 * 32 * 68 * 4) ? 2 * STAGE2_BYTES : 4 * 32 * 68 * 4];
+  __shared__ __attribute__((aligned(16))) unsigned char smem[LDS2_BYTES];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   int lid, p;
-  if (a.pz > 0) {
-    const int orig = blockIdx.x, xcd = orig & 7, k = orig >> 3;
-    lid = k % a.gx; p = xcd + 8 * (k / a.gx);
-  } else {
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7, k = orig >> 3;
-    lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    p = blockIdx.z;
-  }
+  xcd_tile_position(a.pz, a.gx, lid, p);
   const int nb = lid % a.NB, m0 = (lid / a.NB) * (2 * WBM);
   const float* __restrict__ V = a.V + (long long)p * a.sV;
   const unsigned char* __restrict__ U2 = a.U3 + ((long long)p * a.NB + nb) * a.S * STAGE2_BYTES;
@@ -1034,12 +886,7 @@ __global__ __launch_bounds__(WNT, 2) void wgemm_f16x2_rt2_kernel(const WgemmArgs
 #pragma unroll
       for (int j = 0; j < 4; ++j) ra[t][j] = *reinterpret_cast<const float4*>(base + aoff[t] + 16 * j);
   };
-  auto dmaB = [&](int s) {
-    const void* base = uniform_ptr(Ub + (long long)s * STAGE2_BYTES);
-    const unsigned l = lds0 + (s & 1) * STAGE2_BYTES;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) glds16_asm(base, boff + j * (WNT * 16), l + j * (WNT * 16));
-  };
+  auto dmaB = [&](int s) { f16x2_dma_stage<1>(Ub, S, s, lds0, boff); };
   auto stage = [&](int s, auto nx_) {
     constexpr bool NX = decltype(nx_)::value;                  // stage s + 1 exists: request its weights and A rows
     Split2 av[2][2];
@@ -1049,22 +896,7 @@ __global__ __launch_bounds__(WNT, 2) void wgemm_f16x2_rt2_kernel(const WgemmArgs
       for (int kc = 0; kc < 2; ++kc) av[t][kc] = split2(ra[t][2 * kc], ra[t][2 * kc + 1], sv[t]);
     if (NX) { dmaB(s + 1); loadA(s + 1); }
     __builtin_amdgcn_sched_barrier(0);
-    const unsigned char* Bcur = smem + (s & 1) * STAGE2_BYTES + lane * 16;
-#pragma unroll
-    for (int kc = 0; kc < 2; ++kc) {
-      f16x8 b[4][2];
-#pragma unroll
-      for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) b[cb][q] = *reinterpret_cast<const f16x8*>(Bcur + ((kc * 4 + cb) * 2 + q) * FRAG);
-      constexpr int PB[3] = {1, 0, 0}, PA[3] = {0, 1, 0};
-#pragma unroll
-      for (int tm = 0; tm < 3; ++tm)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int cb = 0; cb < 4; ++cb) acc[t][cb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(b[cb][PB[tm]], av[t][kc].p[PA[tm]], acc[t][cb], 0, 0, 0);
-    }
+    f16x2_mfma_stage<2>(smem + (s & 1) * STAGE2_BYTES + lane * 16, av, acc);
     if (NX) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");    // the four weight DMAs have landed, the eight A loads stay in flight
     __syncthreads();
   };
@@ -1122,15 +954,27 @@ bool wgemm_general_supported(int N, int K, int C0, int ldA0, int ldA1, int ldC, 
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   return wgemm_supported(N, K) && C0 % WKS == 0 && ldA0 % 4 == 0 && ldA1 % 4 == 0 && ldC % 4 == 0 && al16(A0) && al16(A1) && al16(C) && al16(bias);
 }
+// the arguments every general launch shares; f16x2: W is an f16x2 image, the matrix's inverse power of two follows its stage images
+static WgemmArgs general_args(const float* A0, int ldA0, const float* A1, int ldA1, int C0, const void* W, bool f16x2, float* C, int ldC, long long M, int N, int K,
+                              const float* bias_n, float alpha, int accumulate) {
+  WgemmArgs a{};
+  a.V = A0; a.U3 = reinterpret_cast<const unsigned char*>(W); a.M = C;
+  a.Mt = (int)M; a.Cin = K; a.Cout = N; a.S = K / WKS; a.NB = N / WBN;
+  a.A1 = A1; a.C0 = A1 ? C0 : K; a.ldA0 = ldA0; a.ldA1 = ldA1; a.ldC = ldC; a.bias_n = bias_n; a.alpha = alpha; a.accumulate = accumulate;
+  if (f16x2) a.uinv = reinterpret_cast<const float*>(a.U3 + (size_t)N * K * 4);
+  return a;
+}
+// the GNB form of them: one-source A, no C / bias; the epilogue's operands
+static WgemmArgs gnbwd_args(const float* A, int ldA, const void* W, bool f16x2, long long M, int N, int K, float alpha, Src2 x, const float* da, const float* stats,
+                            const float* red, const float* gamma, const float* beta, int G, int silu, int HW, Dst2 d) {
+  WgemmArgs a = general_args(A, ldA, nullptr, 0, 0, W, f16x2, nullptr, N, M, N, K, nullptr, alpha, 0);
+  a.gxv = x; a.gd = d; a.gda = da; a.gstats = stats; a.gred = red; a.ggamma = gamma; a.gbeta = beta; a.gG = G; a.gsilu = silu; a.gHW = HW;
+  return a;
+}
 void launch_wgemm_bf16x3_general(const float* A0, int ldA0, const float* A1, int ldA1, int C0, const void* W3, float* C, int ldC, long long M, int N, int K,
                                  const float* bias_n, float alpha, int accumulate, hipStream_t st) {
-  WgemmArgs a{};
-  a.V = A0; a.U3 = reinterpret_cast<const unsigned char*>(W3); a.M = C;
-  a.Mt = (int)M; a.Cin = K; a.Cout = N; a.S = K / WKS; a.NB = N / WBN; a.sV = 0; a.sM = 0;
-  a.A1 = A1; a.C0 = A1 ? C0 : K; a.ldA0 = ldA0; a.ldA1 = ldA1; a.ldC = ldC; a.bias_n = bias_n; a.alpha = alpha; a.accumulate = accumulate;
-  a.pz = 0; a.gx = 0;
-  const dim3 grid((unsigned)(cdiv((int)M, WBM) * a.NB), 1, 1);
-  hipLaunchKernelGGL((wgemm_bf16x3_kernel<true>), grid, dim3(WNT), 0, st, a);
+  const WgemmArgs a = general_args(A0, ldA0, A1, ldA1, C0, W3, false, C, ldC, M, N, K, bias_n, alpha, accumulate);
+  hipLaunchKernelGGL((wgemm_bf16x3_kernel<true>), dim3((unsigned)(cdiv(a.Mt, WBM) * a.NB)), dim3(WNT), 0, st, a);
 }
 
 // out (two-destination view) = alpha * A (M x K) . W^T (N x K, pre-split) + GroupNorm backward apply of (x, da): see the GNB epilogue
@@ -1142,14 +986,8 @@ bool wgemm_gnbwd_supported(int N, int K, int ldA, const Src2& x, const Dst2& d, 
 }
 void launch_wgemm_bf16x3_gnbwd(const float* A, int ldA, const void* W3, long long M, int N, int K, float alpha, Src2 x, const float* da, const float* stats,
                                const float* red, const float* gamma, const float* beta, int G, int silu, int HW, Dst2 d, hipStream_t st) {
-  WgemmArgs a{};
-  a.V = A; a.U3 = reinterpret_cast<const unsigned char*>(W3); a.M = nullptr;
-  a.Mt = (int)M; a.Cin = K; a.Cout = N; a.S = K / WKS; a.NB = N / WBN; a.sV = 0; a.sM = 0;
-  a.A1 = nullptr; a.C0 = K; a.ldA0 = ldA; a.ldA1 = 0; a.ldC = N; a.bias_n = nullptr; a.alpha = alpha; a.accumulate = 0;
-  a.pz = 0; a.gx = 0;
-  a.gxv = x; a.gd = d; a.gda = da; a.gstats = stats; a.gred = red; a.ggamma = gamma; a.gbeta = beta; a.gG = G; a.gsilu = silu; a.gHW = HW;
-  const dim3 grid((unsigned)(cdiv((int)M, WBM) * a.NB), 1, 1);
-  hipLaunchKernelGGL((wgemm_bf16x3_kernel<true, true>), grid, dim3(WNT), 0, st, a);
+  const WgemmArgs a = gnbwd_args(A, ldA, W3, false, M, N, K, alpha, x, da, stats, red, gamma, beta, G, silu, HW, d);
+  hipLaunchKernelGGL((wgemm_bf16x3_kernel<true, true>), dim3((unsigned)(cdiv(a.Mt, WBM) * a.NB)), dim3(WNT), 0, st, a);
 }
 
 // 64-row waves where option gen_rows says so; 0 = by size: from 32768 rows on (below that the halved workgroup count leaves CUs idle: 16384 x 256 x 256
@@ -1158,33 +996,26 @@ void launch_wgemm_bf16x3_gnbwd(const float* A, int ldA, const void* W3, long lon
 // 201 us, x 256 166 -> 158 us, 65536 x 256 x 512 71 -> 65 us in isolation; 16384 x 256 x 256 17 -> 23 us)
 static bool gen_colpair(long long M, int NB) { const int c = cur_opt().gen_cp; return NB % 2 == 0 && (c == 2 || (c == 1 && M >= 32768)); }
 static bool gen_rows64(long long M) { const int r = cur_opt().gen_rows; return r == 64 || (r == 0 && M >= 32768); }
+// the tiling of an f16x2 general launch and its grid
+template <bool GNB>
+static void launch_f16x2_gen(const WgemmArgs& a, hipStream_t st) {
+  if (gen_colpair(a.Mt, a.NB)) hipLaunchKernelGGL((wgemm_f16x2_gen_kernel<2, GNB>), dim3((unsigned)(cdiv(a.Mt, WBM) * (a.NB / 2))), dim3(WNT), 0, st, a);
+  else if (gen_rows64(a.Mt)) hipLaunchKernelGGL((wgemm_f16x2_gen64_kernel<GNB>), dim3((unsigned)(cdiv(a.Mt, 2 * WBM) * a.NB)), dim3(WNT), 0, st, a);
+  else hipLaunchKernelGGL((wgemm_f16x2_gen_kernel<1, GNB>), dim3((unsigned)(cdiv(a.Mt, WBM) * a.NB)), dim3(WNT), 0, st, a);
+}
 // f16x2 forms of the two general launches: W2 = wgemm_f16x2_pack_weights(W, ., 1, N, K) (one power of two for the whole matrix)
 bool wgemm_f16x2_general_supported(int N, int K, int C0, int ldA0, int ldA1, int ldC, const void* A0, const void* A1, const void* C, const void* bias) {
   return wgemm_f16x2_supported(N, K) && wgemm_general_supported(N, K, C0, ldA0, ldA1, ldC, A0, A1, C, bias);
 }
 void launch_wgemm_f16x2_general(const float* A0, int ldA0, const float* A1, int ldA1, int C0, const void* W2, float* C, int ldC, long long M, int N, int K,
                                 const float* bias_n, float alpha, int accumulate, hipStream_t st) {
-  WgemmArgs a{};
-  a.V = A0; a.U3 = reinterpret_cast<const unsigned char*>(W2); a.M = C;
-  a.Mt = (int)M; a.Cin = K; a.Cout = N; a.S = K / WKS; a.NB = N / WBN;
-  a.A1 = A1; a.C0 = A1 ? C0 : K; a.ldA0 = ldA0; a.ldA1 = ldA1; a.ldC = ldC; a.bias_n = bias_n; a.alpha = alpha; a.accumulate = accumulate;
-  a.uinv = reinterpret_cast<const float*>(a.U3 + (size_t)N * K * 4);
-  if (gen_colpair(M, a.NB)) hipLaunchKernelGGL((wgemm_f16x2_gencp_kernel<false>), dim3((unsigned)(cdiv((int)M, WBM) * (a.NB / 2))), dim3(WNT), 0, st, a);
-  else if (gen_rows64(M)) hipLaunchKernelGGL((wgemm_f16x2_gen2_kernel<false>), dim3((unsigned)(cdiv((int)M, 2 * WBM) * a.NB)), dim3(WNT), 0, st, a);
-  else hipLaunchKernelGGL((wgemm_f16x2_gen_kernel<false>), dim3((unsigned)(cdiv((int)M, WBM) * a.NB)), dim3(WNT), 0, st, a);
+  launch_f16x2_gen<false>(general_args(A0, ldA0, A1, ldA1, C0, W2, true, C, ldC, M, N, K, bias_n, alpha, accumulate), st);
 }
 void launch_wgemm_f16x2_gnbwd(const float* A, int ldA, const void* W2, long long M, int N, int K, float alpha, Src2 x, const float* da, const float* stats,
                               const float* red, const float* gamma, const float* beta, int G, int silu, int HW, Dst2 d, hipStream_t st) {
-  WgemmArgs a{};
-  a.V = A; a.U3 = reinterpret_cast<const unsigned char*>(W2); a.M = nullptr;
-  a.Mt = (int)M; a.Cin = K; a.Cout = N; a.S = K / WKS; a.NB = N / WBN;
-  a.A1 = nullptr; a.C0 = K; a.ldA0 = ldA; a.ldA1 = 0; a.ldC = N; a.alpha = alpha;
-  a.uinv = reinterpret_cast<const float*>(a.U3 + (size_t)N * K * 4);
-  a.gxv = x; a.gd = d; a.gda = da; a.gstats = stats; a.gred = red; a.ggamma = gamma; a.gbeta = beta; a.gG = G; a.gsilu = silu; a.gHW = HW;
+  WgemmArgs a = gnbwd_args(A, ldA, W2, true, M, N, K, alpha, x, da, stats, red, gamma, beta, G, silu, HW, d);
   a.gnt = cur_opt().gnb_nt;
-  if (gen_colpair(M, a.NB)) hipLaunchKernelGGL((wgemm_f16x2_gencp_kernel<true>), dim3((unsigned)(cdiv((int)M, WBM) * (a.NB / 2))), dim3(WNT), 0, st, a);
-  else if (gen_rows64(M)) hipLaunchKernelGGL((wgemm_f16x2_gen2_kernel<true>), dim3((unsigned)(cdiv((int)M, 2 * WBM) * a.NB)), dim3(WNT), 0, st, a);
-  else hipLaunchKernelGGL((wgemm_f16x2_gen_kernel<true>), dim3((unsigned)(cdiv((int)M, WBM) * a.NB)), dim3(WNT), 0, st, a);
+  launch_f16x2_gen<true>(a, st);
 }
 
 void launch_wgemm_bf16x3(const float* V, const void* U3, float* M, long long Mt, int Cout, int Cin, int P, hipStream_t st) {

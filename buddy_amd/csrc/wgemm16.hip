@@ -87,15 +87,7 @@ __global__ __launch_bounds__(NT, 2) void wgemm_f16_kernel(const Args a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[(2 * STAGE_BYTES > 4 * 32 * 68 * 4) ? 2 * STAGE_BYTES : 4 * 32 * 68 * 4];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   int lid, p;
-  if (a.pz > 0) {
-    const int orig = blockIdx.x, xcd = orig & 7, k = orig >> 3;
-    lid = k % a.gx; p = xcd + 8 * (k / a.gx);
-  } else {
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7, k = orig >> 3;
-    lid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-    p = blockIdx.z;
-  }
+  xcd_tile_position(a.pz, a.gx, lid, p);
   const int nb = lid % a.NB, m0 = (lid / a.NB) * (2 * BM);
   const char* Vb = reinterpret_cast<const char*>(a.V + (long long)p * a.sV);
   const char* Ub = reinterpret_cast<const char*>(a.U1 + ((long long)p * a.NB + nb) * a.S * STAGE_BYTES);

@@ -169,11 +169,11 @@ def test_gemm_bf16x3_general_form(lib, M, N, K, C0, arith):
 
 @pytest.mark.parametrize("M,N,K", [(40000, 128, 256), (40000, 256, 512), (333, 256, 128)])
 def test_gemm_f16x2_running_row_scale(lib, M, N, K):
-    """The f16x2 general form finds a row's power of two ON THE WAY (wgemm_f16x2_gen_kernel: a K-stage whose abs-max leaves the current scale's range
+    """The f16x2 general form finds a row's power of two ON THE WAY (f16x2_row_rescale of wgemm_f16x2_gen_kernel<CB> / wgemm_f16x2_gen64_kernel: a K-stage whose abs-max leaves the current scale's range
     rescales the row's accumulators by an exact power of two).  Rows whose magnitude climbs twelve decades along K (a rescale at almost every stage), rows
     that fall as far (the first stage fixes the scale), zero rows, one huge element in the last stage, and a zero first half: every row within 2e-5 of its
-    own bound sum_k |a_k| |w_k| -- what a per-row scale known in advance would give.  The three shapes run the three kernel forms (64-row waves, two column
-    blocks per workgroup, 32-row waves: M and N select them, wgemm.hip gen_rows64 / gen_colpair)."""
+    own bound sum_k |a_k| |w_k| -- what a per-row scale known in advance would give.  The three shapes run the three tilings (wgemm_f16x2_gen64_kernel,
+    wgemm_f16x2_gen_kernel<2>, wgemm_f16x2_gen_kernel<1>: M and N select them, wgemm.hip gen_rows64 / gen_colpair)."""
     from buddy_amd import _lib
     g = torch.Generator(device="cpu").manual_seed(7 * M + N + K)
     A = torch.randn(M, K, generator=g)
@@ -198,12 +198,15 @@ def test_gemm_f16x2_running_row_scale(lib, M, N, K):
 
 
 @pytest.mark.parametrize("arith", ["bf16x3", "f16x2"])
-@pytest.mark.parametrize("B,HW,N,K,C0,silu,acc", [(2, 300, 128, 128, 0, 1, 0), (1, 1000, 384, 128, 256, 1, 1), (3, 77, 256, 64, 128, 0, 1), (1, 4096, 512, 256, 256, 1, 0)])
+@pytest.mark.parametrize("B,HW,N,K,C0,silu,acc", [(2, 300, 128, 128, 0, 1, 0), (1, 1000, 384, 128, 256, 1, 1), (3, 77, 256, 64, 128, 0, 1), (1, 4096, 512, 256, 256, 1, 0),
+                                                   (1, 32845, 128, 64, 0, 1, 0), (3, 10949, 256, 128, 128, 1, 1)])
 def test_gemm_bf16x3_gn_bwd(lib, B, HW, N, K, C0, silu, acc, arith):
     """buddy_gemm_bf16x3_gn_bwd: the skip path's 1x1 data-gradient GEMM with the GroupNorm_0 backward's apply pass as its epilogue (a ResBlock's input
     gradient, reference layerspp.py:242-274 backward) against fp64 autograd: dx = alpha * A W^T + d/dx [act(GroupNorm(x))] . da, two-source x,
     two-destination dx (the second accumulating), ragged M.  2e-5 for the GEMM term like the general form, 2e-4 of the abs-max overall (the
-    normalisation backward's cancellation, as test_gnbwd_conv3x3_winograd6)."""
+    normalisation backward's cancellation, as test_gnbwd_conv3x3_winograd6).  The last two rows reach the f16x2 forms that start at 32768 rows: M = 32768 + 77
+    (ragged in the last 256-row workgroup) with one column block -> wgemm_f16x2_gen64_kernel<true>; M = 3 x 10949 (utterance seams inside a wave's rows) with
+    two -> wgemm_f16x2_gen_kernel<2, true>, the x / dx split at the column-block boundary and the second destination accumulating."""
     from buddy_amd import _lib
     G = min(N // 4, 32)
     g = torch.Generator(device="cpu").manual_seed(B * 100 + HW + N + K)
