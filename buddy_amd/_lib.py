@@ -42,6 +42,9 @@ _SIGS = {
     "buddy_optim_sqnorm": (C.c_int, [_f32p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
     "buddy_optim_step": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, C.c_longlong, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double,
                                    C.c_double, C.c_double, C.c_double, C.POINTER(C.c_longlong), C.c_int, C.c_void_p]),
+    "buddy_optim_step_scaled": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, C.c_longlong, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                                          C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_longlong), C.c_int, C.c_void_p]),
+    "buddy_optim_checksum": (C.c_int, [_f32p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
     "buddy_optim_ema": (C.c_int, [_f32p, _f32p, C.c_longlong, C.c_double, C.c_void_p]),
     "buddy_weight_grad_workspace": (C.c_longlong, [C.c_longlong, C.c_int, C.c_int]),
     "buddy_weight_grad_chunks": (C.c_int, [C.c_longlong, C.c_int, C.c_int]),

@@ -54,11 +54,53 @@ __global__ __launch_bounds__(SQ_THREADS) void optim_sqnorm_final_kernel(const do
   if (threadIdx.x == 0) out[0] = s;
 }
 
+// ---- the replica checksum: sum_i bits(x[i]) * (2 i + 1) mod 2^64, the same streaming form as the squared norm (plain loads: the buffers it
+// reads -- p, m, v, ema -- are read again by the next step)
+typedef unsigned int u32x4o __attribute__((ext_vector_type(4)));
+typedef unsigned long long u64;
+
+// the 256 per-thread sums of a workgroup; integer addition mod 2^64 is associative, so the order does not matter
+__device__ __forceinline__ u64 block_sum_256_u64(u64 s, u64* lds) {
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) lds[wave] = s;
+  __syncthreads();
+  return lds[0] + lds[1] + lds[2] + lds[3];
+}
+
+__global__ __launch_bounds__(SQ_THREADS) void optim_checksum_part_kernel(const unsigned int* __restrict__ x, long long n, int aligned, u64* __restrict__ partials) {
+  __shared__ u64 lds[4];
+  const long long base = (long long)blockIdx.x * SQ_CHUNK;
+  u64 s = 0;
+#pragma unroll 4
+  for (int u = 0; u < SQ_WORDS; ++u) {
+    const long long i = base + ((long long)u * SQ_THREADS + threadIdx.x) * 4;
+    const u64 k = 2ull * (u64)i + 1ull;
+    if (aligned && i + 4 <= n) {
+      const u32x4o w = *reinterpret_cast<const u32x4o*>(x + i);
+      s += (u64)w.x * k; s += (u64)w.y * (k + 2); s += (u64)w.z * (k + 4); s += (u64)w.w * (k + 6);
+    } else {
+      for (int j = 0; j < 4; ++j)
+        if (i + j < n) s += (u64)x[i + j] * (k + 2ull * j);
+    }
+  }
+  s = block_sum_256_u64(s, lds);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(SQ_THREADS) void optim_checksum_final_kernel(const u64* __restrict__ partials, long long chunks, u64* __restrict__ out) {
+  __shared__ u64 lds[4];
+  u64 s = 0;
+  for (long long c = threadIdx.x; c < chunks; c += SQ_THREADS) s += partials[c];
+  s = block_sum_256_u64(s, lds);
+  if (threadIdx.x == 0) out[0] = s;
+}
+
 struct Frozen { long long lo[MAX_FROZEN], hi[MAX_FROZEN]; int n; };
 
 struct StepArgs {
   float* p; const float* g; float* m; float* v; float* ema; long long n;
-  const double* sqnorm; double max_norm, beta1, beta2, eps, step_size, bias2_sqrt, ema_s;
+  const double* sqnorm; double max_norm, beta1, beta2, eps, step_size, bias2_sqrt, ema_s, grad_scale;
 };
 
 __device__ __forceinline__ bool is_frozen(const Frozen& fz, long long i) {
@@ -82,8 +124,11 @@ __device__ __forceinline__ void step_one(const StepArgs& a, double coef, bool fr
 __global__ __launch_bounds__(256) void optim_step_kernel(StepArgs a, Frozen fz) {
   const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i >= a.n) return;
+  // grad_scale: g holds a sum over ranks and the step uses its average; the clip acts on the norm of the average.  grad_scale = 1 multiplies
+  // by one twice, which is exact: the bits of the unscaled step
   double coef = 1.0;
-  if (a.max_norm > 0.0) coef = fmin(1.0, a.max_norm / (sqrt(a.sqnorm[0]) + 1e-6));
+  if (a.max_norm > 0.0) coef = fmin(1.0, a.max_norm / (a.grad_scale * sqrt(a.sqnorm[0]) + 1e-6));
+  coef *= a.grad_scale;
   if (i + 4 <= a.n) {
     const f32x4o pw = *reinterpret_cast<const f32x4o*>(a.p + i);
     const f32x4o gw = __builtin_nontemporal_load(reinterpret_cast<const f32x4o*>(a.g + i));
@@ -158,9 +203,27 @@ int buddy_optim_sqnorm(const float* g, long long n, double* partials, double* ou
   return launched();
 }
 
+int buddy_optim_checksum(const float* x, long long n, unsigned long long* partials, unsigned long long* out, void* stream) {
+  if (!x || !partials || !out || n < 1) { set_error("optim_checksum: null argument or n < 1"); return BUDDY_ERR_ARG; }
+  if (((uintptr_t)x & 3) || ((uintptr_t)partials & 7) || ((uintptr_t)out & 7)) { set_error("optim_checksum: misaligned buffer"); return BUDDY_ERR_ARG; }
+  const long long chunks = (n + SQ_CHUNK - 1) / SQ_CHUNK;
+  if (chunks > 0x7fffffffLL) { set_error("optim_checksum: n too large"); return BUDDY_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  optim_checksum_part_kernel<<<dim3((unsigned)chunks), dim3(SQ_THREADS), 0, st>>>(reinterpret_cast<const unsigned int*>(x), n, misaligned(x) ? 0 : 1, partials);
+  optim_checksum_final_kernel<<<dim3(1), dim3(SQ_THREADS), 0, st>>>(partials, chunks, out);
+  return launched();
+}
+
 int buddy_optim_step(float* p, const float* g, float* m, float* v, float* ema, long long n, const double* sqnorm, double max_norm, double beta1,
                      double beta2, double eps, double step_size, double bias2_sqrt, double ema_s, const long long* frozen, int n_frozen,
                      void* stream) {
+  return buddy_optim_step_scaled(p, g, m, v, ema, n, sqnorm, max_norm, beta1, beta2, eps, step_size, bias2_sqrt, ema_s, 1.0, frozen, n_frozen, stream);
+}
+
+int buddy_optim_step_scaled(float* p, const float* g, float* m, float* v, float* ema, long long n, const double* sqnorm, double max_norm,
+                            double beta1, double beta2, double eps, double step_size, double bias2_sqrt, double ema_s, double grad_scale,
+                            const long long* frozen, int n_frozen, void* stream) {
+  if (!(std::isfinite(grad_scale) && grad_scale > 0.0)) { set_error("optim_step: grad_scale must be finite and > 0"); return BUDDY_ERR_ARG; }
   if (!p || !g || !m || !v || n < 1) { set_error("optim_step: null argument or n < 1"); return BUDDY_ERR_ARG; }
   if (misaligned(p) || misaligned(g) || misaligned(m) || misaligned(v) || misaligned(ema)) { set_error("optim_step: buffers must be 16-byte aligned"); return BUDDY_ERR_ARG; }
   if (max_norm > 0.0 && (!sqnorm || ((uintptr_t)sqnorm & 7))) { set_error("optim_step: max_norm > 0 needs the device double of buddy_optim_sqnorm"); return BUDDY_ERR_ARG; }
@@ -175,7 +238,7 @@ int buddy_optim_step(float* p, const float* g, float* m, float* v, float* ema, l
   }
   const long long words = (n + 3) / 4, blocks = (words + 255) / 256;
   if (blocks > 0x7fffffffLL) { set_error("optim_step: n too large"); return BUDDY_ERR_ARG; }
-  StepArgs a{p, g, m, v, ema, n, max_norm > 0.0 ? sqnorm : nullptr, max_norm, beta1, beta2, eps, step_size, bias2_sqrt, ema_s};
+  StepArgs a{p, g, m, v, ema, n, max_norm > 0.0 ? sqnorm : nullptr, max_norm, beta1, beta2, eps, step_size, bias2_sqrt, ema_s, grad_scale};
   optim_step_kernel<<<dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream>>>(a, fz);
   return launched();
 }

@@ -1,6 +1,9 @@
 """Utterance-batch data parallelism: one process per GPU, utterance u -> rank u mod world, no communication inside the
 sampling loop, ONE all_gather of the outputs at the end (RCCL over xGMI on the GPU box; gloo in the CPU tests).
-New capability -- the reference is single-process."""
+New capability -- the reference is single-process.
+
+Data-parallel training (``training/fused.py``, ``training/trainer.py``) uses the same placement helpers, plus what is below the sampler's
+gathers: the per-rank seed rule (``rank_seed``), the plan of a self-launched job (``launch_plan``) and the launcher itself (``launch``)."""
 from __future__ import annotations
 
 import os
@@ -159,11 +162,22 @@ def shard_indices(n_items, rank, world):
     return [i for i in range(n_items) if i % world == rank]
 
 
+def _unsharded(world):
+    """a caller with ``world`` = 1 has every item itself: no group, or -- the Tester of rank 0 inside a data-parallel training job -- a group of
+    more ranks that the other ranks would not enter.  A one-rank group still runs the collective."""
+    if world != 1:
+        return False
+    if not _group_up():
+        return True
+    import torch.distributed as dist
+    return dist.get_world_size() > 1
+
+
 def gather_rows(local, n_items, rank, world):
     """local: (n_local, L) rows of the utterances in ``shard_indices(n_items, rank, world)`` order.
     Returns the (n_items, L) tensor in utterance order on every rank (one all_gather; ragged shards are padded).  With one rank and no
-    process group this is the identity; with a process group the collective runs whatever the world size."""
-    if world == 1 and not _group_up():
+    process group this is the identity; with a process group of ``world`` ranks the collective runs whatever the world size."""
+    if _unsharded(world):
         return local
     import torch.distributed as dist
     per = (n_items + world - 1) // world
@@ -182,7 +196,7 @@ def gather_ragged(rows, n_items, rank, world, device=None):
     """End-of-run gather for the harness: ``rows`` = this rank's 1-D results (utterances ``shard_indices(n_items, rank, world)``, in that
     order, any lengths) -> list of all ``n_items`` rows in utterance order on every rank.  Two collectives in total (lengths, then the
     rows zero-padded to the longest): RCCL over xGMI on the GPU box, gloo in the CPU tests."""
-    if world == 1 and not _group_up():
+    if _unsharded(world):
         return list(rows)
     import torch.distributed as dist
     dev = device if (device is not None and dist.get_backend() == "nccl") else torch.device("cpu")
@@ -194,3 +208,79 @@ def gather_ragged(rows, n_items, rank, world, device=None):
         local[i, : r.shape[-1]] = r.to(dev)
     full = gather_rows(local, n_items, rank, world)
     return [full[i, : int(all_lens[i])] for i in range(n_items)]
+
+
+# ---- data-parallel training: seeds and the self-launcher ----------------------------------------------------------------------------------------
+MAX_RANKS = 16                  # ranks of one job on one node (processes with the GPU open)
+RANK_SEED_STRIDE = 1 << 20      # distance between the seeds of two ranks: far above any DataLoader worker count, so (rank, worker) never collide
+
+
+def rank_seed(seed, rank, worker_id=0):
+    """The seed of rank ``rank``'s random streams (torch's generator for sigma and noise, the dataset's ``random`` / ``numpy.random``), and of
+    its loader worker ``worker_id``, which keeps adding its id.  Rank 0 has the seeds of the single-process run at any world size."""
+    if not 0 <= worker_id < RANK_SEED_STRIDE:
+        raise ValueError(f"worker id {worker_id} outside [0, {RANK_SEED_STRIDE})")
+    return int(seed) + RANK_SEED_STRIDE * int(rank) + int(worker_id)
+
+
+def too_few_devices_message(prog, world, devices):
+    return f"{prog}: {world} RCCL ranks need {world} GPUs, this node shows {devices} (--backend gloo lets ranks share a GPU for smoke tests)"
+
+
+def launch_plan(n, backend="nccl", port=29500, device_count=None, prog="train.py"):
+    """What ``launch`` starts for an ``n``-rank job on this node, as plain data: per rank the environment it adds (the torchrun variables, the
+    rendezvous, dmabuf IPC), the torch device index it will pick (``device_index``) and the physical device behind it under
+    HIP_VISIBLE_DEVICES / ROCR_VISIBLE_DEVICES.  ``device_count``: the number of visible devices where the caller knows it; otherwise the
+    length of the visible-device list when one is set, else unknown (device None: the rank finds out -- the launcher never opens the GPU).
+    Refuses n > MAX_RANKS, and ``nccl`` with more ranks than (known) devices; ``gloo`` lets ranks share a device, for smoke tests."""
+    if backend not in ("nccl", "gloo"):
+        raise ValueError(f"{prog}: backend {backend!r} (nccl or gloo)")
+    if not 1 <= n <= MAX_RANKS:
+        raise ValueError(f"{prog}: {n} ranks asked for, one node runs 1 to {MAX_RANKS}")
+    vis = visible_device_ids()
+    if device_count is None and vis is not None:
+        device_count = len(vis)
+    if backend == "nccl" and device_count is not None and n > device_count:
+        raise ValueError(too_few_devices_message(prog, n, device_count))
+    plan = []
+    for r in range(n):
+        dev = device_index(r, device_count) if device_count else None
+        phys = None if dev is None else (vis[dev] if (vis is not None and dev < len(vis)) else (dev if vis is None else None))
+        env = {"RANK": str(r), "LOCAL_RANK": str(r), "WORLD_SIZE": str(n), "LOCAL_WORLD_SIZE": str(n), "MASTER_ADDR": "127.0.0.1",
+               "MASTER_PORT": str(port), "HSA_ENABLE_IPC_MODE_LEGACY": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")}
+        plan.append({"rank": r, "env": env, "device": dev, "physical_device": phys})
+    return plan
+
+
+def launch(script, argv, n, backend="nccl"):
+    """Start ``n`` fresh rank processes ``python script *argv`` under ``launch_plan`` and wait for them; returns the first non-zero exit status
+    (the remaining ranks are then terminated: they would wait in a collective for ever), else 0.  The calling process neither opens the GPU
+    nor replaces its own program."""
+    import socket
+    import subprocess
+    import sys
+    import time
+    with socket.socket() as so:
+        so.bind(("127.0.0.1", 0))
+        port = so.getsockname()[1]
+    procs = [subprocess.Popen([sys.executable, script] + list(argv), env=dict(os.environ, **item["env"]))
+             for item in launch_plan(n, backend, port, prog=os.path.basename(script))]
+    status, left = 0, list(procs)
+    try:
+        while left and status == 0:
+            time.sleep(0.2)
+            for p in list(left):
+                rc = p.poll()
+                if rc is not None:
+                    left.remove(p)
+                    if rc != 0 and status == 0:
+                        status = rc
+    finally:
+        for p in left:
+            p.terminate()
+        for p in left:
+            try:
+                p.wait(30)
+            except subprocess.TimeoutExpired:
+                p.kill()
+    return status

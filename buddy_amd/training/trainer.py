@@ -12,7 +12,17 @@ EMA-only launch.
 Logging: wandb, the torch profiler and the plots are not part of this package.  With ``args.logging.log`` the mean loss and the
 per-sigma-bin errors (``process_loss_for_logging``) are appended as JSON lines to ``<model_dir>/train_log.jsonl`` every ``log_interval``
 iterations.  The yaml keys ``lr_rampup_it``, ``scheduler_step_size`` and ``scheduler_gamma`` of the reference are read by nothing there and
-by nothing here: the learning rate is constant."""
+by nothing here: the learning rate is constant.
+
+Data parallelism: when ``torch.distributed`` is initialised (more than one rank, or a one-rank group forced for tests) the Trainer is one of W
+replicas.  ``exp.batch_size`` stays the GLOBAL batch and every rank's loader yields ``batch_size // W`` utterances; the gradients are summed by
+one all-reduce on the flat buffer and averaged inside the fused optimizer pass (``FusedAdam.attach_group``), so the step is the single-process
+step on the global batch up to the rounding of that sum.  The replicas are made equal by a broadcast from rank 0 after construction and after
+every resume, and are proved equal (``FusedAdam.check_replicas``: checksums of the weights, both moments and the EMA) then, before every
+checkpoint, after every heavy log and every ``exp.replica_check_interval`` iterations (default: ``logging.log_interval``; 0: never).  Rank r
+seeds its streams with ``dist.rank_seed(exp.seed, r)``; rank 0 writes the checkpoints (same keys, same name: a checkpoint of one world size
+resumes at any other) and the logs, the latter from the per-utterance errors of the global batch.  Without a process group nothing of this
+runs: same launches, same bits as before."""
 from __future__ import annotations
 
 import copy
@@ -24,6 +34,7 @@ from glob import glob
 import numpy as np
 import torch
 
+from .. import dist as bdist
 from ..utils import training_utils as t_utils
 from .fused import FusedAdam
 
@@ -66,10 +77,17 @@ class Trainer:
             # NCSNppTime registers its parameters frozen (the sampler's default); the reference's are trainable except the Fourier W
             for (name, _, kind, _), p in zip(network._specs, network._params()):
                 p.requires_grad_(kind != "fourier")
+        self.world, self.rank, self._dp, self._constructed = 1, 0, False, False
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            self.world, self.rank, self._dp = torch.distributed.get_world_size(), torch.distributed.get_rank(), True
+            if int(args.exp.batch_size) % self.world != 0:
+                raise ValueError(f"exp.batch_size = {int(args.exp.batch_size)} is the global batch and must be a multiple of the {self.world} ranks")
         self.optimizer = make_optimizer(args.exp.optimizer, network)
         self.ema = copy.deepcopy(self.network).eval().requires_grad_(False)
         self.optimizer.attach_ema(self.ema)
-        torch.manual_seed(self.args.exp.seed)
+        if self._dp:
+            self.optimizer.attach_group(None, self.world, self.rank)
+        torch.manual_seed(bdist.rank_seed(self.args.exp.seed, self.rank))
         self.total_params = sum(p.numel() for p in self.network.parameters() if p.requires_grad)
         print("total_params: ", self.total_params / 1e6, "M")
         self._ema_done_it = None        # the iteration whose EMA train_step has already applied
@@ -93,8 +111,25 @@ class Trainer:
             self.latest_checkpoint = None
             if tester is not None:
                 self.tester.it = 0
+        if self._dp:
+            self.sync_replicas()
+        self._constructed = True
         if self.args.logging.log:
             self.setup_logging_variables()
+
+    # ---- data parallelism ---------------------------------------------------------------------------------------------------------
+    def sync_replicas(self):
+        """Every rank continues from rank 0's state -- weights, moments, EMA, step counters, iteration -- whatever each of them loaded, and
+        the replicas are checked to be equal"""
+        self.optimizer.broadcast_state(0)
+        self.it = self.optimizer.broadcast_int(self.it, 0)
+        if self.tester is not None:
+            self.tester.it = self.it
+        self.optimizer.check_replicas()
+
+    def _replica_check_interval(self):
+        v = self.args.exp.get("replica_check_interval", None)
+        return int(self.args.logging.log_interval if v in (None, "None") else v)
 
     def setup_logging_variables(self):
         hp = self.args.diff_params.sde_hp
@@ -105,7 +140,15 @@ class Trainer:
         return t_utils.load_state_dict(state_dict, network=self.network, ema=self.ema, optimizer=self.optimizer)
 
     def resume_from_checkpoint(self, checkpoint_path=None, checkpoint_id=None):
-        """reference :110-169: an explicit path (as given, then under model_dir), else the newest ``<exp_name>-<it>.pt`` of model_dir"""
+        """reference :110-169: an explicit path (as given, then under model_dir), else the newest ``<exp_name>-<it>.pt`` of model_dir.
+        Data-parallel: every rank loads the file itself where it can see it, then all take rank 0's state (the construction does so itself;
+        a call made later is followed by ``sync_replicas()`` here)."""
+        ok = self._resume_from_checkpoint(checkpoint_path, checkpoint_id)
+        if self._dp and self._constructed:
+            self.sync_replicas()
+        return ok
+
+    def _resume_from_checkpoint(self, checkpoint_path=None, checkpoint_id=None):
         if checkpoint_path is not None:
             for path in (checkpoint_path, os.path.join(self.args.model_dir, checkpoint_path)):
                 try:
@@ -137,8 +180,21 @@ class Trainer:
                 "args": self.args}
 
     def save_checkpoint(self):
-        os.makedirs(self.args.model_dir, exist_ok=True)
+        """Data-parallel: the replicas are checked, rank 0 writes the one file, and every rank waits until it is there"""
         save_name = f"{self.args.model_dir}/{self.args.exp.exp_name}-{self.it}.pt"
+        if self._dp:
+            self.optimizer.check_replicas()
+            try:
+                if self.rank == 0:
+                    self._write_checkpoint(save_name)
+            finally:
+                torch.distributed.barrier()
+            self.latest_checkpoint = save_name
+            return
+        self._write_checkpoint(save_name)
+
+    def _write_checkpoint(self, save_name):
+        os.makedirs(self.args.model_dir, exist_ok=True)
         torch.save(self.state_dict(), save_name)
         print("saving", save_name)
         if self.args.logging.get("remove_old_checkpoints", False) and self.latest_checkpoint is not None:
@@ -152,6 +208,14 @@ class Trainer:
     # ---- logging ------------------------------------------------------------------------------------------------------------------
     def process_loss_for_logging(self, error, sigma):
         """mean loss and, per logarithmic sigma bin, the mean error of the first batch row that falls into it (reference :194-218)"""
+        if self._dp:
+            # the global batch: per-utterance mean errors and sigmas of every rank, in rank order (equal shares: the mean of the row means is
+            # the global mean); every rank enters the gather, rank 0 keeps the row
+            error, sigma = self.optimizer.gather_floats(torch.stack([error.detach().mean(dim=tuple(range(1, error.dim()))).float(),
+                                                                     sigma.detach().reshape(-1).float()]))
+            error = error[:, None]
+            if self.rank != 0:
+                return
         error = error.detach().cpu().numpy()
         sigma = sigma.detach().cpu().reshape(-1).numpy()
         row = {"it": int(self.it), "loss": float(error.mean())}
@@ -175,15 +239,25 @@ class Trainer:
     def heavy_logging(self):
         """``tester.do_test`` on the latest checkpoint.  As in the reference, ``train.py`` gives Tester and Trainer the SAME network object, and
         ``Tester.load_checkpoint`` loads the EMA weights into it: every heavy log replaces the training weights by the EMA of the last saved
-        checkpoint (in place, through the flat buffer; the handle is rebuilt).  Give the Tester a deep copy to keep the two apart."""
-        if self.tester is not None:
+        checkpoint (in place, through the flat buffer; the handle is rebuilt).  Give the Tester a deep copy to keep the two apart.
+        Data-parallel: the Tester runs on rank 0 only; afterwards every rank takes rank 0's weights, so all continue from the same ones --
+        the EMA of the last checkpoint, as the single-process run does -- and the replicas are checked."""
+        out = None
+        if self.tester is not None and self.rank == 0:
             if self.latest_checkpoint is not None:
                 self.tester.load_checkpoint(self.latest_checkpoint)
-            return self.tester.do_test(it=self.it)
+            out = self.tester.do_test(it=self.it)
+        if self._dp:
+            self.optimizer.broadcast_state(0, weights_only=True)
+            self.optimizer.check_replicas()
+        return out
 
     # ---- the step -----------------------------------------------------------------------------------------------------------------
     def get_batch(self):
         sample = next(self.dset)
+        if self._dp and len(sample) != int(self.args.exp.batch_size) // self.world:
+            raise ValueError(f"rank {self.rank}: the loader gave {len(sample)} utterances; exp.batch_size = {int(self.args.exp.batch_size)} is the "
+                             f"global batch, each of the {self.world} ranks takes {int(self.args.exp.batch_size) // self.world}")
         return torch.as_tensor(sample).to(self.device).float()
 
     def _ema_s(self):
@@ -215,6 +289,7 @@ class Trainer:
 
     def training_loop(self):
         lg = self.args.logging
+        rci = self._replica_check_interval() if self._dp else 0
         while True:
             self.train_step()
             self.update_ema()
@@ -224,6 +299,8 @@ class Trainer:
                 self.heavy_logging()
             if self.it > 0 and self.it % lg.log_interval == 0 and lg.log:
                 self.easy_logging()
+            if self._dp and rci > 0 and self.it > 0 and self.it % rci == 0:
+                self.optimizer.check_replicas()
             self.it += 1
             if "max_iters" in self.args.exp.keys() and self.args.exp.max_iters is not None and self.it > self.args.exp.max_iters:
                 break

@@ -105,6 +105,19 @@ int buddy_optim_sqnorm(const float* g, long long n, double* partials, double* ou
 int buddy_optim_step(float* p, const float* g, float* m, float* v, float* ema, long long n, const double* sqnorm, double max_norm, double beta1,
                      double beta2, double eps, double step_size, double bias2_sqrt, double ema_s, const long long* frozen, int n_frozen,
                      void* stream);
+/* buddy_optim_step for data-parallel training: g holds the SUM of the ranks' gradients and grad_scale = 1 / world makes the step use their
+ * average without another pass over the buffer: gc = coef * grad_scale * g with coef = min(1, max_norm / (grad_scale * sqrt(*sqnorm) + 1e-6)),
+ * i.e. clip_grad_norm_ on the averaged gradient; *sqnorm is still the squared norm of the buffer as it is (of the sum), and g is not written.
+ * grad_scale must be finite and > 0 (else BUDDY_ERR_ARG).  buddy_optim_step is this entry with grad_scale = 1, which is exact. */
+int buddy_optim_step_scaled(float* p, const float* g, float* m, float* v, float* ema, long long n, const double* sqnorm, double max_norm,
+                            double beta1, double beta2, double eps, double step_size, double bias2_sqrt, double ema_s, double grad_scale,
+                            const long long* frozen, int n_frozen, void* stream);
+/* Checksum of n floats by their bit patterns, for comparing the replicas of data-parallel training:
+ *   out[0] = sum_i bits(x[i]) * (2 i + 1) mod 2^64   (bits = the 32-bit pattern, zero-extended; i = the element's index).
+ * An integer sum, so independent of the reduction order; every multiplier is odd, hence invertible mod 2^64, so a change of one element
+ * changes the result, and it depends on the position, so does a swap of two differing elements.  Same form as buddy_optim_sqnorm: x needs
+ * 4-byte alignment only, partials is ceil(n / buddy_optim_sqnorm_chunk()) 64-bit words of workspace, no atomics, the result stays on the device. */
+int buddy_optim_checksum(const float* x, long long n, unsigned long long* partials, unsigned long long* out, void* stream);
 /* the EMA on its own (Trainer.update_ema outside a fused step): ema = ema * ema_s + p * (1 - ema_s), n floats, 16-byte aligned */
 int buddy_optim_ema(float* ema, const float* p, long long n, double ema_s, void* stream);
 
