@@ -21,7 +21,7 @@ struct Options {
   int attn;            // attention core 0 .. 4 (net.hip)
   int gn_fuse, upconv, c2_fuse;                        // fusions of the network graph (default 1)
   int attn_split, attn_nw;                             // fp32 attention: forced loop-split count / forward tile height (0 = by shape)
-  int wgemm_rt, gen_f16x2, gen_rows, gen_cp, gnb_nt;   // kernel forms of the GEMMs
+  int wgemm_rt, wgemm_cb, gen_f16x2, gen_rows, gen_cp, gnb_nt;   // kernel forms of the GEMMs
   int c2out_tiled;                                     // kernel form of the Cin -> 2 convolutions
   int op_graph;                                        // blind operator: 0 = launch the optimisation loop eagerly instead of as a captured graph
 };

@@ -42,6 +42,7 @@ const Entry kTable[] = {
     {"attn_split", "BUDDY_ATTN_SPLIT", &Options::attn_split, 0, 4096, 0, nullptr},
     {"attn_nw", "BUDDY_ATTN_NW", &Options::attn_nw, 0, 8, 0, nullptr},
     {"wgemm_rt", "BUDDY_WGEMM_RT", &Options::wgemm_rt, 0, 2, 0, nullptr},
+    {"wgemm_cb", "BUDDY_WGEMM_CB", &Options::wgemm_cb, 0, 2, 0, nullptr},
     {"gen_f16x2", "BUDDY_GEN_F16X2", &Options::gen_f16x2, 0, 2, 1, nullptr},
     {"gen_rows", "BUDDY_GEN_ROWS", &Options::gen_rows, 0, 64, 0, nullptr},
     {"gen_cp", "BUDDY_GEN_CP", &Options::gen_cp, 0, 2, 1, nullptr},

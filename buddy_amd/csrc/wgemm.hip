@@ -429,12 +429,10 @@ __device__ __forceinline__ void f16x2_mfma_stage(const unsigned char* Bcur, cons
   }
 }
 
-__global__ __launch_bounds__(WNT, 3) void wgemm_f16x2_kernel(const WgemmArgs a) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[LDS2_BYTES];
+// The 32-row batched kernel's work on CB adjacent column blocks nb ... nb + CB - 1 of row block m0 of position p (see wgemm_f16x2_kernel below).
+template <int CB>
+__device__ __forceinline__ void f16x2_batched_tile(const WgemmArgs& a, unsigned char* smem, const int p, const int nb, const int m0) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  int lid, p;
-  xcd_tile_position(a.pz, a.gx, lid, p);
-  const int nb = lid % a.NB, m0 = (lid / a.NB) * WBM;
   const float* __restrict__ V = a.V + (long long)p * a.sV;
   const unsigned char* __restrict__ U2 = a.U3 + ((long long)p * a.NB + nb) * a.S * STAGE2_BYTES;
   const int S = a.S;
@@ -461,11 +459,13 @@ __global__ __launch_bounds__(WNT, 3) void wgemm_f16x2_kernel(const WgemmArgs a) 
   const char* Vb = reinterpret_cast<const char*>(V);
   const char* Ub = reinterpret_cast<const char*>(U2);
 
-  f32x16 acc[4];
+  f32x16 acc[CB][4];
 #pragma unroll
-  for (int c = 0; c < 4; ++c)
+  for (int t = 0; t < CB; ++t)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[c][r] = 0.f;
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[t][c][r] = 0.f;
 
   // Two K-stages of A in flight (the stage is half as long as bf16x3's: one stage of prefetch no longer covers the HBM latency), the loop unrolled by two
   // so that each register set keeps its name.  The weights' stage image goes global -> LDS by LDS-DMA written as inline asm (no staging registers, no
@@ -478,7 +478,7 @@ __global__ __launch_bounds__(WNT, 3) void wgemm_f16x2_kernel(const WgemmArgs a) 
 #pragma unroll
     for (int j = 0; j < 4; ++j) r[j] = *reinterpret_cast<const float4*>(base + aoff + 16 * j);
   };
-  auto dmaB = [&](int s) { f16x2_dma_stage<1>(Ub, S, s, lds0, boff); };
+  auto dmaB = [&](int s) { f16x2_dma_stage<CB>(Ub, S, s, lds0, boff); };
   // NB / NA (compile time): this stage requests the weights of stage s + 1 / the A rows of stage s + 2 (the last two stages are peeled: behind a run-time `if`
   // the wait-count pass must assume the loads were skipped and waits for everything in flight).
   auto stage = [&](int s, float4 (&r)[4], auto nb_, auto na_) {
@@ -489,7 +489,8 @@ __global__ __launch_bounds__(WNT, 3) void wgemm_f16x2_kernel(const WgemmArgs a) 
     if (NB) dmaB(s + 1);
     if (NA) loadA(s + 2, r);
     __builtin_amdgcn_sched_barrier(0);
-    f16x2_mfma_stage<1>(smem + (s & 1) * STAGE2_BYTES + lane * 16, av, &acc);
+#pragma unroll
+    for (int t = 0; t < CB; ++t) f16x2_mfma_stage<1>(smem + ((s & 1) * CB + t) * STAGE2_BYTES + lane * 16, av, &acc[t]);
     if (NB) { if (NA) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
     __syncthreads();
   };
@@ -507,32 +508,59 @@ __global__ __launch_bounds__(WNT, 3) void wgemm_f16x2_kernel(const WgemmArgs a) 
   stage(s, ra[0], std::true_type{}, std::false_type{});
   stage(s + 1, ra[1], std::false_type{}, std::false_type{});
 #pragma unroll
-  for (int c = 0; c < 4; ++c)
+  for (int t = 0; t < CB; ++t)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc[c][r] *= inv;               // the accumulator is C^T: a lane holds ONE row, so one (utterance, position) scale
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[t][c][r] *= inv;           // the accumulator is C^T: a lane holds ONE row, so one (utterance, position) scale
 
   constexpr int SP = 68;
   float* St = reinterpret_cast<float*>(smem) + wid * (32 * SP);
   const int rr = lane >> 4, c4 = (lane & 15) * 4;
-  float* Mrow = a.M + (long long)p * a.sM + (long long)(m0 + wid * 32) * a.Cout + nb * WBN;
 #pragma unroll
-  for (int hb = 0; hb < 2; ++hb) {
+  for (int t = 0; t < CB; ++t) {
+    float* Mrow = a.M + (long long)p * a.sM + (long long)(m0 + wid * 32) * a.Cout + (nb + t) * WBN;
 #pragma unroll
-    for (int cl = 0; cl < 2; ++cl)
+    for (int hb = 0; hb < 2; ++hb) {
 #pragma unroll
-      for (int g = 0; g < 4; ++g)
-        *reinterpret_cast<float4*>(St + (lane & 31) * SP + cl * 32 + 8 * g + 4 * (lane >> 5)) =
-            make_float4(acc[2 * hb + cl][4 * g], acc[2 * hb + cl][4 * g + 1], acc[2 * hb + cl][4 * g + 2], acc[2 * hb + cl][4 * g + 3]);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+      for (int cl = 0; cl < 2; ++cl)
 #pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int r = 4 * it + rr;
-      const float4 v = *reinterpret_cast<const float4*>(St + r * SP + c4);
-      if (m0 + wid * 32 + r < a.Mt) *reinterpret_cast<float4*>(Mrow + (long long)r * a.Cout + hb * 64 + c4) = v;
+        for (int g = 0; g < 4; ++g)
+          *reinterpret_cast<float4*>(St + (lane & 31) * SP + cl * 32 + 8 * g + 4 * (lane >> 5)) =
+              make_float4(acc[t][2 * hb + cl][4 * g], acc[t][2 * hb + cl][4 * g + 1], acc[t][2 * hb + cl][4 * g + 2], acc[t][2 * hb + cl][4 * g + 3]);
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int it = 0; it < 8; ++it) {
+        const int r = 4 * it + rr;
+        const float4 v = *reinterpret_cast<const float4*>(St + r * SP + c4);
+        if (m0 + wid * 32 + r < a.Mt) *reinterpret_cast<float4*>(Mrow + (long long)r * a.Cout + hb * 64 + c4) = v;
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
     }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// 32 rows per wave; workgroup = 128 rows x 128 CB columns of one position.
+//  * CB = 1: three workgroups per CU; the kernel of tiles_per_utt < 64 (and of option wgemm_rt = 1).
+//  * CB = 2 (128 accumulators per lane, two workgroups per CU, a 32 KB weight stage; the batched sibling of wgemm_f16x2_gen_kernel<2, .>): with NB >= 2 the
+//    NB workgroups of a row block each read -- and split -- the same V rows (an L2 hit, but 40 % of the kernel in isolation: profiles/README.md, "The
+//    batched GEMM once more").  Here a row block's V is read and split once per PAIR of column blocks, the pair's two stage images fetched side by side
+//    (a position's next column block lies S stage images later) and multiplied into two accumulator sets; an odd NB leaves the last block of a row block to
+//    a workgroup that runs the one-block body (a workgroup-uniform branch around the whole tile, nothing inside the K loop).
+//  Every output sums the same products in the same order in both forms and in wgemm_f16x2_rt2_kernel: the same bits.
+template <int CB>
+__global__ __launch_bounds__(WNT, CB == 1 ? 3 : 2) void wgemm_f16x2_kernel(const WgemmArgs a) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[CB == 1 ? LDS2_BYTES : 2 * CB * STAGE2_BYTES];
+  static_assert(CB == 1 || CB == 2, "the grid below counts ceil(NB / CB) workgroups per row block");
+  int lid, p;
+  xcd_tile_position(a.pz, a.gx, lid, p);
+  const int NP = (a.NB + CB - 1) / CB, nb = (lid % NP) * CB, m0 = (lid / NP) * WBM;
+  if constexpr (CB == 1) f16x2_batched_tile<1>(a, smem, p, nb, m0);
+  else {
+    if (nb + 1 < a.NB) f16x2_batched_tile<2>(a, smem, p, nb, m0);
+    else f16x2_batched_tile<1>(a, smem, p, nb, m0);
   }
 }
 
@@ -1046,6 +1074,18 @@ void launch_abs_max_bits(const float* x, int groups, int segments, long long seg
   const unsigned chunks = (unsigned)std::min<long long>(256, (seg_len + 2047) / 2048);
   hipLaunchKernelGGL(abs_max_bits_kernel, dim3(chunks, (unsigned)segments), dim3(256), 0, st, x, groups, segments, seg_len, out);
 }
+// two column blocks per workgroup (wgemm_f16x2_kernel<2>) where option wgemm_cb says so: 1 never, 2 wherever NB >= 2, 0 = by the rule: an EVEN number of
+// column blocks, from 400 rows on.  Every distinct shape with NB >= 2 of the shipped network's step in isolation, 64 positions, this form against what ran before
+// (wgemm_f16x2_rt2_kernel; the 32-row kernel at 400 rows), alternating, two runs each (tools/wgemm_one.py --table, profiles/README.md): NB = 2, 4 and 8 win at every
+// rows x Cin measured -- 29584 x 256 x 256 1197 -> 1147 us, x 128 677 -> 616; 7568 x 256 x {128, 256, 384, 512} 172 -> 161, 263 -> 242, 362 -> 336, 454 -> 423; 7568 x
+// 512 x 256 507 -> 470; 5624 x 1024 x 256 737 -> 691; 1936 x 256 x 256 74.5 -> 70.0; 528 x 256 x 256 33.6 -> 31.9; 400 x 1024 x 256 69.5 -> 63.3 -- by 4 ... 16 %, each
+// run beyond the other form's spread.  NB = 3 (Cout = 384: a pair plus a 32-row single block) loses, 980 -> 986 us at 29584 x 384 x 128 and 381 -> 385 at 7568 x 384 x 256,
+// and stays where it was; below 400 rows nothing was measured.  Option wgemm_rt = 1 (the 32-row one-block kernel everywhere) goes first.
+static bool wgemm_colpair(long long Mt, int NB) {
+  const int c = cur_opt().wgemm_cb;
+  if (NB < 2 || c == 1 || cur_opt().wgemm_rt == 1) return false;
+  return c == 2 || (NB % 2 == 0 && Mt >= 400);
+}
 // vmax: [utterance][VMAX_SUB][VMAX_STRIDE] partial abs-maxima (float bits) of V; an utterance = tiles_per_utt (>= 32) consecutive rows
 void launch_wgemm_f16x2(const float* V, const void* U2, float* M, long long Mt, int Cout, int Cin, int P, const unsigned* vmax, int tiles_per_utt, hipStream_t st) {
   WgemmArgs a{};
@@ -1055,13 +1095,15 @@ void launch_wgemm_f16x2(const float* V, const void* U2, float* M, long long Mt, 
   a.vmax = vmax; a.tpu = tiles_per_utt; a.uinv = reinterpret_cast<const float*>(a.U3 + (size_t)P * Cout * Cin * 4);
   // 64-row waves (wgemm_f16x2_rt2_kernel): 4-6 % faster on every shape of the shipped network (tools/wgemm_modes_bench.py, profiles/README.md r05i); option
   // wgemm_rt 1 = the 32-row kernel
-  const bool rt2 = tiles_per_utt >= 64 && cur_opt().wgemm_rt != 1;
-  const int gx = cdiv((int)Mt, rt2 ? 2 * WBM : WBM) * a.NB;
+  const bool cb2 = wgemm_colpair(Mt, a.NB);
+  const bool rt2 = !cb2 && tiles_per_utt >= 64 && cur_opt().wgemm_rt != 1;
+  const int gx = cb2 ? cdiv((int)Mt, WBM) * ((a.NB + 1) / 2) : cdiv((int)Mt, rt2 ? 2 * WBM : WBM) * a.NB;
   const bool fold = P % 8 == 0 && (long long)gx * P < (1LL << 31);
   a.pz = fold ? P : 0; a.gx = gx;
   const dim3 grid(fold ? (unsigned)(gx * P) : (unsigned)gx, 1, fold ? 1u : (unsigned)P);
-  if (rt2) hipLaunchKernelGGL(wgemm_f16x2_rt2_kernel, grid, dim3(WNT), 0, st, a);
-  else hipLaunchKernelGGL(wgemm_f16x2_kernel, grid, dim3(WNT), 0, st, a);
+  if (cb2) hipLaunchKernelGGL(wgemm_f16x2_kernel<2>, grid, dim3(WNT), 0, st, a);
+  else if (rt2) hipLaunchKernelGGL(wgemm_f16x2_rt2_kernel, grid, dim3(WNT), 0, st, a);
+  else hipLaunchKernelGGL(wgemm_f16x2_kernel<1>, grid, dim3(WNT), 0, st, a);
 }
 
 }  // namespace buddy

@@ -365,7 +365,7 @@ int buddy_fir_resample2(const float* x, float* y, int B, int H, int W, int C, in
 int buddy_ncsnpp_set_fir(void* handle, int fir);
 /* Per-handle launcher options -- "no hidden global state" (SURVEY.md 8(b)): every switch a launcher consults (attention core, GEMM arithmetic, the
  * fusions and kernel forms the tests compare) is a field of the handle's option struct; two handles in one process may differ.  Keys (csrc/options.hip): conv, gemm,
- * attention, gn_fuse, upconv, c2_fuse, attn_split, attn_nw, wgemm_rt, gen_f16x2, gen_rows, gen_cp, gnb_nt, c2out_tiled, op_graph.  An unknown key (the
+ * attention, gn_fuse, upconv, c2_fuse, attn_split, attn_nw, wgemm_rt, wgemm_cb, gen_f16x2, gen_rows, gen_cp, gnb_nt, c2out_tiled, op_graph.  An unknown key (the
  * retired A/B switches included) or a value out of range is BUDDY_ERR_ARG.  A handle starts from the process defaults = the BUDDY_<KEY> environment variables, parsed and validated in ONE place at handle
  * creation: a bad value, or an unknown BUDDY_* name within edit distance 2 of a switch (a misspelling), makes buddy_ncsnpp_create fail with a message naming it;
  * the environment name of a retired A/B switch fails the same way ("... has been retired; unset it"); BUDDY_* names that resemble no switch are not this
