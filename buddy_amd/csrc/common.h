@@ -211,26 +211,6 @@ void launch_unpad_adj(const float* dframes, int ldF, int T, int n_fft, int hop, 
 
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
-// ---- XCD-aware workgroup order of the GEMM kernels (wgemm.hip, wgemm16.hip) -------------------------------
-// The hardware places workgroup b of the flattened grid on XCD b % 8, each XCD with its own L2.
-// 1-D form: the logical tile of workgroup `orig` of `nwg`, such that each XCD gets a contiguous range of logical tiles.
-__device__ __forceinline__ int xcd_tile(int orig, int nwg) {
-  const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7, k = orig >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
-}
-// Batched form: logical tile `lid` and position `p` of this workgroup.  Positions a multiple of 8 are folded into a 1-D grid of pz positions x gx
-// workgroups each (pz > 0): XCD x takes the positions x, x + 8, ... and walks all their tiles, so a position's weight panel is fetched into ONE L2
-// instead of all eight.  Otherwise blockIdx.z is the position and the tiles go by the 1-D form.
-__device__ __forceinline__ void xcd_tile_position(int pz, int gx, int& lid, int& p) {
-  if (pz > 0) {
-    const int orig = blockIdx.x, xcd = orig & 7, k = orig >> 3;     // k-th workgroup of this XCD: gx * pz / 8 of them
-    lid = k % gx; p = xcd + 8 * (k / gx);
-  } else {
-    lid = xcd_tile(blockIdx.x, gridDim.x);
-    p = blockIdx.z;
-  }
-}
-
 // ---- parameter gradients (wgrad.hip) ----------------------------------------------------------------------
 // dY[m][n] = p[(m / T) * sb + (m % T) * sm + n * sn]: an NHWC gradient (T = M, sm = ld, sn = 1) or a per-utterance transposed one
 struct WgY { const float* p; long long T, sb, sm, sn; };

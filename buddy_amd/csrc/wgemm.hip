@@ -18,7 +18,7 @@
 //    x 16 B, so a stage is a linear 24 KB copy and every fragment read is one conflict-free ds_read_b128;
 //  * LDS is double-buffered: ONE barrier per K-stage of 48 MFMAs per wave; global loads for stage s + 1 are issued before the MFMAs of stage s;
 //  * the accumulator is C^T (weights as the MFMA's first operand): a lane holds 4 consecutive output channels of one row -> 16-byte stores.
-#include "common.h"
+#include "wgemm_tile.h"
 #include <algorithm>
 #include <cstdint>
 #include <type_traits>
@@ -26,13 +26,9 @@
 
 namespace buddy {
 namespace {
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int WBM = 128, WBN = 128, WKS = 32, WNT = 256;
 constexpr int STAGE_BYTES = WBN * WKS * 6;                    // 24 KB: 2 k-chunks x 4 column blocks x 3 planes x 1 KB
-constexpr int FRAG = 1024;                                    // bytes of one (chunk, column block, plane) fragment block: 64 lanes x 16 B
 
 struct Split3 { bf16x8 p[3]; };
 // exact three-way split of 8 fp32 values by truncation (hi = top 16 bits; mid = top 16 bits of x - hi; lo = x - hi - mid, <= 8 significant bits)
@@ -101,8 +97,96 @@ __device__ __forceinline__ float dsilu_g(float z) {
   return s * (1.f + z * (1.f - s));
 }
 
-// GEN: the general form (two-source A, row strides, alpha / bias / accumulate epilogue).  The accumulator tile goes through a wave-private LDS
-// slab (the weight buffers are free after the last stage) and leaves as 256-byte row pieces (32-byte pieces per lane pair: +0.3 ... 1.9 % slower).
+// The epilogues of the general form, bf16x3 and f16x2 alike, for one 32-row x 128-column accumulator tile of a wave (rows rbase ..., column block nb; SCALE:
+// times the rows' inverse scale inv) through the wave-private LDS slab St (slab_write, wgemm_tile.h), 256-byte row pieces.
+//  * !GNB: C = alpha * acc + bias (+ C), the same operation order as the fp32 kernel's epilogue.
+//  * GNB: out = the GroupNorm backward's apply pass of (x, da) + alpha * acc (+ out), the same operation order as gn_bwd_apply_m0_kernel: GroupNorm term,
+//    + extra_scale * extra, + previous.  The x / da loads and the dx stores are whole cache lines; a.gnt: x and da by non-temporal loads.
+template <bool GNB, bool SCALE>
+__device__ __forceinline__ void wgemm_gen_epilogue(const WgemmArgs& a, const f32x16 (&acc)[4], const float inv, const int rbase, const int nb, float* St, const int lane) {
+  constexpr int SP = SLAB_SP;
+  const int rr = lane >> 4, c4 = (lane & 15) * 4;
+  if constexpr (!GNB) {
+    const long long ldc = a.ldC;
+    float* Mrow = a.M + (long long)rbase * ldc + nb * WBN;
+#pragma unroll
+    for (int hb = 0; hb < 2; ++hb) {
+      slab_write<SCALE>(acc, inv, hb, St, lane);
+      float4 bs = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (a.bias_n) bs = *reinterpret_cast<const float4*>(a.bias_n + nb * WBN + hb * 64 + c4);
+      float4 pv[8];
+#pragma unroll
+      for (int it = 0; it < 8; ++it) {                         // previous values (accumulate) in flight together, rows clamped
+        const int r = min(4 * it + rr, a.Mt - 1 - rbase);
+        pv[it] = a.accumulate ? *reinterpret_cast<const float4*>(Mrow + (long long)r * ldc + hb * 64 + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+      for (int it = 0; it < 8; ++it) {
+        const int r = 4 * it + rr;
+        float4 v = *reinterpret_cast<const float4*>(St + r * SP + c4);
+        v.x *= a.alpha; v.y *= a.alpha; v.z *= a.alpha; v.w *= a.alpha;
+        if (a.bias_n) { v.x += bs.x; v.y += bs.y; v.z += bs.z; v.w += bs.w; }
+        if (a.accumulate) { v.x += pv[it].x; v.y += pv[it].y; v.z += pv[it].z; v.w += pv[it].w; }
+        if (rbase + r < a.Mt) *reinterpret_cast<float4*>(Mrow + (long long)r * ldc + hb * 64 + c4) = v;
+      }
+      slab_done();
+    }
+  } else {
+    const int cpg = a.Cout / a.gG;
+    const bool second = a.gxv.p1 != nullptr && nb * WBN >= a.gxv.C0, dsecond = a.gd.p1 != nullptr && nb * WBN >= a.gd.C0;
+    const long long ldx = second ? a.gxv.ld1 : a.gxv.ld0, ldo = dsecond ? a.gd.ld1 : a.gd.ld0;
+    const bool accd = (dsecond ? a.gd.acc1 : a.gd.acc0) != 0;
+#pragma unroll
+    for (int hb = 0; hb < 2; ++hb) {
+      const int col = nb * WBN + hb * 64 + c4, grp = col / cpg;
+      const float* xs = (second ? a.gxv.p1 + (col - a.gxv.C0) : a.gxv.p0 + col);
+      float* o = (dsecond ? a.gd.p1 + (col - a.gd.C0) : a.gd.p0 + col);
+      const float* das = a.gda + col;
+      const float4 gm = *reinterpret_cast<const float4*>(a.ggamma + col), bt = *reinterpret_cast<const float4*>(a.gbeta + col);
+      const float g4[4] = {gm.x, gm.y, gm.z, gm.w}, b4[4] = {bt.x, bt.y, bt.z, bt.w};
+      slab_write<SCALE>(acc, inv, hb, St, lane);
+      // 16 rows at a time: the loads of the batch first (rows clamped: never stored past Mt), then the arithmetic (registers: 12 float4 + 16 scalars)
+#pragma unroll
+      for (int bt4 = 0; bt4 < 2; ++bt4) {
+        float4 xv[4], dv[4], pv[4];
+        float mean[4], rstd[4], m1[4], m2[4];
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+          const int r = min(rbase + 16 * bt4 + 4 * it + rr, a.Mt - 1), bb = r / a.gHW;
+          if (a.gnt) { xv[it] = ld4nt_g(xs + (long long)r * ldx); dv[it] = ld4nt_g(das + (long long)r * a.Cout); }
+          else { xv[it] = *reinterpret_cast<const float4*>(xs + (long long)r * ldx); dv[it] = *reinterpret_cast<const float4*>(das + (long long)r * a.Cout); }
+          pv[it] = accd ? *reinterpret_cast<const float4*>(o + (long long)r * ldo) : make_float4(0.f, 0.f, 0.f, 0.f);
+          const float2 sm = *reinterpret_cast<const float2*>(a.gstats + ((long long)bb * a.gG + grp) * 2), rm = *reinterpret_cast<const float2*>(a.gred + ((long long)bb * a.gG + grp) * 2);
+          mean[it] = sm.x; rstd[it] = sm.y; m1[it] = rm.x; m2[it] = rm.y;
+        }
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {
+          const int rl = 16 * bt4 + 4 * it + rr;
+          const float4 cv = *reinterpret_cast<const float4*>(St + rl * SP + c4);
+          const float x4[4] = {xv[it].x, xv[it].y, xv[it].z, xv[it].w}, d4[4] = {dv[it].x, dv[it].y, dv[it].z, dv[it].w};
+          const float p4[4] = {pv[it].x, pv[it].y, pv[it].z, pv[it].w}, c4v[4] = {cv.x, cv.y, cv.z, cv.w};
+          float r[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float xh = (x4[j] - mean[it]) * rstd[it];
+            const float z = xh * g4[j] + b4[j];
+            const float dxh = d4[j] * (a.gsilu ? dsilu_g(z) : 1.f) * g4[j];
+            const float t = dxh - m1[it] - xh * m2[it];
+            // rstd * t + alpha * acc is ONE fma, and which of the two products it keeps unrounded is written out: left to the compiler, the two copies this
+            // text replaces had come out one each way, and each arithmetic keeps the bits it has always computed
+            r[j] = SCALE ? fmaf(a.alpha, c4v[j], rstd[it] * t) : fmaf(rstd[it], t, a.alpha * c4v[j]);
+            r[j] += p4[j];
+          }
+          if (rbase + rl < a.Mt) *reinterpret_cast<float4*>(o + (long long)(rbase + rl) * ldo) = make_float4(r[0], r[1], r[2], r[3]);
+        }
+      }
+      slab_done();
+    }
+  }
+}
+
+// GEN: the general form (two-source A, row strides, alpha / bias / accumulate epilogue: wgemm_gen_epilogue above).  In every form the accumulator tile goes
+// through a wave-private LDS slab and leaves as 256-byte row pieces (the slab-transpose store, wgemm_tile.h; 32-byte pieces per lane pair: +0.3 ... 1.9 % slower).
 // Measured and rejected (profiles/README.md r03a): a second stage of A in flight (190 VGPRs: -3 %), 64 rows per wave (256+ VGPRs: -25 %), two
 // instead of three workgroups per CU (-2...4 %).
 // GNB (with GEN): the skip path's 1x1 data-gradient of a ResBlock (Conv_2^T, layerspp.py:262-264) and the GroupNorm_0 backward's apply pass in ONE launch:
@@ -118,7 +202,7 @@ template <bool GEN, bool GNB = false>
 __global__ __launch_bounds__(WNT, 3) void wgemm_bf16x3_kernel(const WgemmArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE_BYTES];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  // XCD-aware order (xcd_tile_position, common.h): folded, a position's weight panel is K x 128 x 6 B per column block (r03 PMC: the GEMM fetched
+  // XCD-aware order (xcd_tile_position, wgemm_tile.h): folded, a position's weight panel is K x 128 x 6 B per column block (r03 PMC: the GEMM fetched
   // 1.42x its V bytes; 8 x 25 MB of panels per 256 -> 256 convolution were most of the excess).  In both forms the column blocks of one row tile
   // are adjacent, so the second column block finds its V rows in the same L2.
   int lid, p;
@@ -185,116 +269,11 @@ __global__ __launch_bounds__(WNT, 3) void wgemm_bf16x3_kernel(const WgemmArgs a)
     __syncthreads();
   }
 
-  // epilogue: accumulator = C^T tile, lane (row = lane & 31, h = lane >> 5) holds channels 8 g + 4 h + 0..3 of each 32-channel block
-  if constexpr (!GNB) {
-    constexpr int SP = 68;                                   // floats per staged row (64 columns + 4: conflict-free 16-byte writes down a column)
-    float* St = reinterpret_cast<float*>(smem) + wid * (32 * SP);
-    const int rr = lane >> 4, c4 = (lane & 15) * 4;
-    const long long ldc = GEN ? a.ldC : a.Cout;
-    float* Mrow = a.M + (long long)p * a.sM + (long long)(m0 + wid * 32) * ldc + nb * WBN;
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb) {
-#pragma unroll
-      for (int cl = 0; cl < 2; ++cl)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *reinterpret_cast<float4*>(St + (lane & 31) * SP + cl * 32 + 8 * g + 4 * (lane >> 5)) =
-              make_float4(acc[2 * hb + cl][4 * g], acc[2 * hb + cl][4 * g + 1], acc[2 * hb + cl][4 * g + 2], acc[2 * hb + cl][4 * g + 3]);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      if (GEN) {                                              // general form: alpha * acc, + bias, + C (same operation order as the fp32 kernel's epilogue)
-        float4 bs = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (a.bias_n) bs = *reinterpret_cast<const float4*>(a.bias_n + nb * WBN + hb * 64 + c4);
-        float4 pv[8];
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {                       // previous values (accumulate) in flight together, rows clamped
-          const int r = min(4 * it + rr, a.Mt - 1 - (m0 + wid * 32));
-          pv[it] = a.accumulate ? *reinterpret_cast<const float4*>(Mrow + (long long)r * ldc + hb * 64 + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-          const int r = 4 * it + rr;
-          float4 v = *reinterpret_cast<const float4*>(St + r * SP + c4);
-          v.x *= a.alpha; v.y *= a.alpha; v.z *= a.alpha; v.w *= a.alpha;
-          if (a.bias_n) { v.x += bs.x; v.y += bs.y; v.z += bs.z; v.w += bs.w; }
-          if (a.accumulate) { v.x += pv[it].x; v.y += pv[it].y; v.z += pv[it].z; v.w += pv[it].w; }
-          if (m0 + wid * 32 + r < a.Mt) *reinterpret_cast<float4*>(Mrow + (long long)r * ldc + hb * 64 + c4) = v;
-        }
-      } else {
-#pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const int r = 4 * it + rr;
-        const float4 v = *reinterpret_cast<const float4*>(St + r * SP + c4);
-        if (m0 + wid * 32 + r < a.Mt) *reinterpret_cast<float4*>(Mrow + (long long)r * a.Cout + hb * 64 + c4) = v;
-      }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-    }
-  } else {
-    // The accumulator tile goes through the same wave-private LDS slab so that a lane owns 16-byte pieces of 256-byte ROW pieces
-    // (16 lanes per row): the x / da loads and the dx stores are whole cache lines (in MFMA order a lane pair covers 32 bytes of 32 rows).
-    constexpr int SP = 68;
-    float* St = reinterpret_cast<float*>(smem) + wid * (32 * SP);
-    const int rr = lane >> 4, c4 = (lane & 15) * 4;
-    const int rbase = m0 + wid * 32;
-    const int cpg = a.Cout / a.gG;
-    const bool second = a.gxv.p1 != nullptr && nb * WBN >= a.gxv.C0, dsecond = a.gd.p1 != nullptr && nb * WBN >= a.gd.C0;
-    const long long ldx = second ? a.gxv.ld1 : a.gxv.ld0, ldo = dsecond ? a.gd.ld1 : a.gd.ld0;
-    const bool accd = (dsecond ? a.gd.acc1 : a.gd.acc0) != 0;
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb) {
-      const int col = nb * WBN + hb * 64 + c4, grp = col / cpg;
-      const float* xs = (second ? a.gxv.p1 + (col - a.gxv.C0) : a.gxv.p0 + col);
-      float* o = (dsecond ? a.gd.p1 + (col - a.gd.C0) : a.gd.p0 + col);
-      const float* das = a.gda + col;
-      const float4 gm = *reinterpret_cast<const float4*>(a.ggamma + col), bt = *reinterpret_cast<const float4*>(a.gbeta + col);
-      const float g4[4] = {gm.x, gm.y, gm.z, gm.w}, b4[4] = {bt.x, bt.y, bt.z, bt.w};
-#pragma unroll
-      for (int cl = 0; cl < 2; ++cl)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *reinterpret_cast<float4*>(St + (lane & 31) * SP + cl * 32 + 8 * g + 4 * (lane >> 5)) =
-              make_float4(acc[2 * hb + cl][4 * g], acc[2 * hb + cl][4 * g + 1], acc[2 * hb + cl][4 * g + 2], acc[2 * hb + cl][4 * g + 3]);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      // 16 rows at a time: the loads of the batch first (rows clamped: never stored past Mt), then the arithmetic (registers: 12 float4 + 16 scalars)
-#pragma unroll
-      for (int bt4 = 0; bt4 < 2; ++bt4) {
-        float4 xv[4], dv[4], pv[4];
-        float mean[4], rstd[4], m1[4], m2[4];
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-          const int r = min(rbase + 16 * bt4 + 4 * it + rr, a.Mt - 1), bb = r / a.gHW;
-          xv[it] = *reinterpret_cast<const float4*>(xs + (long long)r * ldx);
-          dv[it] = *reinterpret_cast<const float4*>(das + (long long)r * a.Cout);
-          pv[it] = accd ? *reinterpret_cast<const float4*>(o + (long long)r * ldo) : make_float4(0.f, 0.f, 0.f, 0.f);
-          const float2 sm = *reinterpret_cast<const float2*>(a.gstats + ((long long)bb * a.gG + grp) * 2), rm = *reinterpret_cast<const float2*>(a.gred + ((long long)bb * a.gG + grp) * 2);
-          mean[it] = sm.x; rstd[it] = sm.y; m1[it] = rm.x; m2[it] = rm.y;
-        }
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-          const int rl = 16 * bt4 + 4 * it + rr;
-          const float4 cv = *reinterpret_cast<const float4*>(St + rl * SP + c4);
-          const float x4[4] = {xv[it].x, xv[it].y, xv[it].z, xv[it].w}, d4[4] = {dv[it].x, dv[it].y, dv[it].z, dv[it].w};
-          const float p4[4] = {pv[it].x, pv[it].y, pv[it].z, pv[it].w}, c4v[4] = {cv.x, cv.y, cv.z, cv.w};
-          float r[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {                         // same operation order as gn_bwd_apply_m0_kernel: GroupNorm term, + extra_scale * extra, + previous
-            const float xh = (x4[j] - mean[it]) * rstd[it];
-            const float z = xh * g4[j] + b4[j];
-            const float dxh = d4[j] * (a.gsilu ? dsilu_g(z) : 1.f) * g4[j];
-            r[j] = rstd[it] * (dxh - m1[it] - xh * m2[it]);
-            r[j] += a.alpha * c4v[j];
-            r[j] += p4[j];
-          }
-          if (rbase + rl < a.Mt) *reinterpret_cast<float4*>(o + (long long)(rbase + rl) * ldo) = make_float4(r[0], r[1], r[2], r[3]);
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
+  // epilogue (wgemm_tile.h, "the slab-transpose store"): the accumulators are the exact sums, no scale
+  float* St = reinterpret_cast<float*>(smem) + wid * (SLAB_BYTES / 4);
+  const int rbase = m0 + wid * 32;
+  if constexpr (GEN) wgemm_gen_epilogue<GNB, false>(a, acc, 1.f, rbase, nb, St, lane);
+  else slab_store<false>(acc, 1.f, St, a.M + (long long)p * a.sM + (long long)rbase * a.Cout + nb * WBN, a.Cout, a.Mt - rbase, lane);
 }
 
 // ------------------------------------------------------------------------------------------------ f16x2 form of the batched GEMM
@@ -306,22 +285,9 @@ __global__ __launch_bounds__(WNT, 3) void wgemm_bf16x3_kernel(const WgemmArgs a)
 // two per position (their abs-max -> [2^14, 2^15), applied when packing; the inverse is in the image's tail), V one per UTTERANCE (abs-max collected by the
 // input transform with an atomic max, the power of two derived here from its exponent field), so that an utterance's result does not depend on its batch;
 // lo is a normal f16 for |x s| >= 2^-3, i.e. 2^-18 of the abs-max; below that the representation error is absolute, <= 2^-25 = 2^-40 of the abs-max.
-// Same workgroup / wave tiling, staging, XCD order and epilogue as wgemm_bf16x3_kernel<false>; a stage image is 16 KB ([k chunk][column block][plane]
+// Same workgroup / wave tiling, staging, XCD order and store (slab_store, wgemm_tile.h) as wgemm_bf16x3_kernel<false>; a stage image is 16 KB ([k chunk][column block][plane]
 // [lane] x 16 B), 24 MFMAs per wave and barrier.
-// LDS-DMA of 16 bytes per lane as inline asm: source = uniform 64-bit base (SGPR pair) + a 32-bit per-lane byte offset, LDS destination = M0 + 16 * lane
-__device__ __forceinline__ void glds16_asm(const void* sbase, unsigned voff, unsigned lds_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_addr) : "memory");
-}
-__device__ __forceinline__ const void* uniform_ptr(const void* p) {
-  const unsigned long long v = (unsigned long long)p;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return (const void*)(((unsigned long long)hi << 32) | lo);
-}
 constexpr int STAGE2_BYTES = WBN * WKS * 4;                   // 16 KB: 2 k-chunks x 4 column blocks x 2 planes x 1 KB
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
 struct Split2 { f16x8 p[2]; };
 // x s = hi + lo by round-to-nearest.  Measured and rejected (round 5, same box A/B): lo as ONE v_fma_mixlo/hi_f16 per element through inline asm (64 instead of
 // 116 VALU instructions per 48 MFMAs; bit-identical) -- 1.5 % SLOWER on the 256-channel shapes: the vector ALU is not what the kernel waits for.
@@ -335,14 +301,6 @@ __device__ __forceinline__ Split2 split2(const float4 a, const float4 b, float s
     r.p[1][i] = (_Float16)(x[i] - (float)h);
   }
   return r;
-}
-// the power of two that takes an abs-max (float bits) into [2^14, 2^15), and its inverse; exponent fields outside [15, 253] are clamped (zero / tiny / huge
-// tensors: the scale stays a finite normal number)
-__device__ __forceinline__ void pow2_scale(unsigned bits, float& s, float& inv) {
-  int e = (int)((bits >> 23) & 0xFF);
-  e = e < 15 ? 15 : (e > 253 ? 253 : e);
-  s = __uint_as_float((unsigned)(268 - e) << 23);
-  inv = __uint_as_float((unsigned)(e - 14) << 23);
 }
 
 // abs-max of every position's weight matrix -> umax[p] (float bits); grid (chunks, P), umax zeroed before
@@ -390,9 +348,25 @@ __global__ __launch_bounds__(256) void wgemm_pack2_kernel(const float* __restric
   out[i] = (u32x4)sp.p[q];
 }
 
+// The abs-max words (float bits) of the utterances b0 (returned) and b1 >= b0 that hold rows r0 and r1 >= r0 of a wave (tpu rows per utterance, at least as many as
+// the wave has: at most two utterances): mb[0] and mb[1].  An utterance's abs-max = the maximum of its VMAX_SUB partial words: one word per lane, a wave-wide
+// maximum.  Agent-scope atomic loads: the words were written by agent-scope atomics (executed at the memory side); a plain load may hit a stale line of
+// this XCD's L2.
+__device__ __forceinline__ int f16x2_utt_absmax(const unsigned* vmax, const int tpu, const int r0, const int r1, const int lane, unsigned (&mb)[2]) {
+  const int b0 = r0 / tpu, b1 = r1 / tpu;
+  mb[0] = __hip_atomic_load(vmax + ((long long)b0 * VMAX_SUB + lane) * VMAX_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (int o = 32; o > 0; o >>= 1) mb[0] = max(mb[0], (unsigned)__shfl_xor((int)mb[0], o));
+  mb[1] = mb[0];
+  if (b1 != b0) {
+    mb[1] = __hip_atomic_load(vmax + ((long long)b1 * VMAX_SUB + lane) * VMAX_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int o = 32; o > 0; o >>= 1) mb[1] = max(mb[1], (unsigned)__shfl_xor((int)mb[1], o));
+  }
+  return b0;
+}
+
 // ---- the pieces every f16x2 kernel of this file is written on
 // LDS of a workgroup with one column block: two weight stages, or the four waves' epilogue slabs (32 rows x 68 floats each) where those are larger
-constexpr int LDS2_BYTES = (2 * STAGE2_BYTES > 4 * 32 * 68 * 4) ? 2 * STAGE2_BYTES : 4 * 32 * 68 * 4;
+constexpr int LDS2_BYTES = (2 * STAGE2_BYTES > 4 * SLAB_BYTES) ? 2 * STAGE2_BYTES : 4 * SLAB_BYTES;
 
 // The weights of K-stage s of CB column blocks, global -> LDS by LDS-DMA: 4 x 16 B per thread and column block.  Ub = the first column block's stage images
 // (the next block's follow S images later), lds0 = this wave's 1 KB of LDS buffer 0, boff = 16 * tid; buffer s & 1 holds the CB images side by side.
@@ -403,7 +377,7 @@ __device__ __forceinline__ void f16x2_dma_stage(const char* Ub, int S, int s, un
     const void* base = uniform_ptr(Ub + ((long long)t * S + s) * STAGE2_BYTES);
     const unsigned l = lds0 + ((s & 1) * CB + t) * STAGE2_BYTES;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) glds16_asm(base, boff + j * (WNT * 16), l + j * (WNT * 16));
+    for (int j = 0; j < 4; ++j) glds16(base, boff + j * (WNT * 16), l + j * (WNT * 16));
   }
 }
 
@@ -430,6 +404,10 @@ __device__ __forceinline__ void f16x2_mfma_stage(const unsigned char* Bcur, cons
 }
 
 // The 32-row batched kernel's work on CB adjacent column blocks nb ... nb + CB - 1 of row block m0 of position p (see wgemm_f16x2_kernel below).
+// Its utterance-scale lookup and its store are written out here -- the texts of f16x2_utt_absmax (above) and slab_store (wgemm_tile.h), the scale applied in a
+// loop before the store: on the shared texts wgemm_f16x2_kernel<2> kept its registers, scratch, occupancy and LDS but compiled to another instruction stream that
+// ran 0.5 ... 2.8 % slower per launch on 15 of the 21 shapes of tools/wgemm_one.py --table cb2 (10 % at 400 x 256 x 1024), beyond the parent's run-to-run range
+// (profiles/README.md, "one tile header ..."); as written both instantiations compile to the instruction stream they had (profiles/wgemm_tile_resources.txt).
 template <int CB>
 __device__ __forceinline__ void f16x2_batched_tile(const WgemmArgs& a, unsigned char* smem, const int p, const int nb, const int m0) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -507,14 +485,15 @@ __device__ __forceinline__ void f16x2_batched_tile(const WgemmArgs& a, unsigned 
   }
   stage(s, ra[0], std::true_type{}, std::false_type{});
   stage(s + 1, ra[1], std::false_type{}, std::false_type{});
+
 #pragma unroll
   for (int t = 0; t < CB; ++t)
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[t][c][r] *= inv;           // the accumulator is C^T: a lane holds ONE row, so one (utterance, position) scale
+      for (int r = 0; r < 16; ++r) acc[t][c][r] *= inv;
 
-  constexpr int SP = 68;
+  constexpr int SP = SLAB_SP;
   float* St = reinterpret_cast<float*>(smem) + wid * (32 * SP);
   const int rr = lane >> 4, c4 = (lane & 15) * 4;
 #pragma unroll
@@ -572,110 +551,12 @@ __global__ __launch_bounds__(WNT, CB == 1 ? 3 : 2) void wgemm_f16x2_kernel(const
 // multiplied by the (exact) power of two that takes them to the new scale, which puts the stage's abs-max into [2^12, 2^13).  A row's result depends on
 // nothing but the row, no pre-pass re-reads A (the first version's did, from beyond L2: it took away what the halved MFMA count gave), and the rescale is a
 // wave-uniform branch taken a few times per row.
-// One body in three tilings, all with the two-source A of wgemm_bf16x3_kernel<true, GNB>, LDS-DMA weight stages and f16x2_gen_epilogue, chosen per launch
+// One body in three tilings, all with the two-source A of wgemm_bf16x3_kernel<true, GNB>, LDS-DMA weight stages and wgemm_gen_epilogue, chosen per launch
 // by launch_f16x2_gen (gen_colpair / gen_rows64 below):
 //   wgemm_f16x2_gen_kernel<1, GNB>   32-row waves, one column block   (pipeline of wgemm_f16x2_kernel)       the small launches
 //   wgemm_f16x2_gen_kernel<2, GNB>   32-row waves, two column blocks  (the same; A read and split once)      N % 256 == 0 from 32768 rows on
 //   wgemm_f16x2_gen64_kernel<GNB>    64-row waves, one column block   (pipeline of wgemm_f16x2_rt2_kernel)   the other launches from 32768 rows on
 // They share f16x2_gen_rows, f16x2_row_rescale, f16x2_dma_stage and f16x2_mfma_stage; a row's result is the same bits in all three.
-
-// epilogues of wgemm_bf16x3_kernel<true, GNB> for one 32-row x 128-column accumulator tile of a wave (rows rbase ..., x the rows' inverse scale)
-// through the wave-private LDS slab St, 256-byte row pieces
-template <bool GNB>
-__device__ __forceinline__ void f16x2_gen_epilogue(const WgemmArgs& a, const f32x16 (&acc)[4], const float inv, const int rbase, const int nb, float* St, const int lane) {
-  constexpr int SP = 68;
-  const int rr = lane >> 4, c4 = (lane & 15) * 4;
-  if constexpr (!GNB) {
-    const long long ldc = a.ldC;
-    float* Mrow = a.M + (long long)rbase * ldc + nb * WBN;
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb) {
-#pragma unroll
-      for (int cl = 0; cl < 2; ++cl)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *reinterpret_cast<float4*>(St + (lane & 31) * SP + cl * 32 + 8 * g + 4 * (lane >> 5)) =
-              make_float4(acc[2 * hb + cl][4 * g] * inv, acc[2 * hb + cl][4 * g + 1] * inv, acc[2 * hb + cl][4 * g + 2] * inv, acc[2 * hb + cl][4 * g + 3] * inv);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      float4 bs = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (a.bias_n) bs = *reinterpret_cast<const float4*>(a.bias_n + nb * WBN + hb * 64 + c4);
-      float4 pv[8];
-#pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const int r = min(4 * it + rr, a.Mt - 1 - rbase);
-        pv[it] = a.accumulate ? *reinterpret_cast<const float4*>(Mrow + (long long)r * ldc + hb * 64 + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const int r = 4 * it + rr;
-        float4 v = *reinterpret_cast<const float4*>(St + r * SP + c4);
-        v.x *= a.alpha; v.y *= a.alpha; v.z *= a.alpha; v.w *= a.alpha;
-        if (a.bias_n) { v.x += bs.x; v.y += bs.y; v.z += bs.z; v.w += bs.w; }
-        if (a.accumulate) { v.x += pv[it].x; v.y += pv[it].y; v.z += pv[it].z; v.w += pv[it].w; }
-        if (rbase + r < a.Mt) *reinterpret_cast<float4*>(Mrow + (long long)r * ldc + hb * 64 + c4) = v;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-    }
-  } else {
-    const int cpg = a.Cout / a.gG;
-    const bool second = a.gxv.p1 != nullptr && nb * WBN >= a.gxv.C0, dsecond = a.gd.p1 != nullptr && nb * WBN >= a.gd.C0;
-    const long long ldx = second ? a.gxv.ld1 : a.gxv.ld0, ldo = dsecond ? a.gd.ld1 : a.gd.ld0;
-    const bool accd = (dsecond ? a.gd.acc1 : a.gd.acc0) != 0;
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb) {
-      const int col = nb * WBN + hb * 64 + c4, grp = col / cpg;
-      const float* xs = (second ? a.gxv.p1 + (col - a.gxv.C0) : a.gxv.p0 + col);
-      float* o = (dsecond ? a.gd.p1 + (col - a.gd.C0) : a.gd.p0 + col);
-      const float* das = a.gda + col;
-      const float4 gm = *reinterpret_cast<const float4*>(a.ggamma + col), bt = *reinterpret_cast<const float4*>(a.gbeta + col);
-      const float g4[4] = {gm.x, gm.y, gm.z, gm.w}, b4[4] = {bt.x, bt.y, bt.z, bt.w};
-#pragma unroll
-      for (int cl = 0; cl < 2; ++cl)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *reinterpret_cast<float4*>(St + (lane & 31) * SP + cl * 32 + 8 * g + 4 * (lane >> 5)) =
-              make_float4(acc[2 * hb + cl][4 * g] * inv, acc[2 * hb + cl][4 * g + 1] * inv, acc[2 * hb + cl][4 * g + 2] * inv, acc[2 * hb + cl][4 * g + 3] * inv);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int bt4 = 0; bt4 < 2; ++bt4) {
-        float4 xv[4], dv[4], pv[4];
-        float mean[4], rstd[4], m1[4], m2[4];
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-          const int r = min(rbase + 16 * bt4 + 4 * it + rr, a.Mt - 1), bb = r / a.gHW;
-          if (a.gnt) { xv[it] = ld4nt_g(xs + (long long)r * ldx); dv[it] = ld4nt_g(das + (long long)r * a.Cout); }
-          else { xv[it] = *reinterpret_cast<const float4*>(xs + (long long)r * ldx); dv[it] = *reinterpret_cast<const float4*>(das + (long long)r * a.Cout); }
-          pv[it] = accd ? *reinterpret_cast<const float4*>(o + (long long)r * ldo) : make_float4(0.f, 0.f, 0.f, 0.f);
-          const float2 sm = *reinterpret_cast<const float2*>(a.gstats + ((long long)bb * a.gG + grp) * 2), rm = *reinterpret_cast<const float2*>(a.gred + ((long long)bb * a.gG + grp) * 2);
-          mean[it] = sm.x; rstd[it] = sm.y; m1[it] = rm.x; m2[it] = rm.y;
-        }
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-          const int rl = 16 * bt4 + 4 * it + rr;
-          const float4 cv = *reinterpret_cast<const float4*>(St + rl * SP + c4);
-          const float x4[4] = {xv[it].x, xv[it].y, xv[it].z, xv[it].w}, d4[4] = {dv[it].x, dv[it].y, dv[it].z, dv[it].w};
-          const float p4[4] = {pv[it].x, pv[it].y, pv[it].z, pv[it].w}, c4v[4] = {cv.x, cv.y, cv.z, cv.w};
-          float r[4];
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float xh = (x4[j] - mean[it]) * rstd[it];
-            const float z = xh * g4[j] + b4[j];
-            const float dxh = d4[j] * (a.gsilu ? dsilu_g(z) : 1.f) * g4[j];
-            r[j] = rstd[it] * (dxh - m1[it] - xh * m2[it]);
-            r[j] += a.alpha * c4v[j];
-            r[j] += p4[j];
-          }
-          if (rbase + rl < a.Mt) *reinterpret_cast<float4*>(o + (long long)(rbase + rl) * ldo) = make_float4(r[0], r[1], r[2], r[3]);
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
-}
 
 // A 32-row tile's pointers into the two-source A: lane (row r = lane & 31, half h = lane >> 5) reads 16 consecutive floats per K-stage, channels >= C0
 // from the second source; rows past M are clamped (never stored)
@@ -772,12 +653,12 @@ __global__ __launch_bounds__(WNT, CB == 1 ? 3 : 2) void wgemm_f16x2_gen_kernel(c
   stage(s, ra[0], std::true_type{}, std::false_type{});
   stage(s + 1, ra[1], std::false_type{}, std::false_type{});
   const float inv = __uint_as_float((unsigned)(ecur - 12) << 23) * a.uinv[0];
-  float* St = reinterpret_cast<float*>(smem) + wid * (32 * 68);
+  float* St = reinterpret_cast<float*>(smem) + wid * (SLAB_BYTES / 4);
   // CB = 1 outside the loop: as the body of a one-trip loop its GNB epilogue compiles to 168 VGPRs and 29 spills instead of 162 and none
-  if constexpr (CB == 1) f16x2_gen_epilogue<GNB>(a, acc[0], inv, m0 + wid * 32, np, St, lane);
+  if constexpr (CB == 1) wgemm_gen_epilogue<GNB, true>(a, acc[0], inv, m0 + wid * 32, np, St, lane);
   else {
 #pragma unroll
-    for (int t = 0; t < CB; ++t) f16x2_gen_epilogue<GNB>(a, acc[t], inv, m0 + wid * 32, CB * np + t, St, lane);
+    for (int t = 0; t < CB; ++t) wgemm_gen_epilogue<GNB, true>(a, acc[t], inv, m0 + wid * 32, CB * np + t, St, lane);
   }
 }
 
@@ -850,7 +731,7 @@ __global__ __launch_bounds__(WNT, 2) void wgemm_f16x2_gen64_kernel(const WgemmAr
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     const float inv = __uint_as_float((unsigned)(ecur[t] - 12) << 23) * a.uinv[0];
-    f16x2_gen_epilogue<GNB>(a, acc[t], inv, m0 + wid * 64 + t * 32, nb, reinterpret_cast<float*>(smem) + wid * (32 * 68), lane);
+    wgemm_gen_epilogue<GNB, true>(a, acc[t], inv, m0 + wid * 64 + t * 32, nb, reinterpret_cast<float*>(smem) + wid * (SLAB_BYTES / 4), lane);
   }
 }
 
@@ -876,19 +757,13 @@ __global__ __launch_bounds__(WNT, 2) void wgemm_f16x2_rt2_kernel(const WgemmArgs
   float sv[2], inv[2];
   unsigned aoff[2];
   {
-    const int r0 = min(m0 + wid * 64, a.Mt - 1), r1 = min(m0 + wid * 64 + 63, a.Mt - 1), b0 = r0 / a.tpu, b1 = r1 / a.tpu;     // tpu >= 64: at most two utterances
-    unsigned mb0 = __hip_atomic_load(a.vmax + ((long long)b0 * VMAX_SUB + lane) * VMAX_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    for (int o = 32; o > 0; o >>= 1) mb0 = max(mb0, (unsigned)__shfl_xor((int)mb0, o));
-    unsigned mb1 = mb0;
-    if (b1 != b0) {
-      mb1 = __hip_atomic_load(a.vmax + ((long long)b1 * VMAX_SUB + lane) * VMAX_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      for (int o = 32; o > 0; o >>= 1) mb1 = max(mb1, (unsigned)__shfl_xor((int)mb1, o));
-    }
+    unsigned mb[2];                                            // tpu >= 64: at most two utterances
+    const int b0 = f16x2_utt_absmax(a.vmax, a.tpu, min(m0 + wid * 64, a.Mt - 1), min(m0 + wid * 64 + 63, a.Mt - 1), lane, mb);
     const float ui = a.uinv[p];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       row[t] = min(m0 + wid * 64 + t * 32 + (lane & 31), a.Mt - 1);
-      pow2_scale(row[t] / a.tpu == b0 ? mb0 : mb1, sv[t], inv[t]);
+      pow2_scale(row[t] / a.tpu == b0 ? mb[0] : mb[1], sv[t], inv[t]);
       inv[t] *= ui;
       aoff[t] = (unsigned)(((long long)row[t] * a.Cin + 16 * (lane >> 5)) * 4);
     }
@@ -936,33 +811,11 @@ __global__ __launch_bounds__(WNT, 2) void wgemm_f16x2_rt2_kernel(const WgemmArgs
   for (; s + 1 < S; ++s) stage(s, std::true_type{});
   stage(s, std::false_type{});
 
-  constexpr int SP = 68;
-  float* St = reinterpret_cast<float*>(smem) + wid * (32 * SP);
-  const int rr = lane >> 4, c4 = (lane & 15) * 4;
+  float* St = reinterpret_cast<float*>(smem) + wid * (SLAB_BYTES / 4);
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     const int rb = m0 + wid * 64 + t * 32;
-    float* Mrow = a.M + (long long)p * a.sM + (long long)rb * a.Cout + nb * WBN;
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb) {
-#pragma unroll
-      for (int cl = 0; cl < 2; ++cl)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *reinterpret_cast<float4*>(St + (lane & 31) * SP + cl * 32 + 8 * g + 4 * (lane >> 5)) =
-              make_float4(acc[t][2 * hb + cl][4 * g] * inv[t], acc[t][2 * hb + cl][4 * g + 1] * inv[t], acc[t][2 * hb + cl][4 * g + 2] * inv[t],
-                          acc[t][2 * hb + cl][4 * g + 3] * inv[t]);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const int r = 4 * it + rr;
-        const float4 v = *reinterpret_cast<const float4*>(St + r * SP + c4);
-        if (rb + r < a.Mt) *reinterpret_cast<float4*>(Mrow + (long long)r * a.Cout + hb * 64 + c4) = v;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-    }
+    slab_store<true>(acc[t], inv[t], St, a.M + (long long)p * a.sM + (long long)rb * a.Cout + nb * WBN, a.Cout, a.Mt - rb, lane);
   }
 }
 
@@ -1052,20 +905,20 @@ void launch_wgemm_bf16x3(const float* V, const void* U3, float* M, long long Mt,
   a.V = V; a.U3 = reinterpret_cast<const unsigned char*>(U3); a.M = M;
   a.Mt = (int)Mt; a.Cin = Cin; a.Cout = Cout; a.S = Cin / WKS; a.NB = Cout / WBN;
   a.sV = Mt * Cin; a.sM = Mt * Cout;
-  const int gx = cdiv((int)Mt, WBM) * a.NB;
-  const bool fold = P % 8 == 0 && (long long)gx * P < (1LL << 31);     // positions folded into a 1-D grid, one XCD per position (see the kernel)
-  a.pz = fold ? P : 0; a.gx = gx;
-  const dim3 grid(fold ? (unsigned)(gx * P) : (unsigned)gx, 1, fold ? 1u : (unsigned)P);
+  const dim3 grid = xcd_batched_grid(a, cdiv((int)Mt, WBM) * a.NB, P);    // positions folded into a 1-D grid, one XCD per position (see the kernel)
   hipLaunchKernelGGL((wgemm_bf16x3_kernel<false>), grid, dim3(WNT), 0, st, a);
 }
 
 // f16x2 form
+void launch_wgemm_umax(const float* U_dev, unsigned* umax, int P, long long per, hipStream_t st) {
+  (void)hipMemsetAsync(umax, 0, 256, st);
+  hipLaunchKernelGGL(wgemm_umax_kernel, dim3(16, (unsigned)P), dim3(256), 0, st, U_dev, umax, per);
+}
 // image = P * Cout * Cin * 4 bytes of stage images + 256 bytes (the positions' inverse scales, floats) + 256 bytes (their abs-max bit patterns); P <= 64
 size_t wgemm_f16x2_packed_bytes(int P, int Cout, int Cin) { return (size_t)P * Cout * Cin * 4 + 512; }
 void wgemm_f16x2_pack_weights(const float* U_dev, void* U2_dev, int P, int Cout, int Cin, hipStream_t st) {
   unsigned* umax_scratch = reinterpret_cast<unsigned*>(reinterpret_cast<unsigned char*>(U2_dev) + (size_t)P * Cout * Cin * 4 + 256);
-  (void)hipMemsetAsync(umax_scratch, 0, 256, st);
-  hipLaunchKernelGGL(wgemm_umax_kernel, dim3(16, (unsigned)P), dim3(256), 0, st, U_dev, umax_scratch, (long long)Cout * Cin);
+  launch_wgemm_umax(U_dev, umax_scratch, P, (long long)Cout * Cin, st);
   const long long n16 = (long long)P * Cout * Cin * 4 / 16;
   hipLaunchKernelGGL(wgemm_pack2_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, st, U_dev, reinterpret_cast<u32x4*>(U2_dev), umax_scratch, P, Cout, Cin);
 }
@@ -1097,10 +950,7 @@ void launch_wgemm_f16x2(const float* V, const void* U2, float* M, long long Mt, 
   // wgemm_rt 1 = the 32-row kernel
   const bool cb2 = wgemm_colpair(Mt, a.NB);
   const bool rt2 = !cb2 && tiles_per_utt >= 64 && cur_opt().wgemm_rt != 1;
-  const int gx = cb2 ? cdiv((int)Mt, WBM) * ((a.NB + 1) / 2) : cdiv((int)Mt, rt2 ? 2 * WBM : WBM) * a.NB;
-  const bool fold = P % 8 == 0 && (long long)gx * P < (1LL << 31);
-  a.pz = fold ? P : 0; a.gx = gx;
-  const dim3 grid(fold ? (unsigned)(gx * P) : (unsigned)gx, 1, fold ? 1u : (unsigned)P);
+  const dim3 grid = xcd_batched_grid(a, cb2 ? cdiv((int)Mt, WBM) * ((a.NB + 1) / 2) : cdiv((int)Mt, rt2 ? 2 * WBM : WBM) * a.NB, P);
   if (cb2) hipLaunchKernelGGL(wgemm_f16x2_kernel<2>, grid, dim3(WNT), 0, st, a);
   else if (rt2) hipLaunchKernelGGL(wgemm_f16x2_rt2_kernel, grid, dim3(WNT), 0, st, a);
   else hipLaunchKernelGGL(wgemm_f16x2_kernel<1>, grid, dim3(WNT), 0, st, a);

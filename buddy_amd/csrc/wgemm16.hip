@@ -8,56 +8,27 @@
 //
 // Structure = wgemm_f16x2_rt2_kernel (wgemm.hip): workgroup = 4 waves x 64 rows (two 32-row tiles per wave) x all 128 columns of one column block,
 // two workgroups per CU, XCD x owns positions x mod 8, the weights' stage image goes global -> LDS by LDS-DMA (double-buffered, one barrier per
-// K-stage), the accumulator tile leaves through a wave-private LDS slab in 256-byte row pieces.  Differences: a K-stage (32 k) of V is 32 bytes per lane
+// K-stage), the accumulator tile leaves through a wave-private LDS slab in 256-byte row pieces (those pieces: wgemm_tile.h).  Differences: a K-stage (32 k) of V is 32 bytes per lane
 // and row (2 x 16 B of f16 instead of 4 x 16 B of fp32), the weight stage 8 KB; the A operand needs no split: a stage's rows are copied aside and the
 // registers reloaded in place for stage s + 1 while stage s multiplies.  A 64-k stage (one barrier
 // per 32 instead of 16 MFMAs per wave) needs 64 more VGPRs than two workgroups per CU leave: it spilled.
-#include "common.h"
+#include "wgemm_tile.h"
 #include <cstdint>
 #include <type_traits>
 
 namespace buddy {
 namespace {
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int BM = 128, BN = 128, KS = 32, NT = 256;
 constexpr int STAGE_BYTES = BN * KS * 2;                      // 8 KB: 2 k-chunks x 4 column blocks x 1 KB
-constexpr int FRAG = 1024;                                    // one (k chunk, column block) fragment block: 64 lanes x 16 B
 
-// LDS-DMA of 16 bytes per lane (as wgemm.hip): source = uniform 64-bit base + 32-bit per-lane byte offset, LDS destination = M0 + 16 * lane
-__device__ __forceinline__ void glds16(const void* sbase, unsigned voff, unsigned lds_addr) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_addr) : "memory");
-}
-__device__ __forceinline__ const void* uniform_ptr(const void* p) {
-  const unsigned long long v = (unsigned long long)p;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return (const void*)(((unsigned long long)hi << 32) | lo);
-}
-
-// abs-max of every position's weight matrix -> umax[p] (float bits); grid (chunks, P), umax zeroed before
-__global__ __launch_bounds__(256) void wgemm16_umax_kernel(const float* __restrict__ U, unsigned* __restrict__ umax, long long per) {
-  const float* u = U + (long long)blockIdx.y * per;
-  float m = 0.f;
-  for (long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; i < per; i += (long long)gridDim.x * 1024) {
-    const float4 v = *reinterpret_cast<const float4*>(u + i);
-    m = fmaxf(fmaxf(m, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-  }
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((threadIdx.x & 63) == 0) atomicMax(umax + blockIdx.y, __float_as_uint(m));
-}
 // U fp32 [P][Cout][Cin] -> stage images [P][Cout/128][Cin/32][2 k chunks][4 column blocks][64 lanes] x 16 B (lane: column n = nb * 128 + cb * 32 + lane % 32,
 // k = s * 32 + 16 * (lane / 32) + 8 * kc + 0..7), then P inverse scales (floats); one thread per 16-byte element.  The power of two takes the position's
-// abs-max into [2^14, 2^15) (exponent field clamped to [15, 253], as the f16x2 image)
+// abs-max into [2^14, 2^15) (pow2_scale, wgemm_tile.h: as the f16x2 image)
 __global__ __launch_bounds__(256) void wgemm16_pack_kernel(const float* __restrict__ U, u32x4* __restrict__ out, const unsigned* __restrict__ umax, int P, int Cout,
                                                            int Cin) {
   const long long n16 = (long long)P * Cout * Cin * 2 / 16;
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  auto expo = [&](int p) { const int e = (int)((umax[p] >> 23) & 0xFF); return e < 15 ? 15 : (e > 253 ? 253 : e); };
-  if (i < P) reinterpret_cast<float*>(out + n16)[i] = __uint_as_float((unsigned)(expo((int)i) - 14) << 23);
+  if (i < P) { float s, inv; pow2_scale(umax[i], s, inv); reinterpret_cast<float*>(out + n16)[i] = inv; }
   if (i >= n16) return;
   const int lane = (int)(i & 63);
   long long r = i >> 6;
@@ -69,7 +40,7 @@ __global__ __launch_bounds__(256) void wgemm16_pack_kernel(const float* __restri
   const int p = (int)r;
   const int n = nb * BN + cb * 32 + (lane & 31), k = s * KS + 16 * (lane >> 5) + 8 * kc;
   const float* src = U + ((long long)p * Cout + n) * Cin + k;
-  const float sc = __uint_as_float((unsigned)(268 - expo(p)) << 23);
+  float sc, inv; pow2_scale(umax[p], sc, inv);
   f16x8 h;
 #pragma unroll
   for (int j = 0; j < 8; ++j) h[j] = (_Float16)(src[j] * sc);
@@ -84,7 +55,7 @@ struct Args {
 };
 
 __global__ __launch_bounds__(NT, 2) void wgemm_f16_kernel(const Args a) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[(2 * STAGE_BYTES > 4 * 32 * 68 * 4) ? 2 * STAGE_BYTES : 4 * 32 * 68 * 4];
+  __shared__ __attribute__((aligned(16))) unsigned char smem[(2 * STAGE_BYTES > 4 * SLAB_BYTES) ? 2 * STAGE_BYTES : 4 * SLAB_BYTES];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   int lid, p;
   xcd_tile_position(a.pz, a.gx, lid, p);
@@ -160,33 +131,11 @@ __global__ __launch_bounds__(NT, 2) void wgemm_f16_kernel(const Args a) {
   for (; s + 1 < S; ++s) stage(s, std::true_type{});
   stage(s, std::false_type{});
 
-  constexpr int SP = 68;
-  float* St = reinterpret_cast<float*>(smem) + wid * (32 * SP);
-  const int rr = lane >> 4, c4 = (lane & 15) * 4;
+  float* St = reinterpret_cast<float*>(smem) + wid * (SLAB_BYTES / 4);
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     const int rb = m0 + wid * 64 + t * 32;
-    float* Mrow = a.M + (long long)p * a.sM + (long long)rb * a.Cout + nb * BN;
-#pragma unroll
-    for (int hb = 0; hb < 2; ++hb) {
-#pragma unroll
-      for (int cl = 0; cl < 2; ++cl)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *reinterpret_cast<float4*>(St + (lane & 31) * SP + cl * 32 + 8 * g + 4 * (lane >> 5)) =
-              make_float4(acc[t][2 * hb + cl][4 * g] * inv[t], acc[t][2 * hb + cl][4 * g + 1] * inv[t], acc[t][2 * hb + cl][4 * g + 2] * inv[t],
-                          acc[t][2 * hb + cl][4 * g + 3] * inv[t]);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int it = 0; it < 8; ++it) {
-        const int r = 4 * it + rr;
-        const float4 v = *reinterpret_cast<const float4*>(St + r * SP + c4);
-        if (rb + r < a.Mt) *reinterpret_cast<float4*>(Mrow + (long long)r * a.Cout + hb * 64 + c4) = v;
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-    }
+    slab_store<true>(acc[t], inv[t], St, a.M + (long long)p * a.sM + (long long)rb * a.Cout + nb * BN, a.Cout, a.Mt - rb, lane);
   }
 }
 }  // namespace
@@ -196,8 +145,7 @@ bool wgemm_f16_supported(int Cout, int Cin) { return Cout % BN == 0 && Cin % KS 
 size_t wgemm_f16_packed_bytes(int P, int Cout, int Cin) { return (size_t)P * Cout * Cin * 2 + 512; }
 void wgemm_f16_pack_weights(const float* U_dev, void* U1_dev, int P, int Cout, int Cin, hipStream_t st) {
   unsigned* umax_scratch = reinterpret_cast<unsigned*>(reinterpret_cast<unsigned char*>(U1_dev) + (size_t)P * Cout * Cin * 2 + 256);
-  (void)hipMemsetAsync(umax_scratch, 0, 256, st);
-  hipLaunchKernelGGL(wgemm16_umax_kernel, dim3(16, (unsigned)P), dim3(256), 0, st, U_dev, umax_scratch, (long long)Cout * Cin);
+  launch_wgemm_umax(U_dev, umax_scratch, P, (long long)Cout * Cin, st);
   const long long n16 = (long long)P * Cout * Cin * 2 / 16;
   hipLaunchKernelGGL(wgemm16_pack_kernel, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, st, U_dev, reinterpret_cast<u32x4*>(U1_dev), umax_scratch, P, Cout, Cin);
 }
@@ -207,10 +155,7 @@ void launch_wgemm_f16(const void* V16, const signed char* vexp, const void* U1, 
   a.uinv = reinterpret_cast<const float*>(a.U1 + (size_t)P * Cout * Cin * 2);
   a.Mt = (int)Mt; a.Cin = Cin; a.Cout = Cout; a.S = Cin / KS; a.NB = Cout / BN;
   a.sV = Mt * Cin; a.sM = Mt * Cout;
-  const int gx = (int)((Mt + 2 * BM - 1) / (2 * BM)) * a.NB;
-  const bool fold = P % 8 == 0 && (long long)gx * P < (1LL << 31);
-  a.pz = fold ? P : 0; a.gx = gx;
-  const dim3 grid(fold ? (unsigned)(gx * P) : (unsigned)gx, 1, fold ? 1u : (unsigned)P);
+  const dim3 grid = xcd_batched_grid(a, cdiv(Mt, 2 * BM) * a.NB, P);
   hipLaunchKernelGGL(wgemm_f16_kernel, grid, dim3(NT), 0, st, a);
 }
 

@@ -79,7 +79,8 @@ def test_winograd_domain_gemm_bf16x3(lib, tiles, Cout, Cin, P_):
     assert lib.buddy_wgemm_packed_bytes(2, 96, 128) == 0 and lib.buddy_wgemm_packed_bytes(2, 128, 48) == 0
 
 
-@pytest.mark.parametrize("utts,tpu,Cout,Cin,P_", [(3, 100, 128, 128, 3), (2, 500, 256, 384, 2), (1, 129, 256, 64, 5), (4, 1024, 128, 512, 2)])
+@pytest.mark.parametrize("utts,tpu,Cout,Cin,P_", [(3, 100, 128, 128, 3), (2, 500, 256, 384, 2), (1, 129, 256, 64, 5), (4, 1024, 128, 512, 2),
+                                                   (3, 40, 128, 64, 2)])     # 120 rows: a ragged last tile, a wave on two utterances, the 32-row kernel by the rule
 def test_winograd_domain_gemm_f16x2(lib, utts, tpu, Cout, Cin, P_):
     """buddy_gemm_winograd_domain_f16x2 (two-way f16 split of power-of-two-scaled operands, three f16 MFMA products, fp32 accumulate; csrc/wgemm.hip)
     against fp64.  The operands are good to 2^-22, so the bound is 4x the bf16x3 / fp32 kernels' (8e-5 of the abs-max; measured beside them); utterances of

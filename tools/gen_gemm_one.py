@@ -2,9 +2,9 @@
 enough buffers that no launch finds its A rows in the Infinity Cache.  Prints ms and algorithmic GB/s (A read once + C written once) per shape.
 usage: [BUDDY_GEN_ROWS=32|64] python tools/gen_gemm_one.py [out.json]
        [BUDDY_GEN_ROWS=64 | BUDDY_GEN_CP=2] python tools/gen_gemm_one.py --digest
---digest: SHA-256 of what buddy_gemm_f16x2 and buddy_gemm_f16x2_gn_bwd write for seeded inputs at three small shapes that select the three tilings (two-source
-A, bias, accumulate; two-source x / two-destination dx), to compare two builds bit for bit.  Run it in fresh processes under the defaults, BUDDY_GEN_ROWS=64 and
-BUDDY_GEN_CP=2, so that the small M also passes through the large forms."""
+--digest: SHA-256 of what buddy_gemm_f16x2 / buddy_gemm_f16x2_gn_bwd and buddy_gemm_bf16x3 / buddy_gemm_bf16x3_gn_bwd write for seeded inputs at three small
+shapes that select the three f16x2 tilings (two-source A, bias, accumulate; two-source x / two-destination dx), to compare two builds bit for bit.  Run it in
+fresh processes under the defaults, BUDDY_GEN_ROWS=64 and BUDDY_GEN_CP=2, so that the small M also passes through the large forms."""
 import hashlib
 import json
 import os
@@ -71,21 +71,22 @@ def digest():
         rnd = lambda *shape: torch.randn(*shape, generator=g)
         A = (rnd(M, K) * torch.logspace(-3, 3, M)[:, None]).cuda()                      # rows six decades apart: the running row scale moves
         W, bias, prev = rnd(N, K).cuda(), rnd(N).cuda(), rnd(M, N).cuda()
-        W2 = pack(W, "f16x2")
         A0, A1 = A[:, :C0].contiguous(), A[:, C0:].contiguous()
-        Cc = prev.clone()
-        _lib.check(lib.buddy_gemm_f16x2(P(A0), C0, P(A1), K - C0, C0, W2.data_ptr(), P(Cc), N, M, N, K, P(bias), 0.5, 1, S()))
         x, da, gamma, beta = (rnd(B, HW, N) * 1.5 + 0.3).cuda(), rnd(B, HW, N).cuda(), (1 + 0.2 * rnd(N)).cuda(), (0.2 * rnd(N)).cuda()
         xg = x.double().reshape(B, HW, G, N // G)
         stats = torch.stack([xg.mean(dim=(1, 3)), 1.0 / torch.sqrt(xg.var(dim=(1, 3), unbiased=False) + 1e-6)], dim=-1).float().contiguous()
         X0 = N // 2 if N > 128 else 0                                                   # the x / dx split (a multiple of 128)
         x0, x1 = (x[..., :X0].contiguous(), x[..., X0:].contiguous()) if X0 else (x, None)
-        d0, d1 = torch.zeros_like(x0), (prev.reshape(B, HW, N)[..., X0:].contiguous() if X0 else None)
         scratch, red = torch.empty(B * 256 * N * 2, dtype=torch.float64, device="cuda"), torch.empty(B, G, 2, device="cuda")
-        _lib.check(lib.buddy_gemm_f16x2_gn_bwd(P(A), K, W2.data_ptr(), P(x0), P(x1) if X0 else None, X0, P(da), P(stats), P(gamma), P(beta), G, 1, 0.70710678,
-                                               P(d0), P(d1) if X0 else None, 0, 1 if X0 else 0, scratch.data_ptr(), P(red), B, HW, N, K, S()))
-        torch.cuda.synchronize()
-        print(f"M={M} N={N} K={K} gemm_f16x2 {sha(Cc)} gn_bwd {sha(d0, d1) if X0 else sha(d0)}", flush=True)
+        for arith, gemm, gn_bwd in (("f16x2", lib.buddy_gemm_f16x2, lib.buddy_gemm_f16x2_gn_bwd), ("bf16x3", lib.buddy_gemm_bf16x3, lib.buddy_gemm_bf16x3_gn_bwd)):
+            Wp = pack(W, arith)
+            Cc = prev.clone()
+            _lib.check(gemm(P(A0), C0, P(A1), K - C0, C0, Wp.data_ptr(), P(Cc), N, M, N, K, P(bias), 0.5, 1, S()))
+            d0, d1 = torch.zeros_like(x0), (prev.reshape(B, HW, N)[..., X0:].contiguous() if X0 else None)
+            _lib.check(gn_bwd(P(A), K, Wp.data_ptr(), P(x0), P(x1) if X0 else None, X0, P(da), P(stats), P(gamma), P(beta), G, 1, 0.70710678,
+                              P(d0), P(d1) if X0 else None, 0, 1 if X0 else 0, scratch.data_ptr(), P(red), B, HW, N, K, S()))
+            torch.cuda.synchronize()
+            print(f"M={M} N={N} K={K} gemm_{arith} {sha(Cc)} gn_bwd {sha(d0, d1) if X0 else sha(d0)}", flush=True)
 
 
 if __name__ == "__main__":

@@ -1,16 +1,21 @@
 """ONE shape of the Winograd-domain batched GEMM (csrc/wgemm.hip), a few launches (for rocprofv3 --pmc passes and kernel experiments).
 usage: python tools/wgemm_one.py Mt N K [positions] [reps] [bf16x3|f16x2] [form]   (f16x2: Mt = 8 utterances x Mt / 8 tiles)
        python tools/wgemm_one.py --table form [out.json]
+       python tools/wgemm_one.py --digest bf16x3|f16|form
 form (f16x2 only; sets the process defaults before the library reads them): rt2 = one column block per workgroup (BUDDY_WGEMM_CB=1: wgemm_f16x2_rt2_kernel
 from 64 tiles per utterance on), cb2 = two column blocks per workgroup wherever Cout >= 256 (BUDDY_WGEMM_CB=2: wgemm_f16x2_kernel<2>), rt1 = the 32-row
 one-block kernel (BUDDY_WGEMM_RT=1), rule = the library's own choice.
 --table: every distinct shape with Cout >= 256 among the batched GEMMs of one bench.py step (B = 8 x 64 000, nf = 128), 64 positions, each IN ISOLATION:
 operands rotated through enough buffers that no launch finds its V rows in the Infinity Cache, HIP-event time per launch.  One form per process; run the
-forms alternating."""
-import json, os, sys, time
+forms alternating.
+--digest: SHA-256 of what buddy_gemm_winograd_domain_bf16x3, _f16 or _f16x2 (in the given form) writes for seeded inputs at small shapes that reach every edge
+of the store -- 129 and 300 rows (no multiple of 32 or 64), 43 tiles per utterance (the 32-row kernel under the defaults) and 100 (an utterance boundary inside a
+wave), Cout 128 / 256 / 384, Cin 64 / 192, 5 positions (one per blockIdx.z) and 8 (folded) -- to compare two builds bit for bit."""
+import hashlib, json, os, sys, time
 FORMS = {"rt2": {"BUDDY_WGEMM_CB": "1"}, "cb2": {"BUDDY_WGEMM_CB": "2"}, "rt1": {"BUDDY_WGEMM_RT": "1"}, "rule": {}}
 table = len(sys.argv) > 1 and sys.argv[1] == "--table"
-form = sys.argv[2] if table else (sys.argv[7] if len(sys.argv) > 7 else "rule")
+digest = len(sys.argv) > 2 and sys.argv[1] == "--digest"
+form = sys.argv[2] if table or (digest and sys.argv[2] in FORMS) else (sys.argv[7] if len(sys.argv) > 7 else "rule")
 os.environ.update(FORMS[form])
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -23,12 +28,41 @@ SHAPES = [(29584, 256, 256, 2), (29584, 256, 128, 1), (29584, 384, 128, 1), (756
           (1520, 1024, 256, 1), (1520, 256, 1024, 1), (528, 256, 256, 20), (528, 256, 512, 2), (528, 512, 256, 2), (400, 1024, 256, 1), (400, 256, 1024, 1)]
 
 
-def f16x2_setup(A, Bt, Mt, N, K, nb):
+def f16x2_setup(A, Bt, Mt, N, K, nb, utts=8):
     U2 = torch.empty(int(lib.buddy_wgemm_f16x2_packed_bytes(nb, N, K)) // 4, dtype=torch.int32, device="cuda")
     _lib.check(lib.buddy_wgemm_f16x2_pack_weights(P(Bt), U2.data_ptr(), nb, N, K, S()))
-    vmax = torch.empty(8, 64, 32, dtype=torch.int32, device="cuda")
-    _lib.check(lib.buddy_abs_max_bits(P(A), nb, 8, (Mt // 8) * K, vmax.data_ptr(), S()))
+    vmax = torch.empty(utts, 64, 32, dtype=torch.int32, device="cuda")
+    _lib.check(lib.buddy_abs_max_bits(P(A), nb, utts, (Mt // utts) * K, vmax.data_ptr(), S()))
     return U2, vmax
+
+
+if digest:
+    arith = "f16x2" if sys.argv[2] in FORMS else sys.argv[2]
+    for utts, tpu, N, K, nb in [(3, 43, 128, 64, 5), (3, 43, 256, 192, 8), (3, 43, 384, 192, 5), (3, 100, 128, 192, 8), (3, 100, 256, 192, 5), (3, 100, 384, 64, 8)]:
+        Mt = utts * tpu
+        g = torch.Generator(device="cpu").manual_seed(1000 * Mt + N + K + nb)
+        level = torch.tensor([1.0, 3e-4, 2e3]).repeat_interleave(tpu)[None, :, None]      # per-utterance (f16x2) and per-tile (f16) scales that differ
+        Vh = torch.randn(nb, Mt, K, generator=g) * torch.exp(2.0 * torch.randn(1, Mt, 1, generator=g)) * level
+        A, Bt = Vh.cuda(), (torch.randn(nb, N, K, generator=g) * torch.exp(torch.randn(nb, 1, 1, generator=g))).cuda()
+        Cm = torch.full((nb, Mt, N), 7.0, device="cuda")
+        if arith == "bf16x3":
+            U3 = torch.empty(nb * N * K * 6 // 4, dtype=torch.int32, device="cuda")
+            _lib.check(lib.buddy_wgemm_pack_weights(P(Bt), U3.data_ptr(), nb, N, K, S()))
+            _lib.check(lib.buddy_gemm_winograd_domain_bf16x3(P(A), U3.data_ptr(), P(Cm), Mt, N, K, nb, S()))
+        elif arith == "f16":                                      # the operand format of include/buddy_hip.h (buddy_gemm_winograd_domain_f16)
+            e = 141 - ((Vh.abs().amax(dim=(0, 2)).view(torch.int32) >> 23) & 0xFF).clamp(15, 253)
+            V16 = (Vh.double() * torch.pow(2.0, e.double())[None, :, None]).half().cuda()
+            vexp = e.to(torch.int8).cuda()
+            U1 = torch.empty(int(lib.buddy_wgemm_f16_packed_bytes(nb, N, K)), dtype=torch.uint8, device="cuda")
+            _lib.check(lib.buddy_wgemm_f16_pack_weights(P(Bt), U1.data_ptr(), nb, N, K, S()))
+            _lib.check(lib.buddy_gemm_winograd_domain_f16(V16.data_ptr(), vexp.data_ptr(), U1.data_ptr(), P(Cm), Mt, N, K, nb, S()))
+        else:
+            U2, vmax = f16x2_setup(A, Bt, Mt, N, K, nb, utts)
+            _lib.check(lib.buddy_gemm_winograd_domain_f16x2(P(A), U2.data_ptr(), P(Cm), Mt, N, K, nb, vmax.data_ptr(), tpu, S()))
+        torch.cuda.synchronize()
+        print(f"wgemm {arith} {form if arith == 'f16x2' else '-'} utts={utts} tiles/utt={tpu} Cout={N} Cin={K} P={nb}: "
+              f"{hashlib.sha256(Cm.cpu().numpy().tobytes()).hexdigest()}", flush=True)
+    sys.exit(0)
 
 
 if table:
