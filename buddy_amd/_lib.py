@@ -65,6 +65,7 @@ _SIGS = {
     "buddy_wpe": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "buddy_wpe_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int]),
     "buddy_wpe_dereverb": (C.c_int, [_f32p, _f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "buddy_resample": (C.c_int, [_f32p, C.c_int, C.c_longlong, _f32p, C.c_int, C.c_int, C.c_int, _f32p, C.c_longlong, C.c_void_p]),
     "buddy_prof_collect_wino4": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                            C.POINTER(C.c_longlong)]),
     "buddy_prof_collect_hbm": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),

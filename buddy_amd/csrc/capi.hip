@@ -638,6 +638,23 @@ int buddy_fir(const float* x, const float* h, long long h_stride, float* y, int 
 }
 
 
+// ---- rational polyphase resampler (resample.hip) ----
+int buddy_resample(const float* x, int B, long long Lin, const float* h, int Nh, int up, int down, float* y, long long Lout, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_resample: ") + why); return BUDDY_ERR_ARG; };
+  if (!x || !h || !y) return bad("null pointer");
+  if (B < 1 || Lin < 1) return bad("B and Lin must be >= 1");
+  if (Lin > (1LL << 40)) return bad("Lin above 2^40");
+  if (up < 1 || down < 1 || up > 1024 || down > 1024) return bad("up and down must be in 1..1024");
+  int a = up, b = down;
+  while (b) { const int t = a % b; a = b; b = t; }
+  if (a != 1) return bad("up / down is not in lowest terms");
+  if (Nh < 1 || Nh % 2 == 0 || Nh > 65537) return bad("Nh must be odd and <= 65537");
+  if (Lout != (Lin * up + down - 1) / down) return bad("Lout is not ceil(Lin * up / down)");
+  if (resample_tiles(Lout) * B > 0x7fffffffLL) return bad("more output tiles than one grid holds");
+  launch_resample(x, B, Lin, h, Nh, up, down, y, Lout, (hipStream_t)stream);
+  return finish();
+}
+
 // ---- WPE warm start ----
 int buddy_wpe(const double* Y, double* X, double* scratch, int rows, int T, int taps, int delay, int iterations, void* stream) {
   if (!Y || !X || !scratch || rows < 1 || T < 1 || taps < 1 || taps > 56 || delay < 0 || iterations < 0) { set_error("bad wpe arguments (taps <= 56)"); return BUDDY_ERR_ARG; }

@@ -174,6 +174,9 @@ void launch_wpe(const double* Y, double* X, double* inv_scratch, int rows, int T
 size_t wpe_workspace_bytes(int B, int L);
 int wpe_frames(int L);
 void launch_wpe_dereverb(const float* y, float* out, void* work, int B, int L, int taps, int delay, int iters, hipStream_t st);
+// rational polyphase resampler (resample.hip): y[b][n] = sum_m x[b][m] h[n*down - m*up + (Nh-1)/2], Lout = ceil(Lin*up/down); arguments checked by the C entry
+long long resample_tiles(long long Lout);
+void launch_resample(const float* x, int B, long long Lin, const float* h, int Nh, int up, int down, float* y, long long Lout, hipStream_t st);
 void launch_axpy(float* dst, const float* src, float alpha, long long n, int accumulate, hipStream_t st);
 // fir=True resampling with the (1,3,3,1) kernel: (H,W)->(2H,2W) / (H,W)->(H/2,W/2); adjoints: up^T = 4 down, down^T = up / 4
 void launch_fir_up2(const float* x, float* y, int B, int H, int W, int C, float scale, int accumulate, hipStream_t st);

@@ -21,6 +21,26 @@ def chunk_plan(L, chunk, overlap):
     return [round(i * (L - chunk) / (n - 1)) for i in range(n)], chunk
 
 
+def pool_plan(lengths, chunk, overlap, batch_size):
+    """Batches for a set of recordings of different lengths (``Tester.test_real_recordings``).  A file of at least ``chunk`` samples is cut with
+    ``chunk_plan`` (equal chunks of ``chunk`` samples, never padded); the chunks of ALL such files form one pool that is cut, in file-then-chunk
+    order, into batches of ``batch_size`` (the last may be smaller).  A shorter file is one chunk of its own length; such files share a batch only
+    at exactly equal length, as ``Tester.test_dereverberation`` groups utterances.
+
+    Returns ``(cuts, batches)``: ``cuts[f] = (starts, clen)`` and ``batches`` = lists of ``(f, k)`` (file, chunk number), every batch of one length."""
+    batch_size = max(1, int(batch_size))
+    cuts = [chunk_plan(int(L), chunk, overlap) for L in lengths]
+    pool = [(f, k) for f, L in enumerate(lengths) if L >= chunk for k in range(len(cuts[f][0]))]
+    batches = [pool[i:i + batch_size] for i in range(0, len(pool), batch_size)]
+    short = {}
+    for f, L in enumerate(lengths):
+        if L < chunk:
+            short.setdefault(int(L), []).append((f, 0))
+    for grp in short.values():
+        batches += [grp[i:i + batch_size] for i in range(0, len(grp), batch_size)]
+    return cuts, batches
+
+
 def crossfade_weights(starts, chunk, L, device=None):
     """(n, chunk) weights: 1 in the interior, linear ramps over the overlap with each neighbour; columns sum to 1 at every sample"""
     n = len(starts)
@@ -55,6 +75,11 @@ def merge(parts, starts, L):
     return out
 
 
+def chunk_gains(parts, y):
+    """(n, 1) level-match gains of ``predict_chunked``: std(y_chunk) / std(y_clip)"""
+    return parts.std(dim=1, keepdim=True) / (y.reshape(-1).std() + 1e-12)
+
+
 def predict_chunked(sample_batch, y, chunk, overlap, level_match=False):
     """``sample_batch``: (n, chunk) reverberant chunks -> (n, chunk) estimates (one sampler call, chunks = utterances).
 
@@ -69,6 +94,5 @@ def predict_chunked(sample_batch, y, chunk, overlap, level_match=False):
     parts, starts = split(y, chunk, overlap)
     est = sample_batch(parts)
     if level_match and parts.shape[0] > 1:
-        g = parts.std(dim=1, keepdim=True) / (y.reshape(-1).std() + 1e-12)
-        est = est * g.to(est.dtype)
+        est = est * chunk_gains(parts, y).to(est.dtype)
     return merge(est, starts, y.reshape(-1).shape[-1])

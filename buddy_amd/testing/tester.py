@@ -110,11 +110,21 @@ class Tester:
             y = operator_ref.degradation(seg)
             operator = operator_ref
             if blind:
-                assert self.args.tester.blind_dereverberation.operator == "subband_filtering"
-                operator = BlindSubbandFiltering(op_hp, sample_rate=self.args.exp.sample_rate, num_utts=len(items), noise=noise, device=self.device,
-                                                 length=seg.shape[-1])
-                operator.update_H(use_noise=True)
+                operator = self._blind_operator(len(items), seg.shape[-1], noise)
         return seg, y, operator, rirs
+
+    def _blind_operator(self, n, length, noise):
+        """a fresh blind operator for ``n`` independent utterances of ``length`` samples: own parameters / RIR estimate per row"""
+        assert self.args.tester.blind_dereverberation.operator == "subband_filtering"
+        operator = BlindSubbandFiltering(self.args.tester.informed_dereverberation.op_hp, sample_rate=self.args.exp.sample_rate, num_utts=n, noise=noise,
+                                         device=self.device, length=length)
+        operator.update_H(use_noise=True)
+        return operator
+
+    def _num_sub_batches(self, n):
+        """how many concurrent sub-batches a group of ``n`` utterances is sampled as (1 = one batch, one stream)"""
+        S = self.sub_batches if self.sub_batches is not None else (2 if n >= 4 else 1)
+        return S if S > 1 and n >= 2 * S and str(self.device).startswith("cuda") else 1
 
     def test_dereverberation(self, mode, blind=False):
         if self.test_set is None or len(self.test_set) == 0:
@@ -135,8 +145,8 @@ class Tester:
                 # parity runs: one injected noise stream per utterance, shared by the sampler AND the blind operator (random phases,
                 # update_H(use_noise=True), per-step RIR-regulariser draws) in the reference's call order; otherwise the torch RNG
                 self.sampler.noise = self.noise_factory([it[2] for it in grp]) if getattr(self, "noise_factory", None) is not None else None
-                S = self.sub_batches if self.sub_batches is not None else (2 if len(grp) >= 4 else 1)
-                if S > 1 and len(grp) >= 2 * S and str(self.device).startswith("cuda"):
+                S = self._num_sub_batches(len(grp))
+                if S > 1:
                     seg, y, pred, est, rirs = self._sample_concurrent(grp, L, blind, S)
                 else:
                     seg, y, operator, rirs = self.prepare_batch(grp, blind, noise=self.sampler.noise)
@@ -163,9 +173,8 @@ class Tester:
 
     def _sample_concurrent(self, grp, L, blind, S):
         """one equal-length group as ``S`` concurrent sub-batches (testing/concurrent.py)"""
-        from .concurrent import ConcurrentSampler, split_rows
-        if self._concurrent is None or self._concurrent_S != S:
-            self._concurrent, self._concurrent_S = ConcurrentSampler(self.args, self.network, self.diff_params, S), S
+        from .concurrent import split_rows
+        self._concurrent_for(S)
         parts = split_rows(len(grp), S)
         noise = self.sampler.noise
         segs, ys, ops, rirs, noises = [], [], [], [], []
@@ -173,12 +182,102 @@ class Tester:
             nz = None if noise is None else noise[lo:hi]
             seg, y, op, rr = self.prepare_batch(grp[lo:hi], blind, noise=nz)
             segs.append(seg); ys.append(y); ops.append(op); rirs += rr; noises.append(nz)
-        preds = self._concurrent.predict_conditional(ys, ops, blind, None if noise is None else noises)
+        pred, est = self._predict_concurrent(ys, ops, blind, None if noise is None else noises, S)
+        return torch.cat(segs), torch.cat(ys), pred, est, rirs
+
+    def _concurrent_for(self, S):
+        from .concurrent import ConcurrentSampler
+        if self._concurrent is None or self._concurrent_S != S:
+            self._concurrent, self._concurrent_S = ConcurrentSampler(self.args, self.network, self.diff_params, S), S
+        return self._concurrent
+
+    def _predict_concurrent(self, ys, ops, blind, noises, S):
+        """``S`` prepared sub-batches (observations, operators, noise streams) -> (estimates, estimated RIRs or None), rows in order"""
+        preds = self._concurrent_for(S).predict_conditional(ys, ops, blind, noises)
         est = None
         if blind:
             e = [sb.s.operator.get_time_RIR().detach().cpu() for sb in self._concurrent.last]
             est = torch.cat([v if v.dim() == 2 else v[None] for v in e])
-        return torch.cat(segs), torch.cat(ys), torch.cat(preds), est, rirs
+        return torch.cat(preds), est
+
+    def sample_observed(self, y, names):
+        """Blind dereverberation of GIVEN observations: ``y`` (n, L), each row an independent utterance with its own operator row and, with a
+        ``noise_factory``, its own noise stream called ``names[b]``.  The sampling half of ``test_dereverberation`` (same sub-batch policy) without
+        the clean/RIR synthesis.  Returns (estimates (n, L), estimated RIRs (n, M) on the CPU)."""
+        from .concurrent import split_rows
+        n, L = y.shape
+        noise = self.noise_factory(list(names)) if getattr(self, "noise_factory", None) is not None else None
+        self.sampler.noise = noise
+        S = self._num_sub_batches(n)
+        with torch.no_grad():
+            if S > 1:
+                parts = split_rows(n, S)
+                noises = None if noise is None else [noise[lo:hi] for lo, hi in parts]
+                ops = [self._blind_operator(hi - lo, L, None if noise is None else noise[lo:hi]) for lo, hi in parts]
+                return self._predict_concurrent([y[lo:hi].contiguous() for lo, hi in parts], ops, True, noises, S)
+            operator = self._blind_operator(n, L, noise)
+        pred = self.sampler.predict_conditional(y.contiguous(), operator, shape=(n, L), blind=True)
+        est = self.sampler.operator.get_time_RIR().detach().cpu()
+        return pred, est if est.dim() == 2 else est[None]
+
+    # ---- real recordings: any rate, any length, no clean signal or true RIR (no reference counterpart) -----------------------------------------
+    def test_real_recordings(self, mode):
+        """Every file of an ``AudioFolder`` -> its dereverberated version.  Per file, on the GPU: resample to the model's rate, scale to
+        ``gain * scaling_factor / std``; files of at least one chunk are cut into equal overlapping chunks (testing/longform.py) and the chunks of
+        ALL files are sampled as one pool of independent utterances in batches of ``batch_size``; then level match, cross-fade, undo the scaling,
+        resample back.  Files go to ranks by index; every rank writes its own, nothing is gathered."""
+        from . import longform
+        from ..utils.resample import resample
+        if self.test_set is None or len(self.test_set) == 0:
+            print("No test set specified / no samples found")
+            return
+        rr = self.args.tester.real_recordings
+        ps = self.args.tester.posterior_sampling
+        sr = int(self.args.exp.sample_rate)
+        chunk = int(self.args.exp.audio_len) if rr.get("chunk_seconds", None) is None else int(round(float(rr.chunk_seconds) * sr))
+        overlap = int(round(float(rr.get("overlap_seconds", 0.5)) * sr))
+        out_rate = str(rr.get("output_rate", "input"))
+        assert out_rate in ("input", "model"), "real_recordings.output_rate is 'input' or 'model'"
+        to_input_rate = out_rate == "input"
+        csm = ps.get("constraint_speech_magnitude", None)
+        level = bool(csm is not None and csm.get("use", False))      # the condition of dereverberate_long
+        self.skipped = []
+        files = []
+        for i in range(self.rank, len(self.test_set), self.world_size):
+            audio, fs, filename = self.test_set[i]
+            y = resample(torch.from_numpy(np.asarray(audio)).float().to(self.device), fs, sr)
+            std = float(y.std()) if y.numel() > 1 else 0.0
+            if y.numel() < 1024 or not std > 0.0:       # below what the HIP STFT / loss kernels take (operators/reverb.py), or digital silence
+                print(f"skipping {filename}: {y.numel()} samples at {sr} Hz" + ("" if y.numel() < 1024 else ", silent"))
+                self.skipped.append(filename)
+                continue
+            g = float(rr.get("gain", 1.0)) * float(ps.warm_initialization.scaling_factor) / std
+            files.append(dict(name=os.path.basename(filename)[:-4], fs=int(fs), n_in=len(audio), y=g * y, g=g))
+        cuts, batches = longform.pool_plan([f["y"].numel() for f in files], chunk, overlap, self.batch_size)
+        for f, (starts, clen) in zip(files, cuts):
+            f["parts"] = torch.stack([f["y"][s:s + clen] for s in starts])
+            f["est"], f["rir"] = [None] * len(starts), [None] * len(starts)
+        for batch in batches:
+            yb = torch.stack([files[f]["parts"][k] for f, k in batch])
+            pred, est = self.sample_observed(yb, [f"{files[f]['name']}_c{k}.wav" for f, k in batch])
+            for b, (f, k) in enumerate(batch):
+                files[f]["est"][k], files[f]["rir"][k] = pred[b].detach(), est[b]
+        writing = not self.in_training and bool(self.paths)
+        for f, (starts, _) in zip(files, cuts):
+            est = torch.stack(f["est"])
+            if level and len(starts) > 1:
+                est = est * longform.chunk_gains(f["parts"], f["y"]).to(est.dtype)
+            pred = longform.merge(est, starts, f["y"].numel()) / f["g"]
+            if to_input_rate:
+                pred = resample(pred.contiguous(), sr, f["fs"])[:f["n_in"]]
+            self.results.append((f["name"], pred.detach().cpu()))
+            if not writing:
+                continue
+            write_audio_file(f["y"], sr, f["name"], path=self.paths[mode + "degraded"])
+            p = write_audio_file(pred, f["fs"] if to_input_rate else sr, f["name"], path=self.paths[mode + "reconstructed"])
+            for k, r in enumerate(f["rir"]):
+                write_audio_file(r, sr, f"{f['name']}_c{k}", path=self.paths[mode + "estimated_rir"])
+            print(p)
 
     def dereverberate_long(self, original, rir, blind, chunk_seconds=8.0, overlap_seconds=1.0, noise=None):
         """Long-form policy (testing/longform.py): one long clean/RIR pair -> the reverberant signal cut into overlapping equal chunks,
@@ -218,7 +317,9 @@ class Tester:
         os.makedirs(self.paths[mode], exist_ok=True)
         if not unconditional:
             subs = ["original", "degraded", "reconstructed"]
-            if "dereverberation" in mode:
+            if mode == "real_blind_dereverberation":         # no clean signal, no true RIR
+                subs = ["degraded", "reconstructed", "estimated_rir"]
+            elif "dereverberation" in mode:
                 subs.append("true_rir")
                 if mode == "blind_dereverberation":
                     subs.append("estimated_rir")
@@ -249,6 +350,11 @@ class Tester:
                     self.prepare_directories(m)
                     self.save_experiment_args(m)
                 self.test_dereverberation(m, blind=True)
+            elif m == "real_blind_dereverberation":
+                if not self.in_training:
+                    self.prepare_directories(m)
+                    self.save_experiment_args(m)
+                self.test_real_recordings(m)
             else:
                 print("Warning: unknown mode: ", m)
 

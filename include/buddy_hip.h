@@ -537,6 +537,18 @@ int buddy_blindop_param_grads(void* handle, const float* x_den, const float* noi
 int buddy_blindop_optimize(void* handle, const float* x_den, const float* noise, float t_op, int n_iters, float w_rec, float w_reg, float lr,
                            float beta1, float beta2, float weight_decay, void* stream);
 
+/* ---- any-rate input: batched rational polyphase resampler (buddy_amd/utils/resample.py; the reference's loaders assert samplerate == fs and
+ * have no resampler).  x (B, Lin), h: odd-length symmetric FIR of Nh taps with centre c = (Nh-1)/2 and DC gain `up`, y (B, Lout):
+ *
+ *   y[b][n] = sum over m in [0, Lin) with 0 <= n*down - m*up + c < Nh  of  x[b][m] * h[n*down - m*up + c],   n in [0, Lout),
+ *   Lout = ceil(Lin * up / down)
+ *
+ * i.e. zero-stuffing by `up`, filtering with h, keeping every `down`-th sample, zero extension at both ends (scipy.signal.resample_poly
+ * with window = h / up and padtype = 'constant').  fp32 accumulation in ascending m; nothing is written outside y[b][0 .. Lout-1].
+ * BUDDY_ERR_ARG, with nothing launched, for: a null pointer; B < 1 or Lin < 1; up or down outside 1..1024; gcd(up, down) != 1; Nh even or
+ * above 65 537; Lout != ceil(Lin * up / down); Lin above 2^40 or more than 2^31 - 1 tiles of 1024 outputs over all rows. */
+int buddy_resample(const float* x, int B, long long Lin, const float* h, int Nh, int up, int down, float* y, long long Lout, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,7 @@
         tester.sampling_params.T=201 model_dir=experiments/run +gpu=0 dset.test.path=audio_examples dset.test.num_examples=2
 
 without Hydra (not installable offline): `group=name` picks conf/<group>/<name>.yaml, `a.b.c=value` overrides a key.
+`tester=real_dereverberation_BUDDy dset.test.path=<dir of wavs>` dereverberates real recordings of any rate (datasets/recordings.py).
 Extra keys: +batch_size=N (utterances per sampler call), +allow_random_init=true (no checkpoint: synthetic runs), and the torchrun
 environment variables for utterance sharding (rank 0 ends up with every prediction: one RCCL gather at the end)."""
 import os
@@ -52,7 +53,10 @@ def _main(args):
     network = instantiate(args.network).to(device)                       # :32
     dcfg = args.get("dset", AttrDict()).get("test", AttrDict())
     test_set = None
-    if dcfg.get("path", None):
+    if dcfg.get("path", None) and "real_blind_dereverberation" in args.tester.modes:
+        from buddy_amd.datasets.recordings import AudioFolder
+        test_set = AudioFolder(path=dcfg.path, num_examples=int(dcfg.get("num_examples", 0)))
+    elif dcfg.get("path", None):
         from buddy_amd.datasets.vctk import VCTKTestPaired
         test_set = VCTKTestPaired(fs=args.exp.sample_rate, path=dcfg.path, num_examples=int(dcfg.get("num_examples", 8)),
                                   speakers_test=dcfg.get("speakers_test", ()), speakers_discard=dcfg.get("speakers_discard", ()))
@@ -69,13 +73,14 @@ def _main(args):
         print("trying to load latest checkpoint")
         tester.load_latest_checkpoint()                                   # :95-96 -- raises "No checkpoint found"
     tester.do_test()                                                      # :98
+    return tester
 
 
 def main(argv=None):
     groups, overrides = parse(sys.argv[1:] if argv is None else argv)
     args = compose(tester=groups.get("tester", "only_unconditional"), network=groups.get("network", "ncsnpp"),
                    diff_params=groups.get("diff_params", "edm_VCTK"), exp=groups.get("exp", "VCTK_16k_4s_time"), overrides=overrides)
-    _main(args)
+    return _main(args)
 
 
 if __name__ == "__main__":
