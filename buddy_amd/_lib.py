@@ -159,6 +159,7 @@ _SIGS = {
     "buddy_blindop_destroy": (C.c_int, [C.c_void_p]),
     "buddy_blindop_set_params": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_int, C.c_void_p]),
     "buddy_blindop_get_params": (C.c_int, [C.c_void_p, _f32p, _f32p, _f32p, C.c_void_p]),
+    "buddy_blindop_set_groups": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "buddy_blindop_update_H": (C.c_int, [C.c_void_p, _f32p, C.c_void_p]),
     "buddy_blindop_get_H": (C.c_int, [C.c_void_p, _f32p, C.c_void_p]),
     "buddy_blindop_set_y": (C.c_int, [C.c_void_p, _f32p, C.c_void_p]),

@@ -692,6 +692,7 @@ int buddy_blindop_set_params(void* h, const float* decay, const float* weights, 
 int buddy_blindop_get_params(void* h, float* decay, float* weights, float* phases, void* stream) {
   BOP_CHECK(h); return blindop_get_params((BlindOp*)h, decay, weights, phases, (hipStream_t)stream);
 }
+int buddy_blindop_set_groups(void* h, const int* group_of_row, void* stream) { BOP_CHECK(h); return blindop_set_groups((BlindOp*)h, group_of_row, (hipStream_t)stream); }
 int buddy_blindop_update_H(void* h, const float* noise, void* stream) { BOP_CHECK(h); return blindop_update_H((BlindOp*)h, noise, (hipStream_t)stream); }
 int buddy_blindop_get_H(void* h, float* out, void* stream) { BOP_CHECK(h); if (!out) { set_error("null"); return BUDDY_ERR_ARG; } return blindop_get_H((BlindOp*)h, out, (hipStream_t)stream); }
 int buddy_blindop_set_y(void* h, const float* y, void* stream) { BOP_CHECK(h); if (!y) { set_error("null"); return BUDDY_ERR_ARG; } return blindop_set_y((BlindOp*)h, y, (hipStream_t)stream); }

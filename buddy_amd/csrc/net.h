@@ -61,6 +61,7 @@ int blindop_stft_len(BlindOp* o, const float* x, int len, float* X_ref, hipStrea
 int blindop_stft_len_adj(BlindOp* o, const float* G_ref, int len, float* g_x, hipStream_t st);
 int blindop_stft_loss(BlindOp* o, const float* a, const float* b, int len, float weight, float* loss, float* g_a, float* g_b, hipStream_t st);
 int blindop_set_compression(BlindOp* o, float comp);
+int blindop_set_groups(BlindOp* o, const int* group_of_row, hipStream_t st);
 int blindop_set_loss_norm(BlindOp* o, int mode);
 int blindop_set_loss(BlindOp* o, int slot, int kind, int freq_weighting, float comp);
 int blindop_set_freq_weights(BlindOp* o, int freq_weighting, const float* w);

@@ -1151,10 +1151,11 @@ __global__ __launch_bounds__(256) void angle_kernel(const float* H, float* phi, 
     phi[i] = atan2f(h.y, h.x);
   }
 }
-__global__ __launch_bounds__(256) void unit_phase_kernel(const float* Nz, float* phi, int U, int Nf) {   // phi = angle(N[:, 1:]) frame k <- noise frame k+1
+// phi = angle(N[:, 1:]) frame k <- noise frame k+1; leader (tied rows only, else NULL): row u reads the noise of row leader[u]
+__global__ __launch_bounds__(256) void unit_phase_kernel(const float* Nz, float* phi, int U, int Nf, const int* leader) {
   const long long total = (long long)U * Nf * FB;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const int f = (int)(i % FB), k = (int)((i / FB) % Nf), u = (int)(i / ((long long)FB * Nf));
+    const int f = (int)(i % FB), k = (int)((i / FB) % Nf), ur = (int)(i / ((long long)FB * Nf)), u = leader ? leader[ur] : ur;
     const float2 h = reinterpret_cast<const float2*>(Nz + ((long long)u * (Nf + 1) + k + 1) * LDSP)[f];
     phi[i] = atan2f(h.y, h.x);
   }
@@ -1183,6 +1184,51 @@ __global__ __launch_bounds__(256) void spec_from_ref_kernel(const float* in, flo
     reinterpret_cast<float2*>(X + ((long long)u * T + t) * LDSP)[f] = f < FB ? reinterpret_cast<const float2*>(in)[((long long)u * FB + f) * T + t] : make_float2(0.f, 0.f);
   }
 }
+// ---- tied rows (buddy_blindop_set_groups): the rows [start, start + n) of a group share one parameter set.  Only groups of more than one row are listed.
+struct GroupSpan { int start, n; float inv; };      // inv = 1.0f / n
+template <int V> __device__ __forceinline__ void ld_vec(const float* p, float* v) {
+  if constexpr (V == 4) { const float4 q = *reinterpret_cast<const float4*>(p); v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; } else v[0] = *p;
+}
+template <int V> __device__ __forceinline__ void st_vec(float* p, const float* v) {
+  if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); else *p = v[0];
+}
+// gphi (U, Nf, FB) and gdm (U, Nf, K) of every member row := the mean over its group.  One thread owns V consecutive elements of one group: it sums the
+// members in ascending row order, scales by 1 / n and stores the same bits to every member (nobody else touches these elements: no hazard, no atomics).
+// Elements [0, n_phi) of a row index gphi, [n_phi, n_phi + n_dm) index gdm; V == 4 needs both counts to be multiples of 4.
+template <int V> __global__ __launch_bounds__(256) void group_mean_kernel(const GroupSpan* spans, float* gphi, int n_phi, float* gdm, int n_dm) {
+  const GroupSpan g = spans[blockIdx.y];
+  int i = ((int)blockIdx.x * 256 + (int)threadIdx.x) * V;
+  float* base = gphi; int row = n_phi;
+  if (i >= n_phi) { i -= n_phi; base = gdm; row = n_dm; if (i >= n_dm) return; }
+  float* p = base + (long long)g.start * row + i;
+  float acc[V], v[V];
+  ld_vec<V>(p, acc);
+  for (int r = 1; r < g.n; ++r) {
+    ld_vec<V>(p + (long long)r * row, v);
+#pragma unroll
+    for (int c = 0; c < V; ++c) acc[c] += v[c];
+  }
+#pragma unroll
+  for (int c = 0; c < V; ++c) acc[c] *= g.inv;
+  for (int r = 0; r < g.n; ++r) st_vec<V>(p + (long long)r * row, acc);
+}
+// the leader's (first row's) parameters and Adam moments -> every member: blockIdx.y picks the array, blockIdx.z the group; four elements per thread
+struct TieArrays { float* p[9]; int row[9]; };       // decay, weights and their four moments (E * NB per row); phases and their two (Nf * FB per row)
+__global__ __launch_bounds__(256) void group_bcast_kernel(const GroupSpan* spans, TieArrays a) {
+  const GroupSpan g = spans[blockIdx.z];
+  const int row = a.row[blockIdx.y], i = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4;
+  if (i >= row) return;
+  float* p = a.p[blockIdx.y] + (long long)g.start * row + i;
+  float v[4];
+  if ((row & 3) == 0) {
+    ld_vec<4>(p, v);
+    for (int r = 1; r < g.n; ++r) st_vec<4>(p + (long long)r * row, v);
+  } else {
+    const int m = min(4, row - i);
+    for (int c = 0; c < m; ++c) v[c] = p[c];
+    for (int r = 1; r < g.n; ++r) for (int c = 0; c < m; ++c) p[(long long)r * row + c] = v[c];
+  }
+}
 // plain minimum-phase output: hm = Re(o)[:Lm] (no direct-path override)
 
 inline int gridf(long long total) { long long g = (total + 255) / 256; if (g > 8192) g = 8192; if (g < 1) g = 1; return (int)g; }
@@ -1203,6 +1249,8 @@ struct BlindOp {
   float *decay = nullptr, *wts = nullptr, *phi = nullptr;
   float *m_d = nullptr, *v_d = nullptr, *m_w = nullptr, *v_w = nullptr, *m_p = nullptr, *v_p = nullptr;
   int adam_step = 0;
+  // tied rows (buddy_blindop_set_groups): the groups of more than one row, and for every row the first row of its group
+  int n_tied = 0; GroupSpan* d_spans = nullptr; int* d_leader = nullptr;
   // captured optimize_op graph (launch-bound loop: ~72 small kernels per Adam iteration): per-call inputs live at fixed device addresses
   static constexpr int MAXSTEP = 65536;
   int* d_step = nullptr; float* d_scal = nullptr; float2* bc_tab = nullptr; float tab_b1 = -1.f, tab_b2 = -1.f;
@@ -1448,6 +1496,20 @@ struct BlindOp {
     comp_loss(2, leg ? Rc : nullptr, X2, X3, Td, w_reg, losses + U);                                // other kinds: target phi(w_f X3) formed in the loss kernel
     stft_adj_istft_adj(X3, Lr, WIN, Td, 1.f / norm, Td, Q, env_d, norm, X2);
   }
+  // tied rows: group mean of the phase / knot gradients; the leader's parameters and moments to the members
+  void group_mean() {
+    const int n_phi = Nf * FB, n_dm = Nf * K;
+    if (((n_phi | n_dm) & 3) == 0) hipLaunchKernelGGL(group_mean_kernel<4>, dim3(cdiv((n_phi + n_dm) / 4, 256), n_tied), dim3(256), 0, st, (const GroupSpan*)d_spans, gphi, n_phi, gdm, n_dm);
+    else hipLaunchKernelGGL(group_mean_kernel<1>, dim3(cdiv(n_phi + n_dm, 256), n_tied), dim3(256), 0, st, (const GroupSpan*)d_spans, gphi, n_phi, gdm, n_dm);
+  }
+  void group_bcast() {
+    TieArrays a;
+    float* small[6] = {decay, wts, m_d, v_d, m_w, v_w};
+    float* big[3] = {phi, m_p, v_p};
+    for (int k = 0; k < 6; ++k) { a.p[k] = small[k]; a.row[k] = E * NB; }
+    for (int k = 0; k < 3; ++k) { a.p[6 + k] = big[k]; a.row[6 + k] = Nf * FB; }
+    hipLaunchKernelGGL(group_bcast_kernel, dim3(cdiv(cdiv(std::max(E * NB, Nf * FB), 4), 256), 9, n_tied), dim3(256), 0, st, (const GroupSpan*)d_spans, a);
+  }
   void degrade(const float* x, float* y) {
     stft(x, L, WIN, T, 1.f / norm, X1);
     fir(X1, (long long)T * LDSP, T, Ybuf);
@@ -1591,6 +1653,38 @@ int blindop_set_params(BlindOp* o, const float* decay, const float* wts, const f
     const size_t np = (size_t)o->U * o->Nf * FB * 4;
     HIPCHK(hipMemsetAsync(o->m_p, 0, np, st)); HIPCHK(hipMemsetAsync(o->v_p, 0, np, st));
   }
+  if (o->n_tied) { o->group_bcast(); HIPCHK(hipGetLastError()); }       // tied rows: whatever the caller gave the members, the leader's values hold
+  return BUDDY_OK;
+}
+// rows of one group share one parameter set (see include/buddy_hip.h); g == NULL or groups of one row only: untied, today's launches
+int blindop_set_groups(BlindOp* o, const int* g, hipStream_t st) {
+  const int U = o->U;
+  std::vector<GroupSpan> spans;
+  std::vector<int> leader(U), gr(U);
+  hipStream_t prev = o->st;
+  for (int u = 0; u < U; ++u) {
+    gr[u] = g ? g[u] : u;
+    const int d = u ? gr[u] - gr[u - 1] : 1;
+    if (gr[0] != 0 || (d != 0 && d != 1)) { set_error("group_of_row: starts at 0, non-decreasing, steps of 0 or 1 (groups are contiguous row ranges)"); return BUDDY_ERR_ARG; }
+    leader[u] = d ? u : leader[u - 1];
+  }
+  for (int u = 0; u < U;) {
+    int n = 1;
+    while (u + n < U && leader[u + n] == u) ++n;
+    if (n > 1) spans.push_back(GroupSpan{u, n, 1.0f / (float)n});
+    u += n;
+  }
+  o->st = st;
+  if (!spans.empty()) {
+    if ((!o->d_spans && o->dalloc(&o->d_spans, (size_t)U)) || (!o->d_leader && o->dalloc(&o->d_leader, (size_t)U))) { set_error("hipMalloc failed"); return BUDDY_ERR_HIP; }
+    HIPCHK(hipStreamSynchronize(st));                    // launches in flight may still read the previous tables: on this stream ...
+    if (prev != st) HIPCHK(hipStreamSynchronize(prev));  // ... or on the one the handle's last call was given
+    HIPCHK(hipMemcpy(o->d_spans, spans.data(), spans.size() * sizeof(GroupSpan), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(o->d_leader, leader.data(), (size_t)U * sizeof(int), hipMemcpyHostToDevice));
+  }
+  o->n_tied = (int)spans.size();
+  if (o->gexec) { (void)hipGraphExecDestroy(o->gexec); o->gexec = nullptr; }      // the captured loop has the group-mean node or not
+  if (o->n_tied) { o->group_bcast(); HIPCHK(hipGetLastError()); }
   return BUDDY_OK;
 }
 int blindop_get_params(BlindOp* o, float* decay, float* wts, float* phases_ref, hipStream_t st) {
@@ -1606,7 +1700,8 @@ int blindop_update_H(BlindOp* o, const float* noise, hipStream_t st) {
   o->st = st;
   if (noise) {
     o->stft(noise, o->Lh, WIN, o->Nf + 1, 1.f / o->norm, o->X1);     // centred frames 0..Nf; we need 1..Nf
-    hipLaunchKernelGGL(unit_phase_kernel, dim3(gridf((long long)o->U * o->Nf * FB)), dim3(256), 0, st, (const float*)o->X1, o->phi, o->U, o->Nf);
+    hipLaunchKernelGGL(unit_phase_kernel, dim3(gridf((long long)o->U * o->Nf * FB)), dim3(256), 0, st, (const float*)o->X1, o->phi, o->U, o->Nf,
+                       o->n_tied ? (const int*)o->d_leader : (const int*)nullptr);
   }
   o->update_H();
   if (noise) hipLaunchKernelGGL(angle_kernel, dim3(gridf((long long)o->U * o->Nf * FB)), dim3(256), 0, st, (const float*)o->H, o->phi, o->U, o->Nf);
@@ -1934,6 +2029,7 @@ static int param_grads(BlindOp* o, const float* x_den, const float* noise, float
   o->cons_backward(o->GH);
   hipLaunchKernelGGL(h0_bwd_knots_kernel, dim3(U * Nf), dim3(256), 0, st, (const float*)o->GFin, (const float*)o->A, (const float*)o->Apre, (const float*)o->phi, o->tabs(),
                      (const float*)o->dmv, o->gphi, o->gdm, U, o->K, Nf);
+  if (o->n_tied) o->group_mean();        // tied rows: every member gets its group's mean gradient, so Adam below keeps the members equal
   if (!o->fused_loop)      // the captured loop forms these two inside its Adam kernel
     hipLaunchKernelGGL(design_bwd_params_kernel, dim3(cdiv(U * o->E * o->NB, 4)), dim3(256), 0, st, (const float*)o->gdm, (const float*)o->decay, (const float*)o->wts, o->gdecay, o->gw, U, o->E, o->NB, Nf);
   return BUDDY_OK;

@@ -42,6 +42,23 @@ def split_rows(n, parts):
     return out
 
 
+def split_groups(groups, parts):
+    """``split_rows`` for tied operator rows: at most ``parts`` contiguous row ranges whose boundaries fall on group boundaries (a group lives inside
+    one operator), as even as those allow: every cut is the group boundary nearest to the even cut.  One group gives one part."""
+    n = len(groups)
+    starts = [b for b in range(1, n) if groups[b] != groups[b - 1]]
+    parts = max(1, min(int(parts), len(starts) + 1))
+    cuts = []
+    for p in range(1, parts):
+        lo = cuts[-1] if cuts else 0
+        cand = [b for b in starts if b > lo]
+        if not cand:
+            break
+        cuts.append(min(cand, key=lambda b: (abs(b - p * n / parts), b)))
+    edges = [0] + cuts + [n]
+    return [(edges[i], edges[i + 1]) for i in range(len(edges) - 1)]
+
+
 class ConcurrentSampler:
     """S samplers (own network replica each) + S streams, created once and reused for every batch."""
 

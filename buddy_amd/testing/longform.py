@@ -41,6 +41,57 @@ def pool_plan(lengths, chunk, overlap, batch_size):
     return cuts, batches
 
 
+def run_bounds(n, max_rows):
+    """``n`` chunks of one file as consecutive runs of at most ``max_rows`` chunks, near-equal in size: [(lo, hi), ...] (one run when they fit)"""
+    max_rows = max(1, int(max_rows))
+    r = max(1, math.ceil(n / max_rows))
+    base, extra = divmod(n, r)
+    out, lo = [], 0
+    for j in range(r):
+        hi = lo + base + (1 if j < extra else 0)
+        out.append((lo, hi)); lo = hi
+    return out
+
+
+def pool_plan_shared(lengths, chunk, overlap, batch_size, max_rows):
+    """``pool_plan`` for one RIR estimate per file (``real_recordings.shared_rir``): same cuts, same return shape, but a batch never splits a file,
+    because a group of tied operator rows lives inside one operator.  Files are taken in order; a batch closes when the next file's chunks would
+    take it past ``batch_size`` rows.  A file of more than ``batch_size`` chunks gets a batch of its own with all its chunks -- the batch, and the
+    memory it takes, is then as large as the file, up to ``max_rows`` rows.  A file of more than ``max_rows`` chunks is cut into consecutive runs
+    (``run_bounds``); each run is placed like a file and is a group of its own.  Short files as in ``pool_plan``.  ``shared_groups`` gives a
+    batch's group map."""
+    batch_size = max(1, int(batch_size))
+    cuts = [chunk_plan(int(L), chunk, overlap) for L in lengths]
+    batches, cur = [], []
+    for f, L in enumerate(lengths):
+        if L < chunk:
+            continue
+        for lo, hi in run_bounds(len(cuts[f][0]), max_rows):
+            if cur and len(cur) + hi - lo > batch_size:
+                batches.append(cur); cur = []
+            cur = cur + [(f, k) for k in range(lo, hi)]
+    if cur:
+        batches.append(cur)
+    short = {}
+    for f, L in enumerate(lengths):
+        if L < chunk:
+            short.setdefault(int(L), []).append((f, 0))
+    for grp in short.values():
+        batches += [grp[i:i + batch_size] for i in range(0, len(grp), batch_size)]
+    return cuts, batches
+
+
+def shared_groups(cuts, batch, max_rows):
+    """group map of one batch of ``pool_plan_shared``: row b -> number of its (file, run) within the batch (starts at 0, steps of 0 or 1)"""
+    run_of = lambda f, k: next(j for j, (lo, hi) in enumerate(run_bounds(len(cuts[f][0]), max_rows)) if lo <= k < hi)
+    keys = [(f, run_of(f, k)) for f, k in batch]
+    out, g = [], 0
+    for b, key in enumerate(keys):
+        g += 1 if b and key != keys[b - 1] else 0
+        out.append(g)
+    return out
+
+
 def crossfade_weights(starts, chunk, L, device=None):
     """(n, chunk) weights: 1 in the interior, linear ramps over the overlap with each neighbour; columns sum to 1 at every sample"""
     n = len(starts)
@@ -87,7 +138,7 @@ def predict_chunked(sample_batch, y, chunk, overlap, level_match=False):
     (``constraint_speech_magnitude``, reference EulerHeunSamplerDPS.py:127-129) -- per CHUNK here, so a chunk that is mostly a pause would come
     back as loud as a chunk of running speech and the cross-fade would mix segments of different gains.  With ``level_match`` each chunk's
     estimate is scaled by std(y_chunk) / std(y_clip) (the observation's own level profile) before the merge, which restores one gain for the clip;
-    what remains chunk-specific is the RIR estimate (one operator per chunk), see profiles/DESIGN_history_r01-r04.md section 5.  Residual bias: the gain profile is the
+    what remains chunk-specific is the RIR estimate (one operator per chunk, unless the chunks are tied into one group: ``shared_rir``), see profiles/DESIGN_history_r01-r04.md section 5.  Residual bias: the gain profile is the
     OBSERVATION's, and reverberation fills pauses, so a pause comes back louder than in the clean signal (measured pause / speech level 0.107
     against 0.052 in the input of tests/test_hip_cli.py's clip).  Chunks are never padded (equal chunks, the last one starts at L - chunk), so
     every std is over valid samples."""

@@ -1,7 +1,8 @@
 """Subband (STFT-domain) blind reverberation operator, same surface as reference ``testing/operators/subband_filtering.py``
 (``BlindSubbandFiltering`` :142-351 and the methods it inherits from ``SubbandFiltering`` :8-136), batched per utterance: every parameter /
 filter tensor carries a leading utterance axis ``U`` (U = 1 reproduces the reference exactly; U > 1 is the per-utterance vmap of it -- no
-cross-utterance coupling anywhere).
+cross-utterance coupling anywhere, unless the caller ties rows: ``groups`` makes contiguous rows share one parameter set, one Adam state and one H,
+fitted to all of them -- one RIR estimate for the chunks of one recording; no reference counterpart).
 
 HIP only.  Parameters, Adam state, the filter H and every intermediate live inside a ``buddy_blindop_*`` handle of ``libbuddy_hip.so``
 (hand-written forward + analytic backward kernels, one library call per ``optimize_op``).  There is no torch-op implementation in the product:
@@ -217,7 +218,7 @@ class BlindSubbandFiltering(SubbandFiltering):
     kernels, a whole ``optimize_op`` (reference EulerHeunSamplerDPS.py:71-113) is ONE library call."""
 
     def __init__(self, op_hp, sample_rate, magnitude_distance=True, H_cplx=False, num_utts=1, noise=None, device=None, backend=None,
-                 length=None):
+                 length=None, groups=None):
         import ctypes as C
         lib = _lib.require_gpu()              # no GPU / no library: BuddyHipError, never a CPU path
         if backend not in (None, "hip"):
@@ -260,6 +261,9 @@ class BlindSubbandFiltering(SubbandFiltering):
             ph = (self._rand((self.n_fft // 2 + 1, self.Nf)) * 2 * np.pi - np.pi).contiguous()
         _lib.check(lib.buddy_blindop_set_params(self._h, _lib.ptr(d0), _lib.ptr(w0), _lib.ptr(ph), 1, _lib.stream_ptr()))
         self.last_rec_per_utt = None
+        self.groups = None
+        if groups is not None:        # before the first update_H; every row has drawn its phases from its own stream, the library keeps the leader's
+            self.set_groups(groups)
         if op_hp.init_phases == "random_coherent":
             self.update_H(use_noise=True)
         elif op_hp.init_phases == "random":
@@ -349,6 +353,25 @@ class BlindSubbandFiltering(SubbandFiltering):
         if d is not None or w is not None or p is not None:
             self._lib_newer = True
 
+    def set_groups(self, groups):
+        """Tie rows (``buddy_blindop_set_groups``): ``groups`` = U ints, first 0, non-decreasing in steps of 0 or 1; rows of one group share the
+        parameters, Adam state and H of its first row and are fitted to all its rows (mean gradient).  ``None``: every row on its own.
+        The members take the leader's parameters and moments at once; their H follows at the next ``update_H`` (``hip_optimize`` rebuilds it
+        itself), so call ``update_H()`` before reading H / degradation / get_time_RIR of an operator tied after construction.  Tied fitting
+        runs through ``hip_optimize`` only: the autograd mode (torch-side optimizer on ``params``) has per-row gradients and is refused."""
+        import ctypes as C
+        g = None
+        if groups is not None:
+            g = [int(v) for v in groups]
+            if len(g) != self.U:
+                raise ValueError(f"groups: {len(g)} entries for {self.U} rows")
+        if self._torch_side_changed():
+            self._push_persistent()
+        arr = None if g is None else (C.c_int * self.U)(*g)
+        _lib.check(_lib.load().buddy_blindop_set_groups(self._h, arr, _lib.stream_ptr()))
+        self.groups = g
+        self._lib_newer = True        # the members took the leader's parameters
+
     def update_H(self, rir=None, H=None, use_noise=False, noise=None, phases=None):
         if rir is not None or H is not None:
             raise NotImplementedError("an externally given H / RIR is the informed scenario (RIROperator); the blind operator designs H from its parameters")
@@ -356,6 +379,8 @@ class BlindSubbandFiltering(SubbandFiltering):
             self.set_params(phases=phases)
         if not use_noise and self._pt is not None and any(t.requires_grad for t in self._pt) and torch.is_grad_enabled():
             # the reference's optimize_op (:78-83): parameters flagged requires_grad, then update_H -- H comes out attached to them
+            if self.groups is not None and len(set(self.groups)) < self.U:
+                raise NotImplementedError("tied rows (groups) are fitted by hip_optimize: the autograd mode has per-row gradients and no group mean")
             d, w, p = self._persistent()
             self._Hr = _UpdateHFn.apply(d, w, p, self)
             self._pt_seen = [t._version for t in self._pt]

@@ -27,6 +27,11 @@ def write_audio_file(x, sr, string, path="tmp"):
     return p
 
 
+def shared_rir_options(rr):
+    """(shared_rir, shared_rir_max_chunks) of a ``real_recordings`` block; a config written before the keys existed means (False, 32)"""
+    return bool(rr.get("shared_rir", False)), int(rr.get("shared_rir_max_chunks", 32))
+
+
 class Tester:
     def __init__(self, args, network, diff_params, test_set=None, device=None, in_training=False, batch_size=1, rank=0, world_size=1):
         self.args = args
@@ -113,11 +118,11 @@ class Tester:
                 operator = self._blind_operator(len(items), seg.shape[-1], noise)
         return seg, y, operator, rirs
 
-    def _blind_operator(self, n, length, noise):
-        """a fresh blind operator for ``n`` independent utterances of ``length`` samples: own parameters / RIR estimate per row"""
+    def _blind_operator(self, n, length, noise, groups=None):
+        """a fresh blind operator for ``n`` utterances of ``length`` samples: own parameters / RIR estimate per row, or per group of rows (``groups``)"""
         assert self.args.tester.blind_dereverberation.operator == "subband_filtering"
         operator = BlindSubbandFiltering(self.args.tester.informed_dereverberation.op_hp, sample_rate=self.args.exp.sample_rate, num_utts=n, noise=noise,
-                                         device=self.device, length=length)
+                                         device=self.device, length=length, groups=groups)
         operator.update_H(use_noise=True)
         return operator
 
@@ -200,22 +205,25 @@ class Tester:
             est = torch.cat([v if v.dim() == 2 else v[None] for v in e])
         return torch.cat(preds), est
 
-    def sample_observed(self, y, names):
+    def sample_observed(self, y, names, groups=None):
         """Blind dereverberation of GIVEN observations: ``y`` (n, L), each row an independent utterance with its own operator row and, with a
         ``noise_factory``, its own noise stream called ``names[b]``.  The sampling half of ``test_dereverberation`` (same sub-batch policy) without
-        the clean/RIR synthesis.  Returns (estimates (n, L), estimated RIRs (n, M) on the CPU)."""
-        from .concurrent import split_rows
+        the clean/RIR synthesis.  ``groups`` (n ints, contiguous, from 0): rows of one group share one operator row set, i.e. one RIR estimate;
+        sub-batches then never split a group.  Returns (estimates (n, L), estimated RIRs (n, M) on the CPU)."""
+        from .concurrent import split_groups, split_rows
         n, L = y.shape
         noise = self.noise_factory(list(names)) if getattr(self, "noise_factory", None) is not None else None
         self.sampler.noise = noise
         S = self._num_sub_batches(n)
+        parts = split_rows(n, S) if groups is None else split_groups(groups, S)
         with torch.no_grad():
-            if S > 1:
-                parts = split_rows(n, S)
+            if len(parts) > 1:
+                S = len(parts)
                 noises = None if noise is None else [noise[lo:hi] for lo, hi in parts]
-                ops = [self._blind_operator(hi - lo, L, None if noise is None else noise[lo:hi]) for lo, hi in parts]
+                ops = [self._blind_operator(hi - lo, L, None if noise is None else noise[lo:hi],
+                                            None if groups is None else [g - groups[lo] for g in groups[lo:hi]]) for lo, hi in parts]
                 return self._predict_concurrent([y[lo:hi].contiguous() for lo, hi in parts], ops, True, noises, S)
-            operator = self._blind_operator(n, L, noise)
+            operator = self._blind_operator(n, L, noise, groups)
         pred = self.sampler.predict_conditional(y.contiguous(), operator, shape=(n, L), blind=True)
         est = self.sampler.operator.get_time_RIR().detach().cpu()
         return pred, est if est.dim() == 2 else est[None]
@@ -225,7 +233,9 @@ class Tester:
         """Every file of an ``AudioFolder`` -> its dereverberated version.  Per file, on the GPU: resample to the model's rate, scale to
         ``gain * scaling_factor / std``; files of at least one chunk are cut into equal overlapping chunks (testing/longform.py) and the chunks of
         ALL files are sampled as one pool of independent utterances in batches of ``batch_size``; then level match, cross-fade, undo the scaling,
-        resample back.  Files go to ranks by index; every rank writes its own, nothing is gathered."""
+        resample back.  Files go to ranks by index; every rank writes its own, nothing is gathered.  ``real_recordings.shared_rir``: the chunks
+        of a file are tied rows of one operator -- one RIR estimate per file, fitted to all its chunks; a batch then never splits a file
+        (``longform.pool_plan_shared``).  ``self.rirs[name]`` keeps the per-chunk RIR estimates in both modes."""
         from . import longform
         from ..utils.resample import resample
         if self.test_set is None or len(self.test_set) == 0:
@@ -253,16 +263,27 @@ class Tester:
                 continue
             g = float(rr.get("gain", 1.0)) * float(ps.warm_initialization.scaling_factor) / std
             files.append(dict(name=os.path.basename(filename)[:-4], fs=int(fs), n_in=len(audio), y=g * y, g=g))
-        cuts, batches = longform.pool_plan([f["y"].numel() for f in files], chunk, overlap, self.batch_size)
+        shared, max_rows = shared_rir_options(rr)
+        lengths = [f["y"].numel() for f in files]
+        if shared:
+            cuts, batches = longform.pool_plan_shared(lengths, chunk, overlap, self.batch_size, max_rows)
+            for f, (starts, _) in zip(files, cuts):
+                f["runs"] = longform.run_bounds(len(starts), max_rows)
+                if len(f["runs"]) > 1:
+                    print(f"{f['name']}: {len(starts)} chunks, more than shared_rir_max_chunks={max_rows}: {len(f['runs'])} runs with one RIR estimate each")
+        else:
+            cuts, batches = longform.pool_plan(lengths, chunk, overlap, self.batch_size)
         for f, (starts, clen) in zip(files, cuts):
             f["parts"] = torch.stack([f["y"][s:s + clen] for s in starts])
             f["est"], f["rir"] = [None] * len(starts), [None] * len(starts)
         for batch in batches:
             yb = torch.stack([files[f]["parts"][k] for f, k in batch])
-            pred, est = self.sample_observed(yb, [f"{files[f]['name']}_c{k}.wav" for f, k in batch])
+            pred, est = self.sample_observed(yb, [f"{files[f]['name']}_c{k}.wav" for f, k in batch],
+                                             groups=longform.shared_groups(cuts, batch, max_rows) if shared else None)
             for b, (f, k) in enumerate(batch):
                 files[f]["est"][k], files[f]["rir"][k] = pred[b].detach(), est[b]
         writing = not self.in_training and bool(self.paths)
+        self.rirs = {f["name"]: list(f["rir"]) for f in files}
         for f, (starts, _) in zip(files, cuts):
             est = torch.stack(f["est"])
             if level and len(starts) > 1:
@@ -275,13 +296,18 @@ class Tester:
                 continue
             write_audio_file(f["y"], sr, f["name"], path=self.paths[mode + "degraded"])
             p = write_audio_file(pred, f["fs"] if to_input_rate else sr, f["name"], path=self.paths[mode + "reconstructed"])
-            for k, r in enumerate(f["rir"]):
-                write_audio_file(r, sr, f"{f['name']}_c{k}", path=self.paths[mode + "estimated_rir"])
+            if shared:       # one estimate per file (per run where shared_rir_max_chunks cut it): the chunks of a run hold the same RIR
+                for j, (lo, _) in enumerate(f["runs"]):
+                    write_audio_file(f["rir"][lo], sr, f["name"] if len(f["runs"]) == 1 else f"{f['name']}_r{j}", path=self.paths[mode + "estimated_rir"])
+            else:
+                for k, r in enumerate(f["rir"]):
+                    write_audio_file(r, sr, f"{f['name']}_c{k}", path=self.paths[mode + "estimated_rir"])
             print(p)
 
-    def dereverberate_long(self, original, rir, blind, chunk_seconds=8.0, overlap_seconds=1.0, noise=None):
+    def dereverberate_long(self, original, rir, blind, chunk_seconds=8.0, overlap_seconds=1.0, noise=None, shared_rir=False):
         """Long-form policy (testing/longform.py): one long clean/RIR pair -> the reverberant signal cut into overlapping equal chunks,
-        sampled as ONE batch of independent utterances (own operator / RIR estimate each), cross-faded back.  Returns (seg, y, pred)."""
+        sampled as ONE batch of independent utterances (own operator / RIR estimate each; ``shared_rir``: all chunks form one group of tied
+        operator rows, one RIR estimate for the clip), cross-faded back.  Returns (seg, y, pred)."""
         from . import longform
         sr = self.args.exp.sample_rate
         seg, y, _, _ = self.prepare_batch([(original, rir, "long.wav")], blind=False)
@@ -293,7 +319,8 @@ class Tester:
             n, clen = parts.shape
             self.sampler.noise = noise(n) if noise is not None else None
             if blind:
-                op = BlindSubbandFiltering(op_hp, sample_rate=sr, num_utts=n, noise=self.sampler.noise, device=self.device, length=clen)
+                op = BlindSubbandFiltering(op_hp, sample_rate=sr, num_utts=n, noise=self.sampler.noise, device=self.device, length=clen,
+                                           groups=[0] * n if shared_rir else None)
                 op.update_H(use_noise=True)
             else:
                 op = RIROperator(op_hp, time_kernel_size=len(rir), sample_rate=sr, device=self.device)

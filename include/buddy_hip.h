@@ -470,6 +470,19 @@ int buddy_blindop_create(int U, int L, int Nf, int E, int num_knots, const float
 int buddy_blindop_destroy(void* handle);
 int buddy_blindop_set_params(void* handle, const float* decay, const float* weights, const float* phases, int reset_adam, void* stream);
 int buddy_blindop_get_params(void* handle, float* decay, float* weights, float* phases, void* stream);
+/* rows of one group share ONE parameter set (decay, weights, phases), one Adam state and hence one H.
+ * group_of_row: host, U ints, group_of_row[0] == 0, non-decreasing, steps of 0 or 1 (groups are contiguous row ranges).
+ * NULL = every row its own group (the state after create).  Anything else: BUDDY_ERR_ARG, nothing changed.
+ * The leader of a group is its first row.  This call and every later buddy_blindop_set_params copy the leader's decay, weights, phases and
+ * the six Adam moment arrays to the members; buddy_blindop_update_H(noise != NULL) reads the leader's noise row for every member.  In
+ * param_grads / optimize every row runs its own forward and backward chain (own x_den, y and regulariser noise row); the phase and knot
+ * gradients of the members are then replaced by their mean (summed in ascending row order in float32, times 1.0f / n, the same bits stored
+ * to every member) before Adam, so members receive equal updates and stay bit-for-bit equal without any copy.  The mean, not the sum: the
+ * balance between w_rec and w_reg stays that of a single row.  Losses, the likelihood entries and everything else stay per row.  Only
+ * parameters and moments are copied: the members' H is that of their OLD parameters until the next buddy_blindop_update_H (optimize and
+ * param_grads rebuild H themselves).  update_H_vjp stays per row (no mean): tied fitting goes through param_grads / optimize.  Drops the
+ * captured optimize graph.  With no group of more than one row, every call launches exactly what it launches without this entry. */
+int buddy_blindop_set_groups(void* handle, const int* group_of_row /*host*/, void* stream);
 /* update_H (:253-285): H = cons(A exp(j phases)); noise != NULL (U, 128*Nf samples) = use_noise=True (phases := angle(H)). */
 int buddy_blindop_update_H(void* handle, const float* noise, void* stream);
 int buddy_blindop_get_H(void* handle, float* H_out, void* stream);
@@ -529,7 +542,8 @@ int buddy_blindop_rec_loss_grad(void* handle, const float* x_den, float weight, 
  * known RIR(s) rir[u * rir_stride + m], m < M (fast_apply_RIR semantics: first L output samples); same loss, same cached y (set_y). */
 int buddy_blindop_fir_loss_grad(void* handle, const float* x_den, const float* rir, long long rir_stride, int M, float weight, float* loss,
                                 float* g_x, void* stream);
-/* one gradient evaluation of optimize_op's objective (H rebuilt from the parameters first); losses = [rec (U), reg (U)] */
+/* one gradient evaluation of optimize_op's objective (H rebuilt from the parameters first); losses = [rec (U), reg (U)].
+ * With groups set (buddy_blindop_set_groups) every member row of a group holds the group-MEAN gradients; the losses stay per row. */
 int buddy_blindop_param_grads(void* handle, const float* x_den, const float* noise, float t_op, float w_rec, float w_reg, float* g_decay,
                               float* g_weights, float* g_phases, float* losses, void* stream);
 /* n_iters iterations of optimize_op: update_H, rec + RIR-noise losses, backward, Adam on [decay, weights, phases], projection.
