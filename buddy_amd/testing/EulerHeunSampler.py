@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import torch
 
+from ..utils.rng import PhiloxStreams
 from .Sampler import Sampler
 
 
@@ -32,8 +33,11 @@ class EulerHeunSampler(Sampler):
 
     def stochastic_timestep(self, x, t, gamma, Snoise=1):
         t_hat = t + gamma * t
+        hip = x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and getattr(self, "use_hip_update", True)
+        if hip and Snoise == 1 and isinstance(self.noise, PhiloxStreams):       # seeded sampling: the draw happens inside the update, one launch and no noise tensor
+            return self.noise.perturb(x, float((t_hat ** 2 - t ** 2) ** (1 / 2))), t_hat
         epsilon = self._randn(x.shape, x.device) * Snoise     # Snoise from the config never reaches here (reference :41,50)
-        if x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and getattr(self, "use_hip_update", True):      # the fused kernels are fp32
+        if hip:      # the fused kernels are fp32
             from . import _hipops
             return _hipops.perturb(x, epsilon, float((t_hat ** 2 - t ** 2) ** (1 / 2))), t_hat
         x_hat = x + ((t_hat ** 2 - t ** 2) ** (1 / 2)) * epsilon

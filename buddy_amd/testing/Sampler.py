@@ -5,6 +5,8 @@ import abc
 
 import torch
 
+from ..utils.rng import SAMPLER, PhiloxStreams
+
 
 class Sampler:
     def __init__(self, model, diff_params, args):
@@ -18,7 +20,8 @@ class Sampler:
         self.T = self.args.tester.sampling_params.T
         self.step_counter = 0
         # optional injected noise: list (one per utterance) of objects with randn(shape) -> CPU tensor.  None = torch RNG,
-        # drawn on the CPU generator and moved, like the reference (EulerHeunSampler.py:21,43).
+        # drawn on the CPU generator and moved, like the reference (EulerHeunSampler.py:21,43).  A utils.rng.PhiloxStreams (seeded sampling,
+        # tester.noise.generator = philox) draws on the device instead: purpose 0, draw 0 = initialize_x, one more per stochastic_timestep.
         self.noise = None
 
     def _randn(self, shape, device):
@@ -27,6 +30,9 @@ class Sampler:
         asynchronous in stream order: a pageable ``.to(device)`` makes the host wait for everything queued before it, i.e. drains the GPU at
         every step boundary (measured ~1 ms of a 107 ms step: copy + relaunch latency with an empty queue)."""
         cuda = torch.device(device).type == "cuda"
+        if isinstance(self.noise, PhiloxStreams):
+            assert len(self.noise) == shape[0], "one noise stream per utterance"
+            return self.noise.randn(SAMPLER, tuple(shape[1:])).to(device)
         if self.noise is None:
             n = torch.randn(shape, pin_memory=cuda)
         else:

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from ... import _lib
+from ...utils.rng import PHASES, RIR_REG, UPDATE_H, PhiloxStreams
 from .shared import Operator
 from ._stft import OperatorSTFT
 
@@ -273,11 +274,17 @@ class BlindSubbandFiltering(SubbandFiltering):
 
     # -- noise plumbing (the reference draws with torch.rand / torch.randn on the fly) --------------------
     def _rand(self, shape):
+        if isinstance(self.noise, PhiloxStreams):       # seeded sampling (utils/rng.py): drawn on the device, one launch for all rows
+            assert len(self.noise) == self.U, "one noise stream per utterance"
+            return self.noise.rand(PHASES, shape).to(self.device)
         if self.noise is None:
             return torch.rand((self.U,) + tuple(shape)).to(self.device)
         return torch.stack([n.rand(shape) for n in self.noise]).to(self.device)
 
     def _randn(self, shape):
+        if isinstance(self.noise, PhiloxStreams):
+            assert len(self.noise) == self.U, "one noise stream per utterance"
+            return self.noise.randn(UPDATE_H, shape).to(self.device)
         if self.noise is None:
             return torch.randn((self.U,) + tuple(shape)).to(self.device)
         return torch.stack([n.randn(shape) for n in self.noise]).to(self.device)
@@ -518,7 +525,9 @@ class BlindSubbandFiltering(SubbandFiltering):
         noise = None
         if self.w_reg is not None:
             Lr = self.length_rir + 1024
-            if self.noise is None:
+            if isinstance(self.noise, PhiloxStreams):
+                noise = self.noise.randn(RIR_REG, (Lr,), count=n_it).to(self.device)      # one draw per Adam iteration, ONE fill for the step
+            elif self.noise is None:
                 noise = torch.randn(n_it, self.U, Lr, device=self.device)      # the reference draws this one on the device too (randn_like(rir_time))
             else:
                 # injected per-utterance streams (tests, the float64 arbiter runs): drawn on the host in reference call order, ONE pinned buffer and

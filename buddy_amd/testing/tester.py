@@ -14,6 +14,7 @@ import torch
 from scipy.io import wavfile
 
 from ..instantiate import instantiate
+from ..utils.rng import factory_from_config
 from .operators.reverb import RIROperator
 from .operators.subband_filtering import BlindSubbandFiltering
 
@@ -47,12 +48,19 @@ class Tester:
         # a batch of >= 2 * sub_batches utterances is sampled as that many concurrent sub-batches on their own HIP streams
         # (testing/concurrent.py; better occupancy); 1 = one batch, one stream.  Default ("auto", tester.sub_batches absent): 2 whenever
         # a group has >= 4 utterances -- the measured optimum (+4-5 %; 4 loses: profiles/r05_sub_batch_sweep.txt).  Results equal the single-batch run
-        # row for row only with per-utterance noise streams (noise_factory); with the torch RNG the draw ORDER differs between the two
+        # row for row only with per-utterance noise streams (tester.noise.generator = philox, or a noise_factory); with the torch RNG the draw ORDER differs between the two
         # modes, so tester.sub_batches=1 is the way to reproduce a same-seed run of an earlier round.  The second sub-batch's network is a
         # replica: it shares the prepared weights and costs only its activation arena
         sb = args.tester.get("sub_batches", None) if hasattr(args.tester, "get") else None
         self.sub_batches = None if sb in (None, "auto") else int(sb)
         self._concurrent = None
+        # seeded sampling (tester.noise.generator = philox, tester.noise.seed; utils/rng.py): every utterance draws from the Philox stream of
+        # (seed, its name), on the GPU -- rows independent of batch, sub-batch policy, file order and world size for every user, not only under an
+        # injected factory.  Default (torch, or no such block): no attribute, the torch generators in the reference's draw order.  A
+        # ``noise_factory`` assigned from outside replaces this one
+        factory = factory_from_config(args.tester, device)
+        if factory is not None:
+            self.noise_factory = factory
 
     # ---- checkpoints (reference :34-67): the EMA weights are what gets loaded -------------------------------------
     def load_checkpoint(self, path):
@@ -92,6 +100,8 @@ class Tester:
     def sample_unconditional(self, mode):
         unc = self.args.tester.unconditional
         audio_len = self.args.exp.audio_len if "audio_len" not in unc.keys() else unc.audio_len
+        if getattr(self, "noise_factory", None) is not None:
+            self.sampler.noise = self.noise_factory([f"unconditional_{i}" for i in range(unc.num_samples)])
         preds = self.sampler.predict_unconditional([unc.num_samples, audio_len], self.device)
         if not self.in_training:
             for i in range(len(preds)):
@@ -315,9 +325,15 @@ class Tester:
         ps = self.args.tester.posterior_sampling
         op_hp = self.args.tester.informed_dereverberation.op_hp
 
+        factory = getattr(self, "noise_factory", None) if noise is None else None
+        done = [0]                      # chunks handed out so far: chunk k of the clip is the stream "long_c<k>.wav" however they are batched
+
         def sample_batch(parts):
             n, clen = parts.shape
             self.sampler.noise = noise(n) if noise is not None else None
+            if factory is not None:
+                self.sampler.noise = factory([f"long_c{done[0] + k}.wav" for k in range(n)])
+                done[0] += n
             if blind:
                 op = BlindSubbandFiltering(op_hp, sample_rate=sr, num_utts=n, noise=self.sampler.noise, device=self.device, length=clen,
                                            groups=[0] * n if shared_rir else None)

@@ -430,6 +430,15 @@ int buddy_flash_attention_bwd_split(const float* q, const float* k, const float*
 int buddy_axpby_rows(const float* x, const float* y, const float* a, const float* c, float* out, int B, int L, void* stream);
 /* stochastic churn: out = x + scale * eps (EulerHeunSampler.py:41-45, scale = sqrt(t_hat^2 - t^2)) */
 int buddy_perturb(const float* x, const float* eps, float scale, float* out, long long n, void* stream);
+/* ---- per-utterance Philox noise streams (seeded sampling, csrc/rng.hip): Philox4x32-10, stream b has the key keys[b] = (k0, k1) (device, (B, 2)
+ * uint32); sample i of draw d of purpose p is word i & 3 of the block with counter (i >> 2, d, p, 0), a pure function of (key, p, d, i).
+ * uniform = (w >> 8) 2^-24 in [0, 1); normals = Box-Muller per word pair (w0, w1) -> (z0, z1), (w2, w3) -> (z2, z3) with u1 = ((w_even >> 8) + 0.5) 2^-24,
+ * u2 = (w_odd >> 8) 2^-24, r = sqrt(-2 log u1), z_even = r cospi(2 u2), z_odd = r sinpi(2 u2); |z| <= 5.887.
+ * fill: out (R, B, n) fp32 contiguous, row (r, b) = draw draw0 + r of stream b; kind 0 normals, 1 uniforms, 2 the raw words bit-cast. */
+int buddy_philox_fill(float* out, int R, int B, int n, const unsigned* keys, unsigned purpose, unsigned draw0, int kind, void* stream);
+/* stochastic churn with the noise generated in registers: out = x + scale * eps, eps = normals of purpose 0, draw `draw` of stream b for row b of
+ * x (B, L); the bits of the perturb entry above applied to the kind-0 fill of the same draw */
+int buddy_perturb_philox(const float* x, const unsigned* keys, unsigned draw, float scale, float* out, int B, int L, void* stream);
 /* fused Euler / Heun update of the DPS sampler (EulerHeunSamplerDPS.py:128-157, edm.py:83-96), per-utterance rows:
  *   x_den' = x_den * den_scale[b] (NULL = 1);  d = -t * (x_den' - x_hat) / t^2 + lh_scale[b] (NULL = 1) * lh (NULL = 0);
  *   out = base + dt * (w_prev * d_prev (NULL = 0) + w_cur * d);   d_out / x_den_out optional.
