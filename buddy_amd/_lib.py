@@ -188,6 +188,23 @@ _SIGS = {
     "buddy_blindop_param_grads": (C.c_int, [C.c_void_p, _f32p, _f32p, C.c_float, C.c_float, C.c_float, _f32p, _f32p, _f32p, _f32p, C.c_void_p]),
     "buddy_blindop_optimize": (C.c_int, [C.c_void_p, _f32p, _f32p, C.c_float, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                          C.c_float, C.c_void_p]),
+    "buddy_conv_c2in": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "buddy_conv_c2out": (C.c_int, [_f32p, C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_void_p]),
+    "buddy_reflect_pad": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _f32p, C.c_void_p]),
+    "buddy_ola": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_void_p]),
+    "buddy_ola_adj": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, C.c_int, C.c_void_p]),
+    "buddy_unpad_adj": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _f32p, _f32p, _f32p, _f32p,
+                                  C.c_void_p]),
+    "buddy_pool2": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),
+    "buddy_up2_acc": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),
+    "buddy_fourier": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_void_p]),
+    "buddy_linear": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "buddy_softmax_rows": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_void_p]),
+    "buddy_softmax_bwd_rows": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_void_p]),
+    "buddy_transpose_sq": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_void_p]),
+    "buddy_mix2": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_longlong, C.c_int, C.c_int, C.c_void_p]),
+    "buddy_axpy": (C.c_int, [_f32p, _f32p, C.c_float, C.c_longlong, C.c_int, C.c_void_p]),
     "buddy_fir": (C.c_int, [_f32p, _f32p, C.c_longlong, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }
 EXPORTED = sorted(_SIGS)

@@ -19,6 +19,7 @@ void launch_mfma_ubench(const float* seed, float* out, int blocks, int iters, un
 void launch_mfma_ubench_bf16(const float* seed, float* out, int blocks, int iters, unsigned long long* clk, hipStream_t st);
 int launch_hbm_ubench(const void* src, void* dst, long long bytes, int mode, int nt, int blocks, hipStream_t st);
 void launch_fir(const float* x, const float* h, long long h_stride, float* y, int B, int L, int M, int adjoint, hipStream_t st);
+void launch_transpose_sq(const float* src, float* dst, int batch, int n, hipStream_t st);
 }
 
 static int finish() {
@@ -820,5 +821,134 @@ int buddy_linear_bwd_x(const float* dy, const float* Wm, const float* x, int sil
   launch_linear_bwd_x(dy, Wm, x, silu_in ? 1 : 0, B, N, K, dx, (hipStream_t)stream);
   return finish();
 }
+
+// ---- the small kernels of the network (ops.hip), one thin entry per launcher: argument checks, the launch, finish()
+#define SMALL_REFUSE(cond, msg) do { if (cond) { set_error(msg); return BUDDY_ERR_ARG; } } while (0)
+
+int buddy_conv_c2in(const float* x, const float* w, const float* bias, const float* add, int add_ld, float* y, int ldY, int B, int H, int W, int Cout,
+                    int taps, int accumulate, void* stream) {
+  SMALL_REFUSE(!x || !w || !y || B < 1 || H < 1 || W < 1 || Cout < 1, "conv_c2in: null pointer or empty shape");
+  SMALL_REFUSE(taps != 1 && taps != 9, "conv_c2in: taps must be 1 or 9");
+  SMALL_REFUSE(Cout % 4 != 0, "conv_c2in: Cout must be a multiple of 4 (a thread writes one channel quad)");
+  SMALL_REFUSE(ldY < Cout || ldY % 4 != 0, "conv_c2in: ldY must be a multiple of 4 floats, at least Cout");
+  SMALL_REFUSE(add && (add_ld < Cout || add_ld % 4 != 0), "conv_c2in: add_ld must be a multiple of 4 floats, at least Cout");
+  launch_conv_c2in(x, w, bias, add, add_ld, y, ldY, B, H, W, Cout, taps, accumulate ? 1 : 0, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_conv_c2out(const float* x, int ldX, const float* w, const float* bias, const float* up_add, float* y, int B, int H, int W, int Cin, int taps,
+                     int accumulate, int form, void* stream) {
+  SMALL_REFUSE(!x || !w || !y || B < 1 || H < 1 || W < 1 || Cin < 1, "conv_c2out: null pointer or empty shape");
+  SMALL_REFUSE(taps != 1 && taps != 9, "conv_c2out: taps must be 1 or 9");
+  SMALL_REFUSE(Cin % 4 != 0, "conv_c2out: Cin must be a multiple of 4 (a lane reads one channel quad)");
+  SMALL_REFUSE(ldX < Cin || ldX % 4 != 0, "conv_c2out: ldX must be a multiple of 4 floats, at least Cin");
+  SMALL_REFUSE(up_add && ((H | W) & 1), "conv_c2out: up_add (at H/2 x W/2) needs even H and W");
+  SMALL_REFUSE(form < -1 || form > 2, "conv_c2out: form must be -1 (process default), 0 (lane group), 1 (tiled) or 2 (strip)");
+  SMALL_REFUSE(form > 0 && (taps != 9 || Cin % 32 != 0), "conv_c2out: the tiled and strip forms compute 9 taps over Cin % 32 == 0 only");
+  Options o = default_options();
+  if (form >= 0) o.c2out_tiled = form;
+  OptScope scope(&o);
+  launch_conv_c2out(x, ldX, w, bias, up_add, y, B, H, W, Cin, taps, accumulate ? 1 : 0, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_reflect_pad(const float* x, float* xp, int B, int L, int pad, int Lp, float scale, const float* scale_b, void* stream) {
+  SMALL_REFUSE(!x || !xp || B < 1 || L < 1 || pad < 0, "reflect_pad: null pointer or empty shape");
+  SMALL_REFUSE(pad >= L, "reflect_pad: pad must be below L (one reflection per side)");
+  SMALL_REFUSE(Lp < (long long)L + 2LL * pad, "reflect_pad: Lp must be at least L + 2 pad");
+  launch_reflect_pad(x, xp, B, L, pad, Lp, scale, scale_b, (hipStream_t)stream);
+  return finish();
+}
+
+static bool stft_geo_ok(int n_fft, int hop, int frames, int ldF, int B, int L, int pad) {
+  return n_fft >= 1 && hop >= 1 && frames >= 1 && ldF >= n_fft && B >= 1 && L >= 1 && pad >= 0;
+}
+
+int buddy_ola(const float* frames, int ldF, int Tp, int n_fft, int hop, const float* inv_env, float* y, int B, int L, int pad, const float* xin,
+              const float* cskip_b, const float* cout_b, void* stream) {
+  SMALL_REFUSE(!frames || !inv_env || !y || !stft_geo_ok(n_fft, hop, Tp, ldF, B, L, pad), "ola: null pointer, empty shape or ldF < n_fft");
+  SMALL_REFUSE(xin && (!cskip_b || !cout_b), "ola: xin needs cskip_b and cout_b");
+  SMALL_REFUSE((long long)L + pad > (long long)n_fft + (long long)hop * (Tp - 1), "ola: L + pad exceeds the envelope's n_fft + hop (Tp - 1) samples");
+  launch_ola(frames, ldF, Tp, n_fft, hop, inv_env, y, B, L, pad, xin, cskip_b, cout_b, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_ola_adj(const float* g, int B, int L, int pad, int Tp, int n_fft, int hop, const float* inv_env, const float* cout_b, float* frames, int ldF,
+                  void* stream) {
+  SMALL_REFUSE(!g || !inv_env || !frames || !stft_geo_ok(n_fft, hop, Tp, ldF, B, L, pad), "ola_adj: null pointer, empty shape or ldF < n_fft");
+  launch_ola_adj(g, B, L, pad, Tp, n_fft, hop, inv_env, cout_b, frames, ldF, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_unpad_adj(const float* dframes, int ldF, int T, int n_fft, int hop, int B, int L, int pad, float scale, const float* scale_b,
+                    const float* g_out, const float* cskip_b, float* dx, void* stream) {
+  SMALL_REFUSE(!dframes || !dx || !stft_geo_ok(n_fft, hop, T, ldF, B, L, pad), "unpad_adj: null pointer, empty shape or ldF < n_fft");
+  SMALL_REFUSE(pad >= L, "unpad_adj: pad must be below L (one reflection per side)");
+  SMALL_REFUSE(g_out && !cskip_b, "unpad_adj: g_out needs cskip_b");
+  launch_unpad_adj(dframes, ldF, T, n_fft, hop, B, L, pad, scale, scale_b, g_out, cskip_b, dx, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_pool2(const float* src, float* dst, int B, int H, int W, int C, float scale, int accumulate, void* stream) {
+  SMALL_REFUSE(!src || !dst || B < 1 || H < 2 || W < 2 || C < 1, "pool2: null pointer or empty shape");
+  SMALL_REFUSE((H | W) & 1, "pool2: H and W must be even");
+  SMALL_REFUSE(C != 2 && C % 4 != 0, "pool2: C must be 2 or a multiple of 4");
+  launch_pool2(src, dst, B, H, W, C, scale, accumulate ? 1 : 0, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_up2_acc(const float* src, float* dst, int B, int Hs, int Ws, int C, float scale, int accumulate, void* stream) {
+  SMALL_REFUSE(!src || !dst || B < 1 || Hs < 1 || Ws < 1 || C < 1, "up2_acc: null pointer or empty shape");
+  SMALL_REFUSE(C % 2 != 0, "up2_acc: C must be even (float2 granularity)");
+  launch_up2_acc(src, dst, B, Hs, Ws, C, scale, accumulate ? 1 : 0, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_fourier(const float* cnoise, const float* Wf, float* out, int B, int nf, void* stream) {
+  SMALL_REFUSE(!cnoise || !Wf || !out || B < 1 || nf < 1, "fourier: null pointer or empty shape");
+  launch_fourier(cnoise, Wf, out, B, nf, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_linear(const float* x, const float* Wm, const float* bias, float* y, int B, int K, int N, int silu_in, void* stream) {
+  SMALL_REFUSE(!x || !Wm || !y || B < 1 || K < 1 || N < 1, "linear: null pointer or empty shape");
+  launch_linear(x, Wm, bias, y, B, K, N, silu_in ? 1 : 0, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_softmax_rows(float* S, int rows, int cols, void* stream) {
+  SMALL_REFUSE(!S || rows < 1 || cols < 1, "softmax_rows: null pointer or empty shape");
+  launch_softmax_rows(S, rows, cols, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_softmax_bwd_rows(const float* P, float* dP, int rows, int cols, void* stream) {
+  SMALL_REFUSE(!P || !dP || rows < 1 || cols < 1, "softmax_bwd_rows: null pointer or empty shape");
+  launch_softmax_bwd_rows(P, dP, rows, cols, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_transpose_sq(const float* src, float* dst, int batch, int n, void* stream) {
+  SMALL_REFUSE(!src || !dst || batch < 1 || n < 1, "transpose_sq: null pointer or empty shape");
+  SMALL_REFUSE(n % 32 != 0, "transpose_sq: n must be a multiple of 32 (whole 32 x 32 tiles)");
+  SMALL_REFUSE(src == dst, "transpose_sq: not in place");
+  SMALL_REFUSE(batch > 65535 || n / 32 > 65535, "transpose_sq: more than 65535 tiles per side or batch entries");
+  launch_transpose_sq(src, dst, batch, n, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_mix2(const float* x, const float* w, const float* b, float* y, long long npix, int transpose, int accumulate, void* stream) {
+  SMALL_REFUSE(!x || !w || !y || npix < 1, "mix2: null pointer or empty shape");
+  launch_mix2(x, w, b, y, npix, transpose ? 1 : 0, accumulate ? 1 : 0, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_axpy(float* dst, const float* src, float alpha, long long n, int accumulate, void* stream) {
+  SMALL_REFUSE(!dst || !src || n < 1, "axpy: null pointer or empty shape");
+  SMALL_REFUSE(n % 4 != 0, "axpy: n must be a multiple of 4 (float4 granularity; a tail would be dropped)");
+  launch_axpy(dst, src, alpha, n, accumulate ? 1 : 0, (hipStream_t)stream);
+  return finish();
+}
+#undef SMALL_REFUSE
 
 }  // extern "C"

@@ -630,7 +630,9 @@ __global__ __launch_bounds__(256) void conv_c2in_reg4_kernel(const float* x, con
   }
 }
 
-// x [B][H][W][Cin] (ldX) -> y [B][H][W][2]; w [TAPS][Cin][2]; LPP = Cin/4 lanes cooperate on one pixel
+// x [B][H][W][Cin] (ldX) -> y [B][H][W][2]; w [TAPS][Cin][2]; LPP = Cin/4 lanes cooperate on one pixel.  The butterfly below is a sum over the
+// pixel's lanes only for LPP a power of two of at most 64 (the lanes of a pixel are then an aligned group inside one wave); the launcher sends every
+// other Cin to conv_c2out_wide_kernel
 template <int TAPS>
 __global__ __launch_bounds__(256) void conv_c2out_kernel(const float* x, int ldX, const float* w, const float* bias, const float* up_add,
                                                          float* y, int B, int H, int W, int Cin, int accumulate) {
@@ -661,6 +663,52 @@ __global__ __launch_bounds__(256) void conv_c2out_kernel(const float* x, int ldX
       }
     }
     for (int off = lpp >> 1; off > 0; off >>= 1) { s0 += __shfl_xor(s0, off, 64); s1 += __shfl_xor(s1, off, 64); }
+    if (sub == 0 && p < npix) {
+      if (bias) { s0 += bias[0]; s1 += bias[1]; }
+      if (up_add) {
+        const float2 u = reinterpret_cast<const float2*>(up_add)[(((long long)b * (H >> 1)) + (h >> 1)) * (W >> 1) + (wq >> 1)];
+        s0 += u.x; s1 += u.y;
+      }
+      float2* o = reinterpret_cast<float2*>(y) + p;
+      if (accumulate) { s0 += o->x; s1 += o->y; }
+      *o = make_float2(s0, s1);
+    }
+  }
+}
+
+// Same op for every other Cin % 4 == 0 (Cin/4 no power of two, or above 64: Cin = 48, 96, 384, 512, ...).  A pixel gets L lanes, L the largest power of
+// two <= 64 that divides Cin/4, so that its lanes are an aligned group inside one wave and 256 / L pixels fill the block exactly; lane `sub` sums the
+// channel quads sub, sub + L, ... of every tap, then the butterfly over the L lanes.  The weights are read per use (L1): the quad count is not a
+// compile-time number here.  Order of a pixel's sum: per lane (tap, quad), then the butterfly.
+template <int TAPS>
+__global__ __launch_bounds__(256) void conv_c2out_wide_kernel(const float* x, int ldX, const float* w, const float* bias, const float* up_add,
+                                                              float* y, int B, int H, int W, int Cin, int L, int accumulate) {
+  const int nq = Cin >> 2, ppb = 256 / L;
+  const int tid = threadIdx.x, sub = tid % L, slot = tid / L;
+  const long long npix = (long long)B * H * W;
+  const long long ngroups = (npix + ppb - 1) / ppb;
+  for (long long gidx = blockIdx.x; gidx < ngroups; gidx += gridDim.x) {
+    const long long p = gidx * ppb + slot;
+    float s0 = 0.f, s1 = 0.f;
+    int b = 0, h = 0, wq = 0;
+    if (p < npix) {
+      long long pix = p;
+      wq = (int)(pix % W); pix /= W; h = (int)(pix % H); b = (int)(pix / H);
+#pragma unroll
+      for (int t = 0; t < TAPS; ++t) {
+        const int dy = (TAPS == 9) ? t / 3 - 1 : 0, dx = (TAPS == 9) ? t % 3 - 1 : 0;
+        if ((unsigned)(h + dy) >= (unsigned)H || (unsigned)(wq + dx) >= (unsigned)W) continue;
+        const float* xr = x + (p + dy * W + dx) * ldX;
+        const float* wt = w + (long long)t * Cin * 2;
+        for (int qd = sub; qd < nq; qd += L) {
+          const float4 v = ld4(xr + qd * 4);
+          const float* wv = wt + qd * 8;
+          s0 += v.x * wv[0] + v.y * wv[2] + v.z * wv[4] + v.w * wv[6];
+          s1 += v.x * wv[1] + v.y * wv[3] + v.z * wv[5] + v.w * wv[7];
+        }
+      }
+    }
+    for (int off = L >> 1; off > 0; off >>= 1) { s0 += __shfl_xor(s0, off, 64); s1 += __shfl_xor(s1, off, 64); }
     if (sub == 0 && p < npix) {
       if (bias) { s0 += bias[0]; s1 += bias[1]; }
       if (up_add) {
@@ -1156,7 +1204,12 @@ void launch_conv_c2in(const float* x, const float* w, const float* bias, const f
 
 void launch_conv_c2out(const float* x, int ldX, const float* w, const float* bias, const float* up_add, float* y, int B, int H, int W, int Cin,
                        int taps, int accumulate, hipStream_t st) {
-  const int ppb = 256 / (Cin / 4);
+  // lane-group form: Cin/4 lanes per pixel where that is a power of two of at most 64 (the butterfly's condition), else the wide kernel with L lanes
+  const int lpp = Cin / 4;
+  const bool group_ok = lpp <= 64 && (lpp & (lpp - 1)) == 0;
+  int L = 1;
+  while (L < 64 && lpp % (2 * L) == 0) L *= 2;
+  const int ppb = 256 / (group_ok ? lpp : L);
   long long groups = ((long long)B * H * W + ppb - 1) / ppb;
   int grid = (int)(groups < 256 * 8 ? groups : 256 * 8);
   const bool tiled = cur_opt().c2out_tiled != 0;
@@ -1166,6 +1219,9 @@ void launch_conv_c2out(const float* x, int ldX, const float* w, const float* bia
   } else if (taps == 9 && tiled && Cin % C2O_CK == 0 && ldX % 4 == 0) {
     const int blocks = B * ((H + C2O_TH - 1) / C2O_TH) * ((W + C2O_TW - 1) / C2O_TW);
     hipLaunchKernelGGL(conv_c2out_tiled_kernel, dim3(blocks), dim3(256), 0, st, x, ldX, w, bias, up_add, y, B, H, W, Cin, accumulate);
+  } else if (!group_ok) {
+    if (taps == 9) hipLaunchKernelGGL(conv_c2out_wide_kernel<9>, dim3(grid), dim3(256), 0, st, x, ldX, w, bias, up_add, y, B, H, W, Cin, L, accumulate);
+    else hipLaunchKernelGGL(conv_c2out_wide_kernel<1>, dim3(grid), dim3(256), 0, st, x, ldX, w, bias, up_add, y, B, H, W, Cin, L, accumulate);
   } else if (taps == 9)
     hipLaunchKernelGGL(conv_c2out_kernel<9>, dim3(grid), dim3(256), 0, st, x, ldX, w, bias, up_add, y, B, H, W, Cin, accumulate);
   else

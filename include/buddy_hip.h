@@ -572,6 +572,48 @@ int buddy_blindop_optimize(void* handle, const float* x_den, const float* noise,
  * above 65 537; Lout != ceil(Lin * up / down); Lin above 2^40 or more than 2^31 - 1 tiles of 1024 outputs over all rows. */
 int buddy_resample(const float* x, int B, long long Lin, const float* h, int Nh, int up, int down, float* y, long long Lout, void* stream);
 
+/* ---- the small fp32 kernels of the network, one entry per launcher (unit tests: tests/test_hip_small_ops.py).  All tensors NHWC with H = time, device
+ * pointers, fp32.  Each entry returns BUDDY_ERR_ARG with a message, with nothing launched, for a null required pointer, an empty shape, or a shape its
+ * kernels cannot compute (named per entry).
+ *
+ * conv_c2in:  x (B,H,W,2) -> y rows of ldY floats, Cout live; w [Cout][taps][2], taps 1 or 9 (3 x 3, zero padding, tap = 3 (dh + 1) + (dw + 1));
+ *             y = conv + bias (NULL = none) + add (rows of add_ld floats, NULL = none) [+ y if accumulate].  Refused: Cout % 4, ldY / add_ld not a
+ *             multiple of 4 or below Cout.
+ * conv_c2out: x rows of ldX floats, Cin live -> y (B,H,W,2); w [taps][Cin][2]; y = conv + bias + up_add (B,H/2,W/2,2 nearest-upsampled) [+ y].
+ *             form: -1 the process default, 0 lane-group kernel, 1 tiled, 2 strip (1 and 2: 9 taps and Cin % 32 == 0).  Refused: Cin % 4, ldX % 4,
+ *             ldX < Cin, odd H or W with up_add. */
+int buddy_conv_c2in(const float* x, const float* w, const float* bias, const float* add, int add_ld, float* y, int ldY, int B, int H, int W, int Cout,
+                    int taps, int accumulate, void* stream);
+int buddy_conv_c2out(const float* x, int ldX, const float* w, const float* bias, const float* up_add, float* y, int B, int H, int W, int Cin, int taps,
+                     int accumulate, int form, void* stream);
+/* STFT glue.  reflect_pad: xp (B,Lp) = scale * scale_b[b] * reflect(x (B,L), pad), zero from L + 2 pad to Lp; refused: pad >= L, Lp < L + 2 pad.
+ * ola: y (B,L)[s] = inv_env[s + pad] * sum_t frames[b][t][s + pad - t hop] over t < Tp (frames rows of ldF floats, n_fft live), then with xin:
+ *      y = cskip_b[b] xin + cout_b[b] y.  inv_env has n_fft + hop (Tp - 1) entries; refused: ldF < n_fft, L + pad beyond the envelope.
+ * ola_adj: the adjoint of ola in `frames` (every float of the (B,Tp,ldF) buffer is written, the row padding with 0).
+ * unpad_adj: dx (B,L) = scale * scale_b[b] * (adjoint of framing(reflect_pad(x))) applied to dframes (B,T,ldF) [+ cskip_b[b] * g_out]; refused: pad >= L. */
+int buddy_reflect_pad(const float* x, float* xp, int B, int L, int pad, int Lp, float scale, const float* scale_b, void* stream);
+int buddy_ola(const float* frames, int ldF, int Tp, int n_fft, int hop, const float* inv_env, float* y, int B, int L, int pad, const float* xin,
+              const float* cskip_b, const float* cout_b, void* stream);
+int buddy_ola_adj(const float* g, int B, int L, int pad, int Tp, int n_fft, int hop, const float* inv_env, const float* cout_b, float* frames, int ldF,
+                  void* stream);
+int buddy_unpad_adj(const float* dframes, int ldF, int T, int n_fft, int hop, int B, int L, int pad, float scale, const float* scale_b,
+                    const float* g_out, const float* cskip_b, float* dx, void* stream);
+/* pool2: dst (B,H/2,W/2,C) = scale * (sum of the 2 x 2 box) [+ dst]; refused: odd H or W, C neither 2 nor a multiple of 4.
+ * up2_acc: dst (B,2Hs,2Ws,C) = scale * nearest(src (B,Hs,Ws,C)) [+ dst]; refused: odd C. */
+int buddy_pool2(const float* src, float* dst, int B, int H, int W, int C, float scale, int accumulate, void* stream);
+int buddy_up2_acc(const float* src, float* dst, int B, int Hs, int Ws, int C, float scale, int accumulate, void* stream);
+/* fourier: out (B,2 nf) = [sin, cos](cnoise[b] * Wf[j] * 2 * pi) (fp32 phase, that product order).  linear: y (B,N) = act(x (B,K)) W^T (N,K) + bias,
+ * act = SiLU if silu_in. */
+int buddy_fourier(const float* cnoise, const float* Wf, float* out, int B, int nf, void* stream);
+int buddy_linear(const float* x, const float* W, const float* bias, float* y, int B, int K, int N, int silu_in, void* stream);
+/* materialised attention: row softmax in place; dP <- P * (dP - sum_j P dP) per row; dst[b] = src[b]^T (n x n; refused: n % 32, in place) */
+int buddy_softmax_rows(float* S, int rows, int cols, void* stream);
+int buddy_softmax_bwd_rows(const float* P, float* dP, int rows, int cols, void* stream);
+int buddy_transpose_sq(const float* src, float* dst, int batch, int n, void* stream);
+/* mix2: y (npix,2) = x W^T + b with W (2,2) (transpose: y = x W, no bias) [+ y].  axpy: dst = alpha * src [+ dst]; refused: n % 4. */
+int buddy_mix2(const float* x, const float* w, const float* b, float* y, long long npix, int transpose, int accumulate, void* stream);
+int buddy_axpy(float* dst, const float* src, float alpha, long long n, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

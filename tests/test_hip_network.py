@@ -125,6 +125,36 @@ def test_forward_vjp_vs_oracle_batched_fused_edm():
     assert rel(gx.cpu().numpy(), gr.numpy()) < TOL
 
 
+@pytest.mark.parametrize("nf,ch_mult,L", [(128, (1, 3), 1000), (256, (1, 2), 1000), (128, (3, 3), 500)])
+def test_wide_levels_vs_oracle(nf, ch_mult, L):
+    """Level widths of 384 and 512 channels (96 and 128 channel quads: no power of two of at most 64): forward and input-VJP against the float64
+    oracle on synth weights; n_fft = 126, hop = 32, B = 2, the default attention.  With (1, 3) and (1, 2) the wide level is the last one: its
+    pyramid head runs the 3 x 3 Cin -> 2 convolution at 384 / 512 channels, its bottleneck attention the materialised form.  The Combine of the
+    input pyramid sits between two levels and has the width of the upper one, so (3, 3) is the network whose input-VJP runs the one-tap Cin -> 2
+    convolution at 384 channels (L = 500: 16 frames)."""
+    from oracle import ncsnpp_ref
+    from oracle.precision import fp64
+    from buddy_amd.synth import synth_state_dict
+    n_fft, hop, B, seed = 126, 32, 2, 21
+    net = build(nf, n_fft, hop, seed, ch_mult=ch_mult)
+    sd = synth_state_dict(seed, nf, tuple(ch_mult), 1)
+    rs = np.random.RandomState(nf)
+    x = (0.3 * rs.standard_normal((B, L))).astype(np.float32)
+    cot = rs.standard_normal((B, L)).astype(np.float32)
+    cn = np.array([-0.8, -0.2], dtype=np.float32)
+    with fp64():
+        Pr = ncsnpp_ref.to_torch(sd)
+        xr = torch.from_numpy(x).double().requires_grad_(True)
+        yr = ncsnpp_ref.ncsnpp_time(Pr, xr, torch.from_numpy(cn).double(), n_fft, hop, tuple(ch_mult), 1)
+        gr, = torch.autograd.grad(yr, xr, torch.from_numpy(cot).double())
+    xg = torch.from_numpy(x).cuda().requires_grad_(True)
+    y = net(xg, torch.from_numpy(cn).cuda())
+    gx, = torch.autograd.grad(y, xg, torch.from_numpy(cot).cuda())
+    ey, eg = rel(y.detach().cpu().numpy(), yr.detach().numpy()), rel(gx.cpu().numpy(), gr.numpy())
+    print(f"wide levels nf={nf} ch_mult={ch_mult}: forward {ey:.2e} vjp {eg:.2e}")
+    assert ey < TOL and eg < TOL
+
+
 def test_batch_independence_and_determinism():
     """per-utterance semantics: row b of a batched call equals the B=1 call bit-for-bit; repeated calls are bit-identical."""
     net = build(32, 510, 128, 2)
