@@ -66,6 +66,10 @@ _SIGS = {
     "buddy_wpe_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int]),
     "buddy_wpe_dereverb": (C.c_int, [_f32p, _f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "buddy_resample": (C.c_int, [_f32p, C.c_int, C.c_longlong, _f32p, C.c_int, C.c_int, C.c_int, _f32p, C.c_longlong, C.c_void_p]),
+    "buddy_row_argmax_abs": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "buddy_fir_bank": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_longlong, _f32p, C.c_int, C.c_int, _f32p, C.c_longlong, C.c_void_p]),
+    "buddy_decay_metrics": (C.c_int, [_f32p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, _f32p, C.c_void_p]),
+    "buddy_decay_tile": (C.c_int, []),
     "buddy_prof_collect_wino4": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                            C.POINTER(C.c_longlong)]),
     "buddy_prof_collect_hbm": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),

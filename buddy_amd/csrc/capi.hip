@@ -4,6 +4,7 @@
 #include "net.h"
 
 #include <cstring>
+#include <vector>
 
 using namespace buddy;
 
@@ -653,6 +654,77 @@ int buddy_resample(const float* x, int B, long long Lin, const float* h, int Nh,
   if (Lout != (Lin * up + down - 1) / down) return bad("Lout is not ceil(Lin * up / down)");
   if (resample_tiles(Lout) * B > 0x7fffffffLL) return bad("more output tiles than one grid holds");
   launch_resample(x, B, Lin, h, Nh, up, down, y, Lout, (hipStream_t)stream);
+  return finish();
+}
+
+// ---- room-acoustic analysis of RIR rows (acoustics.hip) ----
+// The row lengths are a device array: one small copy to the host (after the work queued on `stream`) so that a bad length or a stride below the
+// longest row is refused before anything is launched.  On a host without a HIP device no device pointer exists and the array is read where it lies.
+static int fetch_lengths(const int* lens, int B, std::vector<int>& host, void* stream, const char* who) {
+  host.resize(B);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
+    (void)hipGetLastError();
+    std::memcpy(host.data(), lens, sizeof(int) * (size_t)B);
+    return BUDDY_OK;
+  }
+  hipError_t e = hipMemcpyAsync(host.data(), lens, sizeof(int) * (size_t)B, hipMemcpyDefault, (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  if (e != hipSuccess) { set_error(std::string(who) + ": reading the row lengths: " + hipGetErrorString(e)); return BUDDY_ERR_HIP; }
+  return BUDDY_OK;
+}
+
+int buddy_decay_tile(void) { return decay_tile(); }
+
+int buddy_row_argmax_abs(const float* h, const int* lens, int B, long long ldh, int* n0, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_row_argmax_abs: ") + why); return BUDDY_ERR_ARG; };
+  if (!h || !lens || !n0) return bad("null pointer");
+  if (B < 1 || B > 65535) return bad("B must be in 1..65535");
+  if (ldh < 1) return bad("ldh must be >= 1");
+  std::vector<int> len;
+  if (int rc = fetch_lengths(lens, B, len, stream, "buddy_row_argmax_abs")) return rc;
+  for (int b = 0; b < B; ++b) {
+    if (len[b] < 1 || len[b] > (1 << 30)) return bad("every lens[b] must be in 1..2^30");
+    if (len[b] > ldh) return bad("ldh is smaller than the longest row");
+  }
+  launch_row_argmax_abs(h, lens, B, ldh, n0, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_fir_bank(const float* h, const int* lens, int B, long long ldh, const float* bank, int nb, int Nh, float* g, long long ldg, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_fir_bank: ") + why); return BUDDY_ERR_ARG; };
+  if (!h || !lens || !bank || !g) return bad("null pointer");
+  if (B < 1 || B > 65535 || nb < 1 || nb > 65535) return bad("B and nb must be in 1..65535");
+  if (Nh < 1 || Nh % 2 == 0 || Nh > 65537) return bad("Nh must be odd and <= 65537");
+  if (ldh < 1 || ldg < 1) return bad("ldh and ldg must be >= 1");
+  std::vector<int> len;
+  if (int rc = fetch_lengths(lens, B, len, stream, "buddy_fir_bank")) return rc;
+  const int P = (Nh - 1) / 2;
+  int longest = 0;
+  for (int b = 0; b < B; ++b) {
+    if (len[b] < 1 || len[b] > (1 << 30)) return bad("every lens[b] must be in 1..2^30");
+    if (len[b] > ldh) return bad("ldh is smaller than the longest row");
+    if ((long long)len[b] + P > ldg) return bad("ldg is smaller than the longest row plus (Nh - 1) / 2");
+    longest = len[b] > longest ? len[b] : longest;
+  }
+  launch_fir_bank(h, lens, B, ldh, longest, bank, nb, Nh, g, ldg, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_decay_metrics(const float* g, const int* lens_g, const int* n0, int B, int nb, long long ldg, int fs, double* out, int* flags, float* edc_db,
+                        void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_decay_metrics: ") + why); return BUDDY_ERR_ARG; };
+  if (!g || !lens_g || !n0 || !out || !flags) return bad("null pointer");
+  if (B < 1 || B > 65535 || nb < 1 || nb > 65535 || (long long)B * nb > 0x7fffffffLL) return bad("B and nb must be in 1..65535");
+  if (fs < 1) return bad("fs must be >= 1");
+  if (ldg < 1) return bad("ldg must be >= 1");
+  std::vector<int> len;
+  if (int rc = fetch_lengths(lens_g, B, len, stream, "buddy_decay_metrics")) return rc;
+  for (int b = 0; b < B; ++b) {
+    if (len[b] < 1 || len[b] > (1 << 30) + 32768) return bad("every lens_g[b] must be in 1..2^30 + 2^15");
+    if (len[b] > ldg) return bad("ldg is smaller than the longest row");
+  }
+  launch_decay_metrics(g, lens_g, n0, B, nb, ldg, fs, out, flags, edc_db, (hipStream_t)stream);
   return finish();
 }
 

@@ -177,6 +177,13 @@ void launch_wpe_dereverb(const float* y, float* out, void* work, int B, int L, i
 // rational polyphase resampler (resample.hip): y[b][n] = sum_m x[b][m] h[n*down - m*up + (Nh-1)/2], Lout = ceil(Lin*up/down); arguments checked by the C entry
 long long resample_tiles(long long Lout);
 void launch_resample(const float* x, int B, long long Lin, const float* h, int Nh, int up, int down, float* y, long long Lout, hipStream_t st);
+// room-acoustic analysis of RIR rows (acoustics.hip): ragged rows, device length arrays; arguments, lengths and strides checked by the C entries
+int decay_tile();                            // samples per tile of the decay kernel's backward sweep
+void launch_row_argmax_abs(const float* h, const int* lens, int B, long long ldh, int* n0, hipStream_t st);
+void launch_fir_bank(const float* h, const int* lens, int B, long long ldh, int max_len, const float* bank, int nb, int Nh, float* g, long long ldg,
+                     hipStream_t st);
+void launch_decay_metrics(const float* g, const int* lens_g, const int* n0, int B, int nb, long long ldg, int fs, double* out, int* flags, float* edc_db,
+                          hipStream_t st);
 void launch_axpy(float* dst, const float* src, float alpha, long long n, int accumulate, hipStream_t st);
 // fir=True resampling with the (1,3,3,1) kernel: (H,W)->(2H,2W) / (H,W)->(H/2,W/2); adjoints: up^T = 4 down, down^T = up / 4
 void launch_fir_up2(const float* x, float* y, int B, int H, int W, int C, float scale, int accumulate, hipStream_t st);

@@ -238,6 +238,7 @@ class BlindSubbandFiltering(SubbandFiltering):
         else:
             t60, wts = op_hp.init_params.T60_breakpoints, op_hp.init_params.multiexp_weighting
         frame_rate = self.sample_rate / op_hp.hop
+        self.knots, self.frame_rate = knots, frame_rate
         decay = 6.908 / (torch.tensor(t60, dtype=torch.float32) * frame_rate)
         self.num_exponentials = decay.shape[0]
         self.max_decay = 6.908 / (op_hp.T60min * frame_rate)
@@ -304,6 +305,13 @@ class BlindSubbandFiltering(SubbandFiltering):
         p = torch.empty(self.U, F, self.Nf, device=self.device)
         _lib.check(_lib.load().buddy_blindop_get_params(self._h, _lib.ptr(d), _lib.ptr(w), _lib.ptr(p), _lib.stream_ptr()))
         return d, w, p
+
+    def acoustic_parameters(self):
+        """The fitted room model in acoustic units, per operator row and exponential, on the CPU in float64: ``freqs`` (the NB interior knots of
+        ``EQ_freqs`` in Hz; the two extremes are fixed), ``T60`` (U, E, NB) in seconds = 6.908 / (decay * frame_rate), the inverse of the
+        constructor's formula, and ``weights`` (U, E, NB), as the library handle holds them (``_get()``).  Rows of one group hold the same values."""
+        d, w, _ = self._get()
+        return {"freqs": list(self.knots[1:-1]), "T60": 6.908 / (d.double().cpu() * self.frame_rate), "weights": w.double().cpu()}
 
     # The reference keeps its parameters as torch tensors the sampler's Adam holds on to (``Adam(operator.params + operator.params_phases)``,
     # EulerHeunSamplerDPS.py:193) and flips ``requires_grad`` on (:78-81).  Here the parameters live in the library handle; ``params`` /

@@ -33,6 +33,16 @@ def shared_rir_options(rr):
     return bool(rr.get("shared_rir", False)), int(rr.get("shared_rir_max_chunks", 32))
 
 
+def rir_report_options(tester_cfg):
+    """(use, octave centres) of the ``rir_report`` block of a tester config; a config written before the block existed means (False, the octaves)"""
+    from ..utils.acoustics import OCTAVES
+    rp = tester_cfg.get("rir_report", None)
+    if rp is None:
+        return False, OCTAVES
+    c = rp.get("centres", None)
+    return bool(rp.get("use", False)), OCTAVES if c is None else tuple(float(v) for v in c)
+
+
 class Tester:
     def __init__(self, args, network, diff_params, test_set=None, device=None, in_training=False, batch_size=1, rank=0, world_size=1):
         self.args = args
@@ -148,6 +158,8 @@ class Tester:
         mine = [i for i in range(len(self.test_set)) if i % self.world_size == self.rank]
         sr = self.args.exp.sample_rate
         local = {}
+        report = blind and rir_report_options(self.args.tester)[0] and not self.in_training and bool(self.paths)
+        rep = []         # room-acoustics report: (name, estimated RIR, true RIR, the operator's parameters of that row) per written RIR wav
         for s in range(0, len(mine), self.batch_size):
             idx = mine[s:s + self.batch_size]
             items = [self.test_set[i] + (i,) for i in idx]
@@ -167,6 +179,7 @@ class Tester:
                     seg, y, operator, rirs = self.prepare_batch(grp, blind, noise=self.sampler.noise)
                     pred = self.sampler.predict_conditional(y, operator, shape=(len(grp), L), blind=blind)
                     est = self.sampler.operator.get_time_RIR().detach().cpu() if blind else None
+                par = self._operator_parameters(S) if report else None
                 for b, (_, _, filename) in enumerate(grp):
                     name = os.path.basename(filename)[:-4]
                     self.results.append((name, pred[b].detach().cpu()))
@@ -179,12 +192,48 @@ class Tester:
                     write_audio_file(rirs[b], sr, name, path=self.paths[mode + "true_rir"])
                     if blind:
                         write_audio_file(est[b] if est.dim() == 2 else est, sr, name, path=self.paths[mode + "estimated_rir"])
+                    if report:
+                        rep.append((name, est[b] if est.dim() == 2 else est, rirs[b], {k: v if k == "freqs" else v[b] for k, v in par.items()}))
                     print(p)
+        if report:
+            self._write_rir_report(mode, rep, sr)
         # utterance-batch data parallelism: ONE gather at the end of the run (RCCL over xGMI on the GPU box) -- afterwards every rank, in
         # particular rank 0, holds all predictions in utterance order, independent of the world size
         from .. import dist as bdist
         rows = bdist.gather_ragged([local[i] for i in mine], len(self.test_set), self.rank, self.world_size, device=self.device)
         self.gathered = [(os.path.basename(self.test_set[i][2])[:-4], rows[i].detach().cpu()) for i in range(len(self.test_set))]
+
+    def _operator_parameters(self, S):
+        """``acoustic_parameters()`` of the operators the last group was sampled with, rows in order (``S`` > 1: one operator per sub-batch)"""
+        ops = [sb.s.operator for sb in self._concurrent.last] if S > 1 else [self.sampler.operator]
+        pars = [op.acoustic_parameters() for op in ops]
+        return {"freqs": pars[0]["freqs"], "T60": torch.cat([p["T60"] for p in pars]), "weights": torch.cat([p["weights"] for p in pars])}
+
+    def _write_rir_report(self, mode, rep, sr):
+        """Room-acoustics report of a blind mode (``tester.rir_report.use``; utils/acoustics.py), once per mode after sampling: ``acoustics.csv`` (the
+        six ISO 3382-1 values per written RIR wav and band; with true RIRs also theirs and the errors of the estimate) and ``parameters.csv`` (the
+        fitted T60 and weight per knot) next to the RIR wavs.  ``rep``: (wav name, estimated RIR, true RIR or None, parameters of that operator
+        row).  Every rank writes its own rows (``acoustics.rank<r>.csv`` when there are several); nothing is gathered."""
+        from ..utils import acoustics
+        self.rir_report = None
+        if not rep:
+            return
+        centres = rir_report_options(self.args.tester)[1]
+        names = [r[0] for r in rep]
+        est = acoustics.rir_acoustics(torch.stack([r[1].float() for r in rep]).to(self.device), int(sr), centres=centres)
+        true = None
+        if rep[0][2] is not None:          # true RIRs of different lengths: one zero-padded batch, analysed up to each row's own length
+            lens = [int(r[2].numel()) for r in rep]
+            rows = torch.zeros(len(rep), max(lens), dtype=torch.float32)
+            for b, r in enumerate(rep):
+                rows[b, :lens[b]] = r[2].flatten()
+            true = acoustics.rir_acoustics(rows.to(self.device), int(sr), lens=lens, centres=centres)
+        params = {"freqs": rep[0][3]["freqs"], "T60": torch.stack([r[3]["T60"] for r in rep]), "weights": torch.stack([r[3]["weights"] for r in rep])}
+        tag = f".rank{self.rank}" if self.world_size > 1 else ""
+        base = self.paths[mode + "estimated_rir"]
+        acoustics.write_report(os.path.join(base, f"acoustics{tag}.csv"), acoustics.report_rows(names, est, true))
+        acoustics.write_parameters(os.path.join(base, f"parameters{tag}.csv"), acoustics.parameter_rows(names, params))
+        self.rir_report = dict(names=names, estimated=est, true=true, parameters=params)
 
     def _sample_concurrent(self, grp, L, blind, S):
         """one equal-length group as ``S`` concurrent sub-batches (testing/concurrent.py)"""
@@ -232,8 +281,10 @@ class Tester:
                 noises = None if noise is None else [noise[lo:hi] for lo, hi in parts]
                 ops = [self._blind_operator(hi - lo, L, None if noise is None else noise[lo:hi],
                                             None if groups is None else [g - groups[lo] for g in groups[lo:hi]]) for lo, hi in parts]
+                self._sampled_concurrently = True
                 return self._predict_concurrent([y[lo:hi].contiguous() for lo, hi in parts], ops, True, noises, S)
             operator = self._blind_operator(n, L, noise, groups)
+        self._sampled_concurrently = False
         pred = self.sampler.predict_conditional(y.contiguous(), operator, shape=(n, L), blind=True)
         est = self.sampler.operator.get_time_RIR().detach().cpu()
         return pred, est if est.dim() == 2 else est[None]
@@ -285,14 +336,20 @@ class Tester:
             cuts, batches = longform.pool_plan(lengths, chunk, overlap, self.batch_size)
         for f, (starts, clen) in zip(files, cuts):
             f["parts"] = torch.stack([f["y"][s:s + clen] for s in starts])
-            f["est"], f["rir"] = [None] * len(starts), [None] * len(starts)
+            f["est"], f["rir"], f["par"] = [None] * len(starts), [None] * len(starts), [None] * len(starts)
+        writing = not self.in_training and bool(self.paths)
+        report = writing and rir_report_options(self.args.tester)[0]
         for batch in batches:
             yb = torch.stack([files[f]["parts"][k] for f, k in batch])
             pred, est = self.sample_observed(yb, [f"{files[f]['name']}_c{k}.wav" for f, k in batch],
                                              groups=longform.shared_groups(cuts, batch, max_rows) if shared else None)
             for b, (f, k) in enumerate(batch):
                 files[f]["est"][k], files[f]["rir"][k] = pred[b].detach(), est[b]
-        writing = not self.in_training and bool(self.paths)
+            if report:
+                par = self._operator_parameters(len(self._concurrent.last) if self._sampled_concurrently else 1)
+                for b, (f, k) in enumerate(batch):
+                    files[f]["par"][k] = {key: v if key == "freqs" else v[b] for key, v in par.items()}
+        rep = []
         self.rirs = {f["name"]: list(f["rir"]) for f in files}
         for f, (starts, _) in zip(files, cuts):
             est = torch.stack(f["est"])
@@ -309,10 +366,14 @@ class Tester:
             if shared:       # one estimate per file (per run where shared_rir_max_chunks cut it): the chunks of a run hold the same RIR
                 for j, (lo, _) in enumerate(f["runs"]):
                     write_audio_file(f["rir"][lo], sr, f["name"] if len(f["runs"]) == 1 else f"{f['name']}_r{j}", path=self.paths[mode + "estimated_rir"])
+                    rep.append((f["name"] if len(f["runs"]) == 1 else f"{f['name']}_r{j}", f["rir"][lo], None, f["par"][lo]))
             else:
                 for k, r in enumerate(f["rir"]):
                     write_audio_file(r, sr, f"{f['name']}_c{k}", path=self.paths[mode + "estimated_rir"])
+                    rep.append((f"{f['name']}_c{k}", r, None, f["par"][k]))
             print(p)
+        if report:
+            self._write_rir_report(mode, rep, sr)
 
     def dereverberate_long(self, original, rir, blind, chunk_seconds=8.0, overlap_seconds=1.0, noise=None, shared_rir=False):
         """Long-form policy (testing/longform.py): one long clean/RIR pair -> the reverberant signal cut into overlapping equal chunks,

@@ -572,6 +572,37 @@ int buddy_blindop_optimize(void* handle, const float* x_den, const float* noise,
  * above 65 537; Lout != ceil(Lin * up / down); Lin above 2^40 or more than 2^31 - 1 tiles of 1024 outputs over all rows. */
 int buddy_resample(const float* x, int B, long long Lin, const float* h, int Nh, int up, int down, float* y, long long Lout, void* stream);
 
+/* ---- room-acoustic analysis of room impulse responses (buddy_amd/utils/acoustics.py; the reference writes its RIR estimates
+ * to wav files and analyses nothing).  RIR rows h (B, <= ldh) are ragged inside a common stride: lens[b] samples of row b are valid, nothing is
+ * read past h[b][lens[b] - 1].  lens, lens_g and n0 are DEVICE arrays of int32; every entry copies its length array to the host once (after the
+ * work queued on `stream`) to check it.  BUDDY_ERR_ARG, with nothing launched, for: a null pointer (edc_db may be NULL); B or nb outside
+ * 1..65535; Nh even or above 65 537; a length below 1 or above 2^30; a stride smaller than the longest row it holds; fs < 1.
+ *
+ * buddy_row_argmax_abs: n0[b] = the FIRST index of max |h[b][n]|, n < lens[b] (fp32 compare): the direct path of a peak-aligned RIR.
+ *
+ * buddy_fir_bank: zero-phase band signals g (B, nb, ldg) of a bank (nb, Nh) of odd-length FIR rows sharing one Nh, centre P = (Nh - 1) / 2:
+ *   g[b][k][n] = sum_j bank[k][j] * h[b][n - j + P],   n in [0, lens[b] + P),   zero extension
+ * (the tail of P samples past the end of h is kept, the pre-ringing before index 0 is dropped).  fp32 accumulation in ascending input index;
+ * zero taps are skipped, so a unit impulse at j = P copies h bit for bit.  ldg >= max lens[b] + P; nothing is written past g[b][k][lens[b] + P - 1].
+ *
+ * buddy_decay_metrics: per (row, band) of g with lens_g[b] (= lens[b] + P) valid samples and the row's direct-path index n0[b] (clamped to the
+ * row): w = round(0.0025 fs) = (fs + 200) / 400, analysis start ns = max(n0 - w, 0), t = (n - ns) / fs; Schroeder curve
+ * D[n] = 10 log10(sum_{m >= n} g[m]^2 / sum_{m >= ns} g[m]^2), n >= ns; least-squares lines D ~ a + s t over the samples with lo <= D[n] <= hi.
+ *   out (B, nb, 6) doubles: EDT (0..-10 dB), T20 (-5..-25), T30 (-5..-35), each -60 / s [s]; C50 [dB], split at ns + round(0.05 fs) = ns + (fs + 10) / 20;
+ *     DRR [dB], direct part ns <= n <= n0 + w; centre time Ts [s].  NaN where undefined: fewer than two samples in a range or s >= 0, a zero
+ *     denominator, an all-zero row (every value NaN, which disturbs no other row).
+ *   flags (B, nb) int32: bit q (0..5) = out[..][q] is defined; bit 6 + q (q = 0..2) = the fit of decay time q is VALID: the decay left between
+ *     its last fitted sample n_hi and the end of the row at the fitted slope, |s| (lens_g[b] - 1 - n_hi) / fs, is at least 10 dB (a truncated
+ *     response bends the curve down by 10 log10(1 - 10^(-R/10)) dB, below 0.5 dB for R >= 9.6 dB).  The value is written either way.
+ *   edc_db (B, nb, ldg) fp32 or NULL: D[n] for ns <= n < lens_g[b], NaN for n < ns, untouched from lens_g[b] on.
+ * One workgroup per (row, band); every sum in double; no atomics, no workspace.  buddy_decay_tile: samples per tile of its backward sweep (the
+ * lengths around which the unit tests place their rows). */
+int buddy_row_argmax_abs(const float* h, const int* lens, int B, long long ldh, int* n0, void* stream);
+int buddy_fir_bank(const float* h, const int* lens, int B, long long ldh, const float* bank, int nb, int Nh, float* g, long long ldg, void* stream);
+int buddy_decay_metrics(const float* g, const int* lens_g, const int* n0, int B, int nb, long long ldg, int fs, double* out, int* flags, float* edc_db,
+                        void* stream);
+int buddy_decay_tile(void);
+
 /* ---- the small fp32 kernels of the network, one entry per launcher (unit tests: tests/test_hip_small_ops.py).  All tensors NHWC with H = time, device
  * pointers, fp32.  Each entry returns BUDDY_ERR_ARG with a message, with nothing launched, for a null required pointer, an empty shape, or a shape its
  * kernels cannot compute (named per entry).
