@@ -70,6 +70,19 @@ _SIGS = {
     "buddy_fir_bank": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_longlong, _f32p, C.c_int, C.c_int, _f32p, C.c_longlong, C.c_void_p]),
     "buddy_decay_metrics": (C.c_int, [_f32p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, _f32p, C.c_void_p]),
     "buddy_decay_tile": (C.c_int, []),
+    "buddy_metrics_tile": (C.c_int, []),
+    "buddy_pair_moments": (C.c_int, [_f32p, _f32p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "buddy_stoi_select_workspace": (C.c_longlong, [C.c_int, C.c_longlong]),
+    "buddy_stoi_select": (C.c_int, [_f32p, _f32p, C.c_void_p, C.c_int, C.c_longlong, _f32p, _f32p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "buddy_band_spectra": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_longlong, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, _f32p, C.c_longlong,
+                                     C.c_void_p]),
+    "buddy_stoi_scores_workspace": (C.c_longlong, [C.c_int, C.c_int]),
+    "buddy_stoi_scores": (C.c_int, [_f32p, _f32p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "buddy_lsd_workspace": (C.c_longlong, [C.c_int, C.c_longlong]),
+    "buddy_frame_power": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "buddy_lsd": (C.c_int, [_f32p, _f32p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
+                            C.c_void_p]),
     "buddy_prof_collect_wino4": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                            C.POINTER(C.c_longlong)]),
     "buddy_prof_collect_hbm": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),

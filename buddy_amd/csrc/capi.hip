@@ -728,6 +728,106 @@ int buddy_decay_metrics(const float* g, const int* lens_g, const int* n0, int B,
   return finish();
 }
 
+// ---- objective evaluation of (estimate, clean) pairs (metrics.hip) ----
+// the lengths of ragged rows, fetched once: each in lo..2^30 and within the stride; *longest receives the largest
+static int check_rows(const int* lens, int B, long long ld, int lo, void* stream, const char* who, int* longest) {
+  auto bad = [who](const char* why) { set_error(std::string(who) + ": " + why); return BUDDY_ERR_ARG; };
+  if (B < 1 || B > 65535) return bad("B must be in 1..65535");
+  if (ld < 1) return bad("the row stride must be >= 1");
+  std::vector<int> len;
+  if (int rc = fetch_lengths(lens, B, len, stream, who)) return rc;
+  *longest = 0;
+  for (int b = 0; b < B; ++b) {
+    if (len[b] < lo || len[b] > (1 << 30)) return bad(lo ? "every length must be in 1..2^30" : "every length must be in 0..2^30");
+    if (len[b] > ld) return bad("the row stride is smaller than the longest row");
+    *longest = len[b] > *longest ? len[b] : *longest;
+  }
+  return BUDDY_OK;
+}
+static long long at_least_one(long long v) { return v > 1 ? v : 1; }
+
+int buddy_metrics_tile(void) { return metrics_tile(); }
+
+int buddy_pair_moments(const float* e, const float* x, const int* lens, int B, long long ld, double* out, int* flags, void* stream) {
+  if (!e || !x || !lens || !out || !flags) { set_error("buddy_pair_moments: null pointer"); return BUDDY_ERR_ARG; }
+  int longest;
+  if (int rc = check_rows(lens, B, ld, 1, stream, "buddy_pair_moments", &longest)) return rc;
+  launch_pair_moments(e, x, lens, B, ld, out, flags, (hipStream_t)stream);
+  return finish();
+}
+
+long long buddy_stoi_select_workspace(int B, long long max_len) {
+  if (B < 1 || max_len < 1 || max_len > (1LL << 30)) return -1;
+  return 8LL * B * at_least_one(metrics_frames(max_len));
+}
+
+int buddy_stoi_select(const float* x, const float* e, const int* lens, int B, long long ld, float* xo, float* eo, long long ldo, int* lens_out, int* K, int* F,
+                      int* src, long long ldf, void* ws, long long ws_bytes, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_stoi_select: ") + why); return BUDDY_ERR_ARG; };
+  if (!x || !e || !lens || !xo || !eo || !lens_out || !K || !F || !src || !ws) return bad("null pointer");
+  int longest;
+  if (int rc = check_rows(lens, B, ld, 1, stream, "buddy_stoi_select", &longest)) return rc;
+  const long long maxF = metrics_frames(longest);
+  if (ldf < at_least_one(maxF)) return bad("ldf is smaller than the frames of the longest row");
+  if (ldo < 1 || (maxF > 0 && ldo < (maxF - 1) * 128 + 256)) return bad("ldo is smaller than the full frames of the longest row");
+  if (ws_bytes < 8LL * B * ldf) return bad("the workspace is smaller than 8 B ldf bytes");
+  launch_stoi_select(x, e, lens, B, ld, longest, xo, eo, ldo, lens_out, K, F, src, ldf, (double*)ws, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_band_spectra(const float* x, const int* lens, int B, long long ld, const int* lo, const int* hi, int J, float* out, long long ldm, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_band_spectra: ") + why); return BUDDY_ERR_ARG; };
+  if (!x || !lens || !lo || !hi || !out) return bad("null pointer");
+  if (J < 1 || J > 32) return bad("J must be in 1..32");
+  for (int j = 0; j < J; ++j)
+    if (lo[j] < 0 || hi[j] < lo[j] || hi[j] > 257) return bad("every band must be bins [lo, hi) with 0 <= lo <= hi <= 257");
+  int longest;
+  if (int rc = check_rows(lens, B, ld, 0, stream, "buddy_band_spectra", &longest)) return rc;      // a row without a kept frame has length 0
+  if (ldm < at_least_one(metrics_frames(longest))) return bad("ldm is smaller than the frames of the longest row");
+  launch_band_spectra(x, lens, B, ld, longest, lo, hi, J, out, ldm, (hipStream_t)stream);
+  return finish();
+}
+
+long long buddy_stoi_scores_workspace(int B, int max_frames) {
+  if (B < 1 || max_frames < 0) return -1;
+  return 16LL * B * at_least_one((long long)max_frames - 29);
+}
+
+int buddy_stoi_scores(const float* X, const float* Y, const int* lens_m, int B, int J, long long ldm, double* out, int* flags, void* ws, long long ws_bytes,
+                      void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_stoi_scores: ") + why); return BUDDY_ERR_ARG; };
+  if (!X || !Y || !lens_m || !out || !flags || !ws) return bad("null pointer");
+  if (J < 1 || J > 32) return bad("J must be in 1..32");
+  int longest;
+  if (int rc = check_rows(lens_m, B, ldm, 0, stream, "buddy_stoi_scores", &longest)) return rc;
+  if (ws_bytes < buddy_stoi_scores_workspace(B, longest)) return bad("the workspace is smaller than buddy_stoi_scores_workspace(B, longest row)");
+  launch_stoi_scores(X, Y, lens_m, B, J, ldm, longest, out, flags, (double*)ws, (hipStream_t)stream);
+  return finish();
+}
+
+long long buddy_lsd_workspace(int B, long long max_len) { return buddy_stoi_select_workspace(B, max_len); }
+
+int buddy_frame_power(const float* x, const int* lens, int B, long long ld, double* mean_p, void* ws, long long ws_bytes, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_frame_power: ") + why); return BUDDY_ERR_ARG; };
+  if (!x || !lens || !mean_p || !ws) return bad("null pointer");
+  int longest;
+  if (int rc = check_rows(lens, B, ld, 1, stream, "buddy_frame_power", &longest)) return rc;
+  if (ws_bytes < buddy_lsd_workspace(B, longest)) return bad("the workspace is smaller than buddy_lsd_workspace(B, longest row)");
+  launch_frame_power(x, lens, B, ld, longest, mean_p, (double*)ws, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_lsd(const float* e, const float* x, const int* lens, int B, long long ld, const double* gain, const double* delta, double* out, int* flags, void* ws,
+              long long ws_bytes, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_lsd: ") + why); return BUDDY_ERR_ARG; };
+  if (!e || !x || !lens || !gain || !delta || !out || !flags || !ws) return bad("null pointer");
+  int longest;
+  if (int rc = check_rows(lens, B, ld, 1, stream, "buddy_lsd", &longest)) return rc;
+  if (ws_bytes < buddy_lsd_workspace(B, longest)) return bad("the workspace is smaller than buddy_lsd_workspace(B, longest row)");
+  launch_lsd(e, x, lens, B, ld, longest, gain, delta, out, flags, (double*)ws, (hipStream_t)stream);
+  return finish();
+}
+
 // ---- WPE warm start ----
 int buddy_wpe(const double* Y, double* X, double* scratch, int rows, int T, int taps, int delay, int iterations, void* stream) {
   if (!Y || !X || !scratch || rows < 1 || T < 1 || taps < 1 || taps > 56 || delay < 0 || iterations < 0) { set_error("bad wpe arguments (taps <= 56)"); return BUDDY_ERR_ARG; }

@@ -184,6 +184,20 @@ void launch_fir_bank(const float* h, const int* lens, int B, long long ldh, int 
                      hipStream_t st);
 void launch_decay_metrics(const float* g, const int* lens_g, const int* n0, int B, int nb, long long ldg, int fs, double* out, int* flags, float* edc_db,
                           hipStream_t st);
+// objective evaluation of (estimate, clean) pairs (metrics.hip): ragged rows, device length arrays; arguments, lengths, strides and workspaces are
+// checked by the C entries, which pass the longest row (max_len, max_m) for the grids
+int metrics_tile();                          // samples per step of the row reductions
+long long metrics_frames(long long len);     // full frames of 256 at hop 128
+void launch_pair_moments(const float* e, const float* x, const int* lens, int B, long long ld, double* out, int* flags, hipStream_t st);
+void launch_stoi_select(const float* x, const float* e, const int* lens, int B, long long ld, int max_len, float* xo, float* eo, long long ldo, int* lens_out,
+                        int* K, int* F, int* src, long long ldf, double* ws, hipStream_t st);
+void launch_band_spectra(const float* x, const int* lens, int B, long long ld, int max_len, const int* lo, const int* hi, int J, float* out, long long ldm,
+                         hipStream_t st);
+void launch_stoi_scores(const float* X, const float* Y, const int* lens_m, int B, int J, long long ldm, int max_m, double* out, int* flags, double* ws,
+                        hipStream_t st);
+void launch_frame_power(const float* x, const int* lens, int B, long long ld, int max_len, double* mean_p, double* ws, hipStream_t st);
+void launch_lsd(const float* e, const float* x, const int* lens, int B, long long ld, int max_len, const double* gain, const double* delta, double* out, int* flags,
+                double* ws, hipStream_t st);
 void launch_axpy(float* dst, const float* src, float alpha, long long n, int accumulate, hipStream_t st);
 // fir=True resampling with the (1,3,3,1) kernel: (H,W)->(2H,2W) / (H,W)->(H/2,W/2); adjoints: up^T = 4 down, down^T = up / 4
 void launch_fir_up2(const float* x, float* y, int B, int H, int W, int C, float scale, int accumulate, hipStream_t st);

@@ -25,10 +25,10 @@ class VCTKTestPaired:
         if normalize:
             raise NotImplementedError("normalization not implemented yet")
         self.test_samples, self.rir_samples = [], []
-        for s in os.listdir(os.path.join(path, "clean")):
+        for s in sorted(os.listdir(os.path.join(path, "clean"))):      # sorted: the utterance order must not depend on the file system's listing order
             if s in speakers_discard or (len(speakers_test) and s not in speakers_test):
                 continue
-            new = glob.glob(os.path.join(path, "clean", s, "*.wav"))
+            new = sorted(glob.glob(os.path.join(path, "clean", s, "*.wav")))
             self.test_samples.extend(new)
             for f in new:
                 self.rir_samples.append(os.path.join(path, "rir", s, os.path.splitext(os.path.basename(f))[0] + ".wav"))

@@ -43,6 +43,16 @@ def rir_report_options(tester_cfg):
     return bool(rp.get("use", False)), OCTAVES if c is None else tuple(float(v) for v in c)
 
 
+def metrics_options(tester_cfg):
+    """(use, values) of the ``metrics`` block of a tester config; a config written before the block existed means (False, all four values)"""
+    from ..utils.metrics import VALUES
+    mt = tester_cfg.get("metrics", None)
+    if mt is None:
+        return False, VALUES
+    v = mt.get("values", None)
+    return bool(mt.get("use", False)), VALUES if v is None else tuple(str(s) for s in v)
+
+
 class Tester:
     def __init__(self, args, network, diff_params, test_set=None, device=None, in_training=False, batch_size=1, rank=0, world_size=1):
         self.args = args
@@ -160,6 +170,8 @@ class Tester:
         local = {}
         report = blind and rir_report_options(self.args.tester)[0] and not self.in_training and bool(self.paths)
         rep = []         # room-acoustics report: (name, estimated RIR, true RIR, the operator's parameters of that row) per written RIR wav
+        scoring = metrics_options(self.args.tester)[0] and not self.in_training and bool(self.paths)
+        scored = []      # evaluation report: (name, clean, degraded, reconstructed) per written utterance, as written to the wavs
         for s in range(0, len(mine), self.batch_size):
             idx = mine[s:s + self.batch_size]
             items = [self.test_set[i] + (i,) for i in idx]
@@ -194,9 +206,13 @@ class Tester:
                         write_audio_file(est[b] if est.dim() == 2 else est, sr, name, path=self.paths[mode + "estimated_rir"])
                     if report:
                         rep.append((name, est[b] if est.dim() == 2 else est, rirs[b], {k: v if k == "freqs" else v[b] for k, v in par.items()}))
+                    if scoring:
+                        scored.append((name, seg[b].detach(), y[b].detach(), pred[b].detach()))
                     print(p)
         if report:
             self._write_rir_report(mode, rep, sr)
+        if scoring:
+            self._write_metrics_report(mode, scored, sr)
         # utterance-batch data parallelism: ONE gather at the end of the run (RCCL over xGMI on the GPU box) -- afterwards every rank, in
         # particular rank 0, holds all predictions in utterance order, independent of the world size
         from .. import dist as bdist
@@ -234,6 +250,32 @@ class Tester:
         acoustics.write_report(os.path.join(base, f"acoustics{tag}.csv"), acoustics.report_rows(names, est, true))
         acoustics.write_parameters(os.path.join(base, f"parameters{tag}.csv"), acoustics.parameter_rows(names, params))
         self.rir_report = dict(names=names, estimated=est, true=true, parameters=params)
+
+    def _write_metrics_report(self, mode, scored, sr):
+        """Evaluation report of a paired mode (``tester.metrics.use``; utils/metrics.py), once per mode after sampling: ``metrics.csv`` (per written
+        utterance SI-SDR, STOI, ESTOI and LSD of the degraded and of the reconstructed signal against the clean one, and the difference) and
+        ``metrics_summary.csv`` (n, mean, median, std per column) in the mode's directory.  ``scored``: (wav name, clean, degraded, reconstructed),
+        the float32 rows the wavs hold; equal lengths are scored as one batch.  Every rank writes its own rows (``metrics.rank<r>.csv`` when there are
+        several); nothing is gathered -- ``tools/evaluate.py`` scores the directory of a multi-rank run as a whole."""
+        from ..utils import metrics
+        self.metrics_report = None
+        if not scored:
+            return
+        values = metrics_options(self.args.tester)[1]
+        groups = {}
+        for i, r in enumerate(scored):
+            groups.setdefault(int(r[1].numel()), []).append(i)
+        rows = [None] * len(scored)
+        for idx in groups.values():
+            clean, deg, rec = (torch.stack([scored[i][k].flatten().float() for i in idx]).to(self.device) for k in (1, 2, 3))
+            inp = metrics.evaluate(deg, clean, int(sr), values=values)
+            out = metrics.evaluate(rec, clean, int(sr), values=values)
+            for i, row in zip(idx, metrics.report_rows([scored[i][0] for i in idx], inp, out)):
+                rows[i] = row
+        tag = f".rank{self.rank}" if self.world_size > 1 else ""
+        metrics.write_report(os.path.join(self.paths[mode], f"metrics{tag}.csv"), rows)
+        metrics.write_report(os.path.join(self.paths[mode], f"metrics_summary{tag}.csv"), metrics.summary_rows(rows))
+        self.metrics_report = rows
 
     def _sample_concurrent(self, grp, L, blind, S):
         """one equal-length group as ``S`` concurrent sub-batches (testing/concurrent.py)"""

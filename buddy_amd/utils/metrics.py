@@ -1,5 +1,17 @@
-"""SI-SDR (not in the reference): 10 log10(||a s||^2 / ||a s - s_hat||^2), a = <s_hat,s>/||s||^2, zero-mean."""
+"""SI-SDR (not in the reference): 10 log10(||a s||^2 / ||a s - s_hat||^2), a = <s_hat,s>/||s||^2, zero-mean.
+
+``evaluate`` scores (estimate, clean) pairs on the GPU -- SI-SDR, STOI, ESTOI and the log-spectral distance, definitions in DESIGN.md section 17 --
+through ``csrc/metrics.hip`` and, for the 10 kHz step of STOI, the project's own resampler.  It has no CPU form: a CPU tensor raises
+``BuddyHipError``.  ``report_rows`` / ``summary_rows`` / ``write_report`` turn two evaluations (input and output of a run against the clean
+signals) into the CSV report of the tester and of ``tools/evaluate.py``."""
+import functools
+
+import numpy as np
 import torch
+
+from .. import _lib
+from . import resample as _rs
+from .acoustics import write_report  # noqa: F401  -- the CSV conventions of the acoustics report: NaN as an empty field, repr(float)
 
 
 def si_sdr(est, ref):
@@ -8,3 +20,160 @@ def si_sdr(est, ref):
     a = (est * ref).sum(-1, keepdim=True) / (ref * ref).sum(-1, keepdim=True).clamp_min(1e-30)
     t = a * ref
     return 10 * torch.log10((t * t).sum(-1) / ((t - est) ** 2).sum(-1).clamp_min(1e-30))
+
+
+VALUES = ("si_sdr", "stoi", "estoi", "lsd")         # order of the last axis of ``Evaluation.values``; flag bit q = value q is defined
+STOI_FS = 10000                                      # the rate STOI and ESTOI are defined at
+FRAME, HOP, NFFT, SEGMENT = 256, 128, 512, 30
+
+
+@functools.lru_cache(maxsize=None)
+def third_octave_bands(fs=STOI_FS, nfft=NFFT, num_bands=15, first_centre=150.0):
+    """((lo, hi),) * num_bands: band j is the bins [lo, hi) of an ``nfft``-point transform at ``fs``, from the bin nearest the lower edge
+    cf_j 2^(-1/6) to the bin nearest the upper edge cf_j 2^(1/6), cf_j = first_centre 2^(j/3).  Designed in float64, cached."""
+    f = np.arange(nfft // 2 + 1, dtype=np.float64) * (float(fs) / nfft)
+    cf = float(first_centre) * 2.0 ** (np.arange(num_bands, dtype=np.float64) / 3.0)
+    lo = [int(np.argmin(np.abs(f - c * 2.0 ** (-1.0 / 6.0)))) for c in cf]
+    hi = [int(np.argmin(np.abs(f - c * 2.0 ** (1.0 / 6.0)))) for c in cf]
+    return tuple(zip(lo, hi))
+
+
+def frames_of(n):
+    """full frames of 256 samples at hop 128"""
+    return (int(n) - FRAME) // HOP + 1 if int(n) >= FRAME else 0
+
+
+class Evaluation:
+    """result of ``evaluate``: ``values`` (B, 4) float64 on the CPU in the order ``VALUES`` (dB, 0..1, 0..1, dB; NaN where undefined or not asked
+    for), ``flags`` (B,) int32 (bit q: value q is defined), ``kept_frames`` / ``frames`` (B,) int32: the 10 kHz frames STOI kept and had,
+    ``samples`` (B,) int32: the samples scored per row, ``names``: the values asked for"""
+
+    def __init__(self, values, flags, kept_frames, frames, samples, names):
+        self.values, self.flags, self.kept_frames, self.frames, self.samples, self.names = values, flags, kept_frames, frames, samples, names
+
+
+def evaluate(est, ref, fs, lens=None, values=VALUES):
+    """est, ref (B, L) float32 on the GPU at rate ``fs`` (an int >= 10 000): the estimates and the clean signals, row by row; ``lens`` (B ints,
+    default L): valid samples per row, the rest is ignored.  No time alignment: the pairs are scored as they are."""
+    if not isinstance(est, torch.Tensor) or not isinstance(ref, torch.Tensor) or not est.is_cuda or not ref.is_cuda:
+        raise _lib.BuddyHipError("evaluate: the metrics run on the MI355X only (got a CPU tensor)")
+    lib = _lib.require_gpu()
+    assert est.dim() == 2 and est.shape == ref.shape and est.dtype == ref.dtype == torch.float32, "evaluate takes two (B, L) float32 tensors"
+    if int(fs) != fs or int(fs) < STOI_FS:
+        raise ValueError(f"evaluate: the sample rate must be an integer >= {STOI_FS} Hz (STOI is defined at 10 kHz and nothing here upsamples to it), got {fs}")
+    names = tuple(v for v in VALUES if v in tuple(values))
+    unknown = sorted(set(values) - set(VALUES))
+    if unknown:
+        raise ValueError(f"evaluate: unknown values {unknown}; known: {list(VALUES)}")
+    fs = int(fs)
+    est, ref = est.contiguous(), ref.contiguous()
+    B, L = est.shape
+    dev = est.device
+    lens_t = torch.full((B,), L, dtype=torch.int32) if lens is None else torch.as_tensor(lens, dtype=torch.int32).reshape(B).cpu()
+    assert int(lens_t.min()) >= 1 and int(lens_t.max()) <= L, "every length must be in 1..L"
+    lens_d = lens_t.to(dev)
+    st = _lib.stream_ptr()
+    out = torch.full((B, 4), float("nan"), dtype=torch.float64)
+    flags = torch.zeros(B, dtype=torch.int32)
+    kept, frames = torch.zeros(B, dtype=torch.int32), torch.zeros(B, dtype=torch.int32)
+
+    mom = torch.empty(B, 4, dtype=torch.float64, device=dev)
+    mom_fl = torch.empty(B, dtype=torch.int32, device=dev)
+    _lib.check(lib.buddy_pair_moments(_lib.ptr(est), _lib.ptr(ref), lens_d.data_ptr(), B, L, mom.data_ptr(), mom_fl.data_ptr(), st))
+    if "si_sdr" in names:
+        out[:, 0] = mom[:, 3].cpu()
+        flags |= mom_fl.cpu()
+
+    if "stoi" in names or "estoi" in names:
+        e10, x10, lens10 = est, ref, lens_t
+        if fs != STOI_FS:
+            up, down = _rs.ratio(fs, STOI_FS)
+            if int(lens_t.min()) < L:            # the resampler takes whole rows: zero behind each row's end (zero extension is what it assumes there)
+                live = torch.arange(L, device=dev)[None, :] < lens_d[:, None]
+                zero = torch.zeros((), dtype=torch.float32, device=dev)
+                e10, x10 = torch.where(live, est, zero), torch.where(live, ref, zero)
+            e10, x10 = _rs.resample(e10, fs, STOI_FS), _rs.resample(x10, fs, STOI_FS)
+            lens10 = torch.tensor([_rs.out_length(int(n), up, down) for n in lens_t], dtype=torch.int32)
+        L10 = x10.shape[1]
+        lens10_d = lens10.to(dev)
+        maxF = frames_of(int(lens10.max()))
+        ldf, ldo = max(maxF, 1), max((maxF - 1) * HOP + FRAME, 1)
+        xo, eo = torch.empty(B, ldo, dtype=torch.float32, device=dev), torch.empty(B, ldo, dtype=torch.float32, device=dev)
+        lens_o, K, F = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
+        src = torch.empty(B, ldf, dtype=torch.int32, device=dev)
+        ws = torch.empty(B * ldf, dtype=torch.float64, device=dev)
+        _lib.check(lib.buddy_stoi_select(_lib.ptr(x10), _lib.ptr(e10), lens10_d.data_ptr(), B, L10, _lib.ptr(xo), _lib.ptr(eo), ldo, lens_o.data_ptr(),
+                                         K.data_ptr(), F.data_ptr(), src.data_ptr(), ldf, ws.data_ptr(), ws.numel() * 8, st))
+        kept, frames = K.cpu(), F.cpu()
+        ldm = max(int(kept.max()), 1)            # a signal rebuilt from K frames has K full frames
+        bands = third_octave_bands()
+        J = len(bands)
+        lo, hi = (_lib.C.c_int * J)(*[b[0] for b in bands]), (_lib.C.c_int * J)(*[b[1] for b in bands])
+        X, Y = torch.empty(B, J, ldm, dtype=torch.float32, device=dev), torch.empty(B, J, ldm, dtype=torch.float32, device=dev)
+        _lib.check(lib.buddy_band_spectra(_lib.ptr(xo), lens_o.data_ptr(), B, ldo, lo, hi, J, _lib.ptr(X), ldm, st))
+        _lib.check(lib.buddy_band_spectra(_lib.ptr(eo), lens_o.data_ptr(), B, ldo, lo, hi, J, _lib.ptr(Y), ldm, st))
+        sc = torch.empty(B, 2, dtype=torch.float64, device=dev)
+        sc_fl = torch.empty(B, dtype=torch.int32, device=dev)
+        ws2 = torch.empty(lib.buddy_stoi_scores_workspace(B, ldm) // 8, dtype=torch.float64, device=dev)
+        _lib.check(lib.buddy_stoi_scores(_lib.ptr(X), _lib.ptr(Y), K.data_ptr(), B, J, ldm, sc.data_ptr(), sc_fl.data_ptr(), ws2.data_ptr(), ws2.numel() * 8, st))
+        sc, sc_fl = sc.cpu(), sc_fl.cpu()
+        for q, name in ((1, "stoi"), (2, "estoi")):
+            if name in names:
+                out[:, q] = sc[:, q - 1]
+                flags |= sc_fl << q
+
+    if "lsd" in names:
+        ws = torch.empty(lib.buddy_lsd_workspace(B, int(lens_t.max())) // 8, dtype=torch.float64, device=dev)
+        mean_p = torch.empty(B, dtype=torch.float64, device=dev)
+        _lib.check(lib.buddy_frame_power(_lib.ptr(ref), lens_d.data_ptr(), B, L, mean_p.data_ptr(), ws.data_ptr(), ws.numel() * 8, st))
+        ee, xx = mom[:, 0], mom[:, 1]
+        gain = torch.where(ee > 0, torch.sqrt(xx / ee), torch.ones_like(ee)).contiguous()      # the estimate scaled to the clean signal's energy
+        delta = (1e-8 * mean_p).contiguous()
+        lsd = torch.empty(B, dtype=torch.float64, device=dev)
+        lsd_fl = torch.empty(B, dtype=torch.int32, device=dev)
+        _lib.check(lib.buddy_lsd(_lib.ptr(est), _lib.ptr(ref), lens_d.data_ptr(), B, L, gain.data_ptr(), delta.data_ptr(), lsd.data_ptr(), lsd_fl.data_ptr(),
+                                 ws.data_ptr(), ws.numel() * 8, st))
+        out[:, 3] = lsd.cpu()
+        flags |= lsd_fl.cpu() << 3
+    return Evaluation(out, flags, kept, frames, lens_t.clone(), names)
+
+
+# ---- the CSV report ------------------------------------------------------------------------------------------------------------------------
+def report_rows(names, inp, out):
+    """one dict per file from two ``Evaluation``s of the same rows against the clean signals -- ``inp``: the degraded input, ``out``: the
+    reconstruction: ``<m>_in``, ``<m>_out`` and ``<m>_delta`` = out - in per value asked for, both flag words, and the frame counts of the
+    clean signal (the same in both)"""
+    rows = []
+    for b, name in enumerate(names):
+        row = {"file": name, "samples": int(out.samples[b])}
+        for q, m in enumerate(VALUES):
+            if m in out.names:
+                vi, vo = float(inp.values[b, q]), float(out.values[b, q])
+                row[m + "_in"], row[m + "_out"], row[m + "_delta"] = vi, vo, vo - vi
+        row["flags_in"], row["flags_out"] = int(inp.flags[b]), int(out.flags[b])
+        row["kept_frames"], row["frames"] = int(out.kept_frames[b]), int(out.frames[b])
+        rows.append(row)
+    return rows
+
+
+def summary_rows(rows):
+    """one dict per value column of ``report_rows``: the number of files where it is defined, and their mean, median and standard deviation
+    (numpy's, population form); NaN where no file defines it"""
+    rows = list(rows)
+    out = []
+    if not rows:
+        return out
+    for col in rows[0]:
+        if not col.endswith(("_in", "_out", "_delta")) or col.startswith("flags"):
+            continue
+        v = np.array([r[col] for r in rows], dtype=np.float64)
+        v = v[~np.isnan(v)]
+        nan = float("nan")
+        out.append({"value": col, "n": int(v.size), "mean": float(np.mean(v)) if v.size else nan, "median": float(np.median(v)) if v.size else nan,
+                    "std": float(np.std(v)) if v.size else nan})
+    return out
+
+
+def format_summary(summary):
+    """the summary as lines of text (what the tool prints)"""
+    return "\n".join(f"{r['value']:>14}  n {r['n']:4d}  mean {r['mean']:10.4f}  median {r['median']:10.4f}  std {r['std']:9.4f}" for r in summary)

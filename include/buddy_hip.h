@@ -603,6 +603,53 @@ int buddy_decay_metrics(const float* g, const int* lens_g, const int* n0, int B,
                         void* stream);
 int buddy_decay_tile(void);
 
+/* ---- objective evaluation of a paired run (buddy_amd/utils/metrics.py; the reference writes its wavs and scores nothing):
+ * SI-SDR, STOI, ESTOI and the log-spectral distance of pairs (estimate e, clean reference x).  Rows are ragged inside a common stride: lens[b]
+ * samples of row b are valid, nothing behind them is read, nothing outside the declared extents is written.  Every lengths array is a DEVICE array
+ * of B ints; each entry copies it to the host once (after the work queued on `stream`) to check it.  Every reduction has a fixed order (no
+ * atomics), and a row's result does not depend on the other rows.  Frames are 256 samples at hop 128 under the window
+ * w[i] = 0.5 - 0.5 cos(2 pi (i + 1) / 257), all FULL frames: frames(len) = (len - 256) / 128 + 1 for len >= 256, else 0; the transform has 512 points.
+ * BUDDY_ERR_ARG, with nothing launched, for: a null pointer; B outside 1..65535; a length outside 1..2^30 (0..2^30 for the frame counts of buddy_stoi_scores and the rebuilt rows of buddy_band_spectra); a stride
+ * smaller than the longest row it holds; J outside 1..32 or a band outside the bins 0..257; a workspace below the size stated.
+ *
+ * buddy_pair_moments: out (B, 4) doubles = zero-mean ||e||^2, ||x||^2, <e,x>, and SI-SDR [dB] = 10 log10(||a x||^2 / max(||a x - e||^2, 1e-30)) with
+ *   a = <e,x> / max(||x||^2, 1e-30), both means removed; every sum in double, the two energies element by element.  flags[b] = 1 unless
+ *   ||x||^2 = 0 or lens[b] < 2 (the value is the clamped formula's either way).  buddy_metrics_tile: samples per step of its reductions (the
+ *   lengths around which the unit tests place their rows).
+ *
+ * buddy_stoi_select: silent-frame removal at 10 kHz, decided on the clean rows x alone.  E[f] = 20 log10(||w x_f||_2 + 2^-52) in double; frame f is
+ *   kept when E[f] > max_f E - 40; F[b] = frames(lens[b]), K[b] kept frames, src (B, ldf): src[b][j] = the frame that became kept frame j (j < K[b],
+ *   ascending; the rest of the row is untouched).  xo, eo (B, ldo): both signals rebuilt by overlap-adding their kept windowed frames at hop 128,
+ *   lens_out[b] = (K[b] - 1) 128 + 256 samples (0 for K[b] = 0); each sample is w x of the earlier covering frame plus w x of the later one, fp32.
+ *   ldf >= max(frames of the longest row, 1); ldo >= its full-frame extent; ws: 8 B ldf bytes (buddy_stoi_select_workspace(B, longest row) for
+ *   ldf = its frames).
+ *
+ * buddy_band_spectra: out (B, J, ldm) fp32, out[b][j][m] = sqrt(sum_{lo[j] <= k < hi[j]} |X[k, m]|^2) of frame m < frames(lens[b]), X the 512-point
+ *   transform (fp32, radix 2) of the windowed, zero-padded frame; the band sums in double.  lo, hi: HOST arrays of J ints.  ldm >= max(frames, 1).
+ *
+ * buddy_stoi_scores: X, Y (B, J, ldm) band spectra of the clean and the estimated rows with lens_m[b] frames.  One segment per run of 30
+ *   consecutive frames, S = lens_m[b] - 29.  out (B, 2) doubles = STOI (scale to the clean row's norm, clip at x (1 + 10^(15/20)), correlation of the
+ *   mean-removed rows, / (J S)) and ESTOI (rows, then columns, mean-removed and normalised; sum of products / (30 S)); every norm + 2^-52; all in
+ *   double.  S < 1: NaN and flags[b] = 0, else flags[b] = 1.  ws: buddy_stoi_scores_workspace(B, longest frame count) bytes.
+ *
+ * buddy_frame_power: mean_p[b] = mean over frames m and bins k = 0..256 of |X[k, m]|^2, by Parseval from the windowed frames in double (NaN without a
+ *   full frame).  buddy_lsd: out[b] = mean_m sqrt(mean_{k = 0..256} (10 log10((P + d) / (Q + d)))^2) with P = |X|^2, Q = gain[b]^2 |E|^2, d = delta[b]
+ *   (device doubles), means in double.  No full frame, or delta[b] not above zero: NaN and flags[b] = 0.  ws of both: buddy_lsd_workspace(B, longest row). */
+int buddy_metrics_tile(void);
+int buddy_pair_moments(const float* e, const float* x, const int* lens, int B, long long ld, double* out, int* flags, void* stream);
+long long buddy_stoi_select_workspace(int B, long long max_len);
+int buddy_stoi_select(const float* x, const float* e, const int* lens, int B, long long ld, float* xo, float* eo, long long ldo, int* lens_out, int* K, int* F,
+                      int* src, long long ldf, void* ws, long long ws_bytes, void* stream);
+int buddy_band_spectra(const float* x, const int* lens, int B, long long ld, const int* lo /*host*/, const int* hi /*host*/, int J, float* out, long long ldm,
+                       void* stream);
+long long buddy_stoi_scores_workspace(int B, int max_frames);
+int buddy_stoi_scores(const float* X, const float* Y, const int* lens_m, int B, int J, long long ldm, double* out, int* flags, void* ws, long long ws_bytes,
+                      void* stream);
+long long buddy_lsd_workspace(int B, long long max_len);
+int buddy_frame_power(const float* x, const int* lens, int B, long long ld, double* mean_p, void* ws, long long ws_bytes, void* stream);
+int buddy_lsd(const float* e, const float* x, const int* lens, int B, long long ld, const double* gain, const double* delta, double* out, int* flags, void* ws,
+              long long ws_bytes, void* stream);
+
 /* ---- the small fp32 kernels of the network, one entry per launcher (unit tests: tests/test_hip_small_ops.py).  All tensors NHWC with H = time, device
  * pointers, fp32.  Each entry returns BUDDY_ERR_ARG with a message, with nothing launched, for a null required pointer, an empty shape, or a shape its
  * kernels cannot compute (named per entry).
