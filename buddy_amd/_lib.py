@@ -83,6 +83,13 @@ _SIGS = {
     "buddy_frame_power": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "buddy_lsd": (C.c_int, [_f32p, _f32p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
                             C.c_void_p]),
+    "buddy_srmr_tile": (C.c_int, []),
+    "buddy_modulation_chunk": (C.c_int, []),
+    "buddy_gammatone_env": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_longlong, _f32p, _f32p, C.POINTER(C.c_int), C.c_int, _f32p, C.c_longlong, C.c_void_p]),
+    "buddy_modulation_energies": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                            C.c_longlong, C.c_void_p, C.c_void_p]),
+    "buddy_srmr_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "buddy_prof_collect_wino4": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                            C.POINTER(C.c_longlong)]),
     "buddy_prof_collect_hbm": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),

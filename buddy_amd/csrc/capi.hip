@@ -828,6 +828,53 @@ int buddy_lsd(const float* e, const float* x, const int* lens, int B, long long 
   return finish();
 }
 
+// ---- non-intrusive SRMR of single signals (srmr.hip) ----
+int buddy_srmr_tile(void) { return srmr_tile(); }
+int buddy_modulation_chunk(void) { return modulation_chunk(); }
+
+int buddy_gammatone_env(const float* x, const int* lens, int B, long long ld, const float* g_re, const float* g_im, const int* tap_off, int J, float* env,
+                        long long lde, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_gammatone_env: ") + why); return BUDDY_ERR_ARG; };
+  if (!x || !lens || !g_re || !g_im || !tap_off || !env) return bad("null pointer");
+  if (J < 1 || J > 32) return bad("J must be in 1..32");
+  if (tap_off[0] < 0) return bad("tap_off[0] must be >= 0");
+  for (int j = 0; j < J; ++j)
+    if (tap_off[j + 1] - tap_off[j] < 1 || tap_off[j + 1] - tap_off[j] > srmr_max_taps()) return bad("every channel must have 1..1536 taps");
+  int longest;
+  if (int rc = check_rows(lens, B, ld, 1, stream, "buddy_gammatone_env", &longest)) return rc;
+  if (lde < longest) return bad("lde is smaller than the longest row");
+  launch_gammatone_env(x, lens, B, ld, longest, g_re, g_im, tap_off, J, env, lde, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_modulation_energies(const float* env, const int* lens, int B, int J, long long lde, const double* coef, int K, int W, int H, double* E, long long ldm,
+                              int* frames, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_modulation_energies: ") + why); return BUDDY_ERR_ARG; };
+  if (!env || !lens || !coef || !E || !frames) return bad("null pointer");
+  if (J < 1 || J > 32) return bad("J must be in 1..32");
+  if (K < 1 || K > 8) return bad("K must be in 1..8");
+  if (H < 1 || H % modulation_chunk() != 0 || W != 4 * H || W > modulation_max_window()) return bad("the window must be four hops, the hop a multiple of 256, W <= 4096");
+  for (int k = 0; k < K; ++k)
+    if (coef[k * 6 + 3] != 1.0) return bad("every filter must be normalised to a0 = 1");
+  int longest;
+  if (int rc = check_rows(lens, B, lde, 1, stream, "buddy_modulation_energies", &longest)) return rc;
+  if (ldm < at_least_one(longest >= W ? (longest - W) / H + 1 : 0)) return bad("ldm is smaller than the frames of the longest row");
+  launch_modulation_energies(env, lens, B, J, lde, coef, K, W, H, E, ldm, frames, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_srmr_scores(const double* E, const int* frames, int B, int J, int K, long long ldm, const double* erb, const double* l, double* out, double* Ebar,
+                      int* flags, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_srmr_scores: ") + why); return BUDDY_ERR_ARG; };
+  if (!E || !frames || !erb || !l || !out || !Ebar || !flags) return bad("null pointer");
+  if (J < 1 || J > 32) return bad("J must be in 1..32");
+  if (K != 8) return bad("K must be 8 (the ratio is bands 0..3 over bands 4..K* - 1, K* in 5..8)");
+  int longest;
+  if (int rc = check_rows(frames, B, ldm, 0, stream, "buddy_srmr_scores", &longest)) return rc;
+  launch_srmr_scores(E, frames, B, J, ldm, erb, l, out, Ebar, flags, (hipStream_t)stream);
+  return finish();
+}
+
 // ---- WPE warm start ----
 int buddy_wpe(const double* Y, double* X, double* scratch, int rows, int T, int taps, int delay, int iterations, void* stream) {
   if (!Y || !X || !scratch || rows < 1 || T < 1 || taps < 1 || taps > 56 || delay < 0 || iterations < 0) { set_error("bad wpe arguments (taps <= 56)"); return BUDDY_ERR_ARG; }

@@ -198,6 +198,18 @@ void launch_stoi_scores(const float* X, const float* Y, const int* lens_m, int B
 void launch_frame_power(const float* x, const int* lens, int B, long long ld, int max_len, double* mean_p, double* ws, hipStream_t st);
 void launch_lsd(const float* e, const float* x, const int* lens, int B, long long ld, int max_len, const double* gain, const double* delta, double* out, int* flags,
                 double* ws, hipStream_t st);
+// non-intrusive SRMR of single signals (srmr.hip): ragged rows, device length arrays; arguments, lengths and strides are checked by the C entries, which
+// pass the longest row (max_len) for the grid.  tap_off, coef, erb and l are host arrays
+int srmr_tile();                             // outputs per workgroup of the envelope kernel
+int srmr_max_taps();                         // longest channel its LDS tile holds
+int modulation_chunk();                      // envelope samples per channel staged at a time; the hop is a multiple of it
+int modulation_max_window();
+void launch_gammatone_env(const float* x, const int* lens, int B, long long ld, int max_len, const float* gre, const float* gim, const int* tap_off, int J,
+                          float* env, long long lde, hipStream_t st);
+void launch_modulation_energies(const float* env, const int* lens, int B, int J, long long lde, const double* coef, int K, int W, int H, double* E, long long ldm,
+                                int* frames, hipStream_t st);
+void launch_srmr_scores(const double* E, const int* frames, int B, int J, long long ldm, const double* erb, const double* l, double* out, double* Ebar, int* flags,
+                        hipStream_t st);
 void launch_axpy(float* dst, const float* src, float alpha, long long n, int accumulate, hipStream_t st);
 // fir=True resampling with the (1,3,3,1) kernel: (H,W)->(2H,2W) / (H,W)->(H/2,W/2); adjoints: up^T = 4 down, down^T = up / 4
 void launch_fir_up2(const float* x, float* y, int B, int H, int W, int C, float scale, int accumulate, hipStream_t st);

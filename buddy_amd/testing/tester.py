@@ -53,6 +53,12 @@ def metrics_options(tester_cfg):
     return bool(mt.get("use", False)), VALUES if v is None else tuple(str(s) for s in v)
 
 
+def srmr_options(tester_cfg):
+    """use of the ``srmr`` block of a tester config; a config written before the block existed means False"""
+    sm = tester_cfg.get("srmr", None)
+    return False if sm is None else bool(sm.get("use", False))
+
+
 class Tester:
     def __init__(self, args, network, diff_params, test_set=None, device=None, in_training=False, batch_size=1, rank=0, world_size=1):
         self.args = args
@@ -172,6 +178,8 @@ class Tester:
         rep = []         # room-acoustics report: (name, estimated RIR, true RIR, the operator's parameters of that row) per written RIR wav
         scoring = metrics_options(self.args.tester)[0] and not self.in_training and bool(self.paths)
         scored = []      # evaluation report: (name, clean, degraded, reconstructed) per written utterance, as written to the wavs
+        srmr_on = srmr_options(self.args.tester) and not self.in_training and bool(self.paths)
+        heard = []     # SRMR report: (name, degraded, reconstructed, clean) per written utterance, each row with the rate of its wav
         for s in range(0, len(mine), self.batch_size):
             idx = mine[s:s + self.batch_size]
             items = [self.test_set[i] + (i,) for i in idx]
@@ -208,11 +216,15 @@ class Tester:
                         rep.append((name, est[b] if est.dim() == 2 else est, rirs[b], {k: v if k == "freqs" else v[b] for k, v in par.items()}))
                     if scoring:
                         scored.append((name, seg[b].detach(), y[b].detach(), pred[b].detach()))
+                    if srmr_on:
+                        heard.append((name, (y[b].detach(), sr), (pred[b].detach(), sr), (seg[b].detach(), sr)))
                     print(p)
         if report:
             self._write_rir_report(mode, rep, sr)
         if scoring:
             self._write_metrics_report(mode, scored, sr)
+        if srmr_on:
+            self._write_srmr_report(mode, heard)
         # utterance-batch data parallelism: ONE gather at the end of the run (RCCL over xGMI on the GPU box) -- afterwards every rank, in
         # particular rank 0, holds all predictions in utterance order, independent of the world size
         from .. import dist as bdist
@@ -276,6 +288,24 @@ class Tester:
         metrics.write_report(os.path.join(self.paths[mode], f"metrics{tag}.csv"), rows)
         metrics.write_report(os.path.join(self.paths[mode], f"metrics_summary{tag}.csv"), metrics.summary_rows(rows))
         self.metrics_report = rows
+
+    def _write_srmr_report(self, mode, items):
+        """SRMR report of a mode (``tester.srmr.use``; utils/srmr.py), once per mode after sampling: ``srmr.csv`` (per written
+        utterance the score of the degraded and of the reconstructed signal, their difference, and in a paired mode the clean signal's) and
+        ``srmr_summary.csv`` (n, mean, median, std per score column) in the mode's directory.  ``items``: (wav name, degraded, reconstructed, clean or
+        None), each a (row, rate) pair: the float32 samples its wav holds at the rate the wav is written at.  Every rank writes its own rows
+        (``srmr.rank<r>.csv`` when there are several); nothing is gathered -- ``tools/srmr.py`` scores the directory of a multi-rank run as a whole."""
+        from ..utils import srmr
+        self.srmr_report = None
+        if not items:
+            return
+        paired = items[0][3] is not None
+        cols = [srmr.score_signals([(it[k][0].flatten().float(), it[k][1]) for it in items], self.device) for k in ((1, 2, 3) if paired else (1, 2))]
+        rows = srmr.report_rows([it[0] for it in items], cols[0], cols[1], cols[2] if paired else None)
+        tag = f".rank{self.rank}" if self.world_size > 1 else ""
+        srmr.write_report(os.path.join(self.paths[mode], f"srmr{tag}.csv"), rows)
+        srmr.write_report(os.path.join(self.paths[mode], f"srmr_summary{tag}.csv"), srmr.summary_rows(rows))
+        self.srmr_report = rows
 
     def _sample_concurrent(self, grp, L, blind, S):
         """one equal-length group as ``S`` concurrent sub-batches (testing/concurrent.py)"""
@@ -381,6 +411,8 @@ class Tester:
             f["est"], f["rir"], f["par"] = [None] * len(starts), [None] * len(starts), [None] * len(starts)
         writing = not self.in_training and bool(self.paths)
         report = writing and rir_report_options(self.args.tester)[0]
+        srmr_on = writing and srmr_options(self.args.tester)
+        heard = []     # SRMR report: (name, degraded at the model's rate, reconstructed at its own rate, no clean signal) per written file
         for batch in batches:
             yb = torch.stack([files[f]["parts"][k] for f, k in batch])
             pred, est = self.sample_observed(yb, [f"{files[f]['name']}_c{k}.wav" for f, k in batch],
@@ -405,6 +437,8 @@ class Tester:
                 continue
             write_audio_file(f["y"], sr, f["name"], path=self.paths[mode + "degraded"])
             p = write_audio_file(pred, f["fs"] if to_input_rate else sr, f["name"], path=self.paths[mode + "reconstructed"])
+            if srmr_on:
+                heard.append((f["name"], (f["y"].detach(), sr), (pred.detach(), f["fs"] if to_input_rate else sr), None))
             if shared:       # one estimate per file (per run where shared_rir_max_chunks cut it): the chunks of a run hold the same RIR
                 for j, (lo, _) in enumerate(f["runs"]):
                     write_audio_file(f["rir"][lo], sr, f["name"] if len(f["runs"]) == 1 else f"{f['name']}_r{j}", path=self.paths[mode + "estimated_rir"])
@@ -416,6 +450,8 @@ class Tester:
             print(p)
         if report:
             self._write_rir_report(mode, rep, sr)
+        if srmr_on:
+            self._write_srmr_report(mode, heard)
 
     def dereverberate_long(self, original, rir, blind, chunk_seconds=8.0, overlap_seconds=1.0, noise=None, shared_rir=False):
         """Long-form policy (testing/longform.py): one long clean/RIR pair -> the reverberant signal cut into overlapping equal chunks,

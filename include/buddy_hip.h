@@ -650,6 +650,37 @@ int buddy_frame_power(const float* x, const int* lens, int B, long long ld, doub
 int buddy_lsd(const float* e, const float* x, const int* lens, int B, long long ld, const double* gain, const double* delta, double* out, int* flags, void* ws,
               long long ws_bytes, void* stream);
 
+/* ---- non-intrusive score of single signals (buddy_amd/utils/srmr.py): the speech-to-reverberation modulation energy ratio.
+ * The conventions of the evaluation entries above hold: ragged rows inside a common stride, DEVICE length arrays copied to the host once to be checked,
+ * nothing behind lens[b] read, nothing outside the declared extents written, fixed-order sums without atomics, a row's result independent of its batch.
+ * BUDDY_ERR_ARG, with nothing launched, for: a null pointer; B outside 1..65535; a length outside 1..2^30 (0..2^30 for the frame counts of
+ * buddy_srmr_scores); a stride smaller than the longest row it holds; J outside 1..32; the limits named per entry.
+ *
+ * buddy_gammatone_env: env (B, J, lde) fp32, env[b][j][n] = |sum_{t < N_j} g_j[t] x[b][n - t]| for n < lens[b], x zero before the row's start; nothing is
+ *   written at or behind lens[b].  g_re, g_im: the taps of all channels one behind the other (device, fp32); tap_off: HOST array of J + 1 ints, channel j
+ *   is the taps tap_off[j] .. tap_off[j + 1] - 1, 1..1536 of them.  Order of the fp32 arithmetic, the same for every output: real and imaginary sum start
+ *   at zero and take one fused multiply-add per tap, t ascending; the magnitude is sqrt(fma(re, re, im * im)).  The grid runs the channels by descending
+ *   tap count.  buddy_srmr_tile: outputs per workgroup (the lengths around which the unit tests place their rows).
+ *
+ * buddy_modulation_energies: K <= 8 second-order filters (coef: HOST array (K, 6) doubles b0 b1 b2 a0 a1 a2 with a0 = 1; direct form II transposed, zero
+ *   initial state, double) run along each envelope row env (B, J, lde) with lens[b] samples; E (B, J, K, ldm) doubles,
+ *   E[b][j][k][m] = sum_{i < W} (h[i] v_jk[m H + i])^2 for the full frames m < frames[b] = (lens[b] - W) / H + 1 (0 below W), h[i] = 0.54 - 0.46 cos(2 pi
+ *   (i + 1) / (W + 1)); the filtered signals v are not stored.  W = 4 H, H a multiple of buddy_modulation_chunk() = 256, W <= 4096.  ldm >= max(frames, 1).
+ *
+ * buddy_srmr_scores: Ebar (B, J, 8) doubles = mean over the frames of E (NaN without a frame); A[j] = sum_k Ebar[j][k]; the channels are visited in index
+ *   order, which the caller makes the order of ascending centre frequency: BW = erb[j] of the first j whose running sum of A is strictly above 0.9 sum_j A[j];
+ *   K* = 5 + #{k in 5..7: BW >= l[k]}; out (B, 3) doubles = (sum_j sum_{k < 4} Ebar / sum_j sum_{4 <= k < K*} Ebar, K*, BW).  erb (J), l (8): HOST doubles.
+ *   flags[b] = 1 where the ratio is defined.  No frame or no energy: three NaN and flag 0; a zero denominator: NaN, K*, BW and flag 0.  K must be 8.
+ *   One workgroup per row. */
+int buddy_srmr_tile(void);
+int buddy_modulation_chunk(void);
+int buddy_gammatone_env(const float* x, const int* lens, int B, long long ld, const float* g_re, const float* g_im, const int* tap_off /*host*/, int J, float* env,
+                        long long lde, void* stream);
+int buddy_modulation_energies(const float* env, const int* lens, int B, int J, long long lde, const double* coef /*host*/, int K, int W, int H, double* E,
+                              long long ldm, int* frames, void* stream);
+int buddy_srmr_scores(const double* E, const int* frames, int B, int J, int K, long long ldm, const double* erb /*host*/, const double* l /*host*/, double* out,
+                      double* Ebar, int* flags, void* stream);
+
 /* ---- the small fp32 kernels of the network, one entry per launcher (unit tests: tests/test_hip_small_ops.py).  All tensors NHWC with H = time, device
  * pointers, fp32.  Each entry returns BUDDY_ERR_ARG with a message, with nothing launched, for a null required pointer, an empty shape, or a shape its
  * kernels cannot compute (named per entry).
