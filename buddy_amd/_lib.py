@@ -83,6 +83,12 @@ _SIGS = {
     "buddy_frame_power": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "buddy_lsd": (C.c_int, [_f32p, _f32p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_longlong,
                             C.c_void_p]),
+    "buddy_align_tile": (C.c_int, []),
+    "buddy_align_lag_tile": (C.c_int, []),
+    "buddy_xcorr_lag_workspace": (C.c_longlong, [C.c_int, C.c_longlong, C.c_int]),
+    "buddy_xcorr_lag": (C.c_int, [_f32p, _f32p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_longlong, C.c_void_p]),
+    "buddy_align_pair": (C.c_int, [_f32p, _f32p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, _f32p, _f32p, C.c_longlong, C.c_void_p, C.c_void_p]),
     "buddy_srmr_tile": (C.c_int, []),
     "buddy_modulation_chunk": (C.c_int, []),
     "buddy_gammatone_env": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_longlong, _f32p, _f32p, C.POINTER(C.c_int), C.c_int, _f32p, C.c_longlong, C.c_void_p]),

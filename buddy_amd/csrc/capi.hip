@@ -828,6 +828,46 @@ int buddy_lsd(const float* e, const float* x, const int* lens, int B, long long 
   return finish();
 }
 
+// ---- time alignment of a pair before it is scored (align.hip) ----
+int buddy_align_tile(void) { return align_tile(); }
+int buddy_align_lag_tile(void) { return align_lag_tile(); }
+
+long long buddy_xcorr_lag_workspace(int B, long long max_len, int K) {
+  if (B < 1 || B > 65535 || max_len < 1 || max_len > (1LL << 30) || K < 0 || K > 65535) return -1;
+  return 8LL * xcorr_workspace_doubles(B, max_len, K);
+}
+
+int buddy_xcorr_lag(const float* e, const float* x, const int* lens, int B, long long ld, int K, int* lag, double* out, int* flags, double* r_out, void* ws,
+                    long long ws_bytes, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_xcorr_lag: ") + why); return BUDDY_ERR_ARG; };
+  if (!e || !x || !lens || !lag || !out || !flags || !ws) return bad("null pointer");
+  if (K < 0 || K > 65535) return bad("K must be in 0..65535");
+  int longest;
+  if (int rc = check_rows(lens, B, ld, 1, stream, "buddy_xcorr_lag", &longest)) return rc;
+  if (ws_bytes < buddy_xcorr_lag_workspace(B, longest, K)) return bad("the workspace is smaller than buddy_xcorr_lag_workspace(B, longest row, K)");
+  launch_xcorr_lag(e, x, lens, B, ld, longest, K, lag, out, flags, r_out, (double*)ws, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_align_pair(const float* e, const float* x, const int* lens, const int* lag, int B, long long ld, float* eo, float* xo, long long ldo, int* lens_out,
+                     void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_align_pair: ") + why); return BUDDY_ERR_ARG; };
+  if (!e || !x || !lens || !lag || !eo || !xo || !lens_out) return bad("null pointer");
+  if (B < 1 || B > 65535) return bad("B must be in 1..65535");
+  if (ld < 1 || ldo < 1 || ldo > 0x7fffffffLL) return bad("the row strides must be >= 1, ldo below 2^31");
+  std::vector<int> len, d;
+  if (int rc = fetch_lengths(lens, B, len, stream, "buddy_align_pair")) return rc;
+  if (int rc = fetch_lengths(lag, B, d, stream, "buddy_align_pair")) return rc;
+  for (int b = 0; b < B; ++b) {
+    if (len[b] < 1 || len[b] > (1 << 30)) return bad("every length must be in 1..2^30");
+    if (len[b] > ld) return bad("the row stride is smaller than the longest row");
+    if (d[b] <= -len[b] || d[b] >= len[b]) return bad("every |lag[b]| must be below lens[b]");
+    if (len[b] - (d[b] < 0 ? -d[b] : d[b]) > ldo) return bad("ldo is smaller than the longest overlap");
+  }
+  launch_align_pair(e, x, lens, lag, B, ld, eo, xo, ldo, lens_out, (hipStream_t)stream);
+  return finish();
+}
+
 // ---- non-intrusive SRMR of single signals (srmr.hip) ----
 int buddy_srmr_tile(void) { return srmr_tile(); }
 int buddy_modulation_chunk(void) { return modulation_chunk(); }

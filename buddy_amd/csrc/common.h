@@ -198,6 +198,15 @@ void launch_stoi_scores(const float* X, const float* Y, const int* lens_m, int B
 void launch_frame_power(const float* x, const int* lens, int B, long long ld, int max_len, double* mean_p, double* ws, hipStream_t st);
 void launch_lsd(const float* e, const float* x, const int* lens, int B, long long ld, int max_len, const double* gain, const double* delta, double* out, int* flags,
                 double* ws, hipStream_t st);
+// time alignment of a pair before it is scored (align.hip): ragged rows, device length and lag arrays; arguments, lengths, lags, strides and the
+// workspace are checked by the C entries, which pass the longest row (max_len) for the grids
+int align_tile();                            // samples per chunk of the correlation kernel
+int align_lag_tile();                        // lags per tile of the correlation kernel
+long long xcorr_workspace_doubles(int B, long long max_len, int K);
+void launch_xcorr_lag(const float* e, const float* x, const int* lens, int B, long long ld, int max_len, int K, int* lag, double* out, int* flags, double* r_out,
+                      double* ws, hipStream_t st);
+void launch_align_pair(const float* e, const float* x, const int* lens, const int* lag, int B, long long ld, float* eo, float* xo, long long ldo, int* lens_out,
+                       hipStream_t st);
 // non-intrusive SRMR of single signals (srmr.hip): ragged rows, device length arrays; arguments, lengths and strides are checked by the C entries, which
 // pass the longest row (max_len) for the grid.  tap_off, coef, erb and l are host arrays
 int srmr_tile();                             // outputs per workgroup of the envelope kernel

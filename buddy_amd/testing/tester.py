@@ -53,6 +53,18 @@ def metrics_options(tester_cfg):
     return bool(mt.get("use", False)), VALUES if v is None else tuple(str(s) for s in v)
 
 
+def align_options(tester_cfg):
+    """(use, max_lag_ms) of the ``metrics.align`` block of a tester config: whether every pair is time-aligned before it is scored, and the search
+    window in ms; a config written before the block existed means (False, 50.0)"""
+    from ..utils.metrics import MAX_LAG_MS
+    mt = tester_cfg.get("metrics", None)
+    al = None if mt is None else mt.get("align", None)
+    if al is None:
+        return False, MAX_LAG_MS
+    ms = al.get("max_lag_ms", None)
+    return bool(al.get("use", False)), MAX_LAG_MS if ms is None else float(ms)
+
+
 def srmr_options(tester_cfg):
     """use of the ``srmr`` block of a tester config; a config written before the block existed means False"""
     sm = tester_cfg.get("srmr", None)
@@ -267,21 +279,25 @@ class Tester:
         """Evaluation report of a paired mode (``tester.metrics.use``; utils/metrics.py), once per mode after sampling: ``metrics.csv`` (per written
         utterance SI-SDR, STOI, ESTOI and LSD of the degraded and of the reconstructed signal against the clean one, and the difference) and
         ``metrics_summary.csv`` (n, mean, median, std per column) in the mode's directory.  ``scored``: (wav name, clean, degraded, reconstructed),
-        the float32 rows the wavs hold; equal lengths are scored as one batch.  Every rank writes its own rows (``metrics.rank<r>.csv`` when there are
+        the float32 rows the wavs hold; equal lengths are scored as one batch.  ``tester.metrics.align.use``: the degraded and the reconstructed signal
+        are each shifted by their own integer lag against the clean one and trimmed to the overlap first (``metrics.align``), and the lags, their
+        correlations and flags are further columns.  Every rank writes its own rows (``metrics.rank<r>.csv`` when there are
         several); nothing is gathered -- ``tools/evaluate.py`` scores the directory of a multi-rank run as a whole."""
         from ..utils import metrics
         self.metrics_report = None
         if not scored:
             return
         values = metrics_options(self.args.tester)[1]
+        use_align, max_lag_ms = align_options(self.args.tester)
+        window = max_lag_ms if use_align else None
         groups = {}
         for i, r in enumerate(scored):
             groups.setdefault(int(r[1].numel()), []).append(i)
         rows = [None] * len(scored)
         for idx in groups.values():
             clean, deg, rec = (torch.stack([scored[i][k].flatten().float() for i in idx]).to(self.device) for k in (1, 2, 3))
-            inp = metrics.evaluate(deg, clean, int(sr), values=values)
-            out = metrics.evaluate(rec, clean, int(sr), values=values)
+            inp = metrics.evaluate(deg, clean, int(sr), values=values, align=window)
+            out = metrics.evaluate(rec, clean, int(sr), values=values, align=window)
             for i, row in zip(idx, metrics.report_rows([scored[i][0] for i in idx], inp, out)):
                 rows[i] = row
         tag = f".rank{self.rank}" if self.world_size > 1 else ""

@@ -3,7 +3,8 @@
 ``evaluate`` scores (estimate, clean) pairs on the GPU -- SI-SDR, STOI, ESTOI and the log-spectral distance, definitions in DESIGN.md section 17 --
 through ``csrc/metrics.hip`` and, for the 10 kHz step of STOI, the project's own resampler.  It has no CPU form: a CPU tensor raises
 ``BuddyHipError``.  ``report_rows`` / ``summary_rows`` / ``write_report`` turn two evaluations (input and output of a run against the clean
-signals) into the CSV report of the tester and of ``tools/evaluate.py``."""
+signals) into the CSV report of the tester and of ``tools/evaluate.py``.  ``align`` (``csrc/align.hip``) estimates one integer
+lag per pair and trims the pair to its overlap; ``evaluate(..., align=ms)`` scores after it.  It is off unless asked for."""
 import functools
 
 import numpy as np
@@ -48,13 +49,63 @@ class Evaluation:
     for), ``flags`` (B,) int32 (bit q: value q is defined), ``kept_frames`` / ``frames`` (B,) int32: the 10 kHz frames STOI kept and had,
     ``samples`` (B,) int32: the samples scored per row, ``names``: the values asked for"""
 
-    def __init__(self, values, flags, kept_frames, frames, samples, names):
+    def __init__(self, values, flags, kept_frames, frames, samples, names, alignment=None):
         self.values, self.flags, self.kept_frames, self.frames, self.samples, self.names = values, flags, kept_frames, frames, samples, names
+        self.alignment = alignment                   # the ``Alignment`` the rows were scored after (``evaluate(..., align=ms)``), or None
 
 
-def evaluate(est, ref, fs, lens=None, values=VALUES):
+ALIGN_FLAGS = ("defined", "edge", "inverted")        # bits 0..2 of ``Alignment.flags``
+MAX_LAG_MS = 50.0                                    # default search window: +-50 ms, about 17 m of path difference.  A choice, not a measurement
+
+
+class Alignment:
+    """result of ``align``: per row ``lag`` (B,) int32 -- positive: the estimate is late --, ``rho`` (B,) float64: the normalised cross-correlation at
+    that lag, signed, ``frac`` (B,) float64: the sub-sample offset of the peak by a parabola through its neighbours (reported, never applied),
+    ``flags`` (B,) int32 (bit 0: defined, bit 1: the peak lies on the edge of the window, bit 2: rho < 0), all on the CPU; ``est``, ``ref`` (B, L) on the
+    GPU: the pair shifted to its overlap, zeros behind it, and ``lens`` (B,) int32 on the CPU: the overlap, input length - |lag|; ``max_lag``: the
+    window K in samples, ``fs``: the rate.  A row that is not defined (fewer than two samples, a constant or non-finite signal) has lag 0 and rho NaN."""
+
+    def __init__(self, lag, rho, frac, flags, est, ref, lens, max_lag, fs):
+        self.lag, self.rho, self.frac, self.flags, self.est, self.ref, self.lens, self.max_lag, self.fs = lag, rho, frac, flags, est, ref, lens, max_lag, fs
+
+
+def align(est, ref, fs, lens=None, max_lag_ms=MAX_LAG_MS):
+    """Time-align (B, L) float32 estimates to their clean signals on the GPU (``csrc/align.hip``): one integer lag per row, the
+    largest |cross-correlation| of the zero-mean signals within +-K = round(max_lag_ms fs / 1000) samples, and both signals trimmed to the
+    overlap.  ``lens`` as in ``evaluate``.  Returns an ``Alignment``."""
+    if not isinstance(est, torch.Tensor) or not isinstance(ref, torch.Tensor) or not est.is_cuda or not ref.is_cuda:
+        raise _lib.BuddyHipError("align: the alignment runs on the MI355X only (got a CPU tensor)")
+    lib = _lib.require_gpu()
+    assert est.dim() == 2 and est.shape == ref.shape and est.dtype == ref.dtype == torch.float32, "align takes two (B, L) float32 tensors"
+    K = int(round(float(max_lag_ms) * float(fs) / 1000.0))
+    if not 0 <= K <= 65535:
+        raise ValueError(f"align: max_lag_ms = {max_lag_ms} at {fs} Hz is a window of {K} samples; it must be in 0..65535")
+    est, ref = est.contiguous(), ref.contiguous()
+    B, L = est.shape
+    dev = est.device
+    lens_t = torch.full((B,), L, dtype=torch.int32) if lens is None else torch.as_tensor(lens, dtype=torch.int32).reshape(B).cpu()
+    assert int(lens_t.min()) >= 1 and int(lens_t.max()) <= L, "every length must be in 1..L"
+    lens_d = lens_t.to(dev)
+    st = _lib.stream_ptr()
+    lag, flags, lens_o = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
+    out = torch.empty(B, 2, dtype=torch.float64, device=dev)
+    ws = torch.empty(lib.buddy_xcorr_lag_workspace(B, int(lens_t.max()), K) // 8, dtype=torch.float64, device=dev)
+    _lib.check(lib.buddy_xcorr_lag(_lib.ptr(est), _lib.ptr(ref), lens_d.data_ptr(), B, L, K, lag.data_ptr(), out.data_ptr(), flags.data_ptr(), None,
+                                   ws.data_ptr(), ws.numel() * 8, st))
+    eo, xo = torch.empty_like(est), torch.empty_like(ref)
+    _lib.check(lib.buddy_align_pair(_lib.ptr(est), _lib.ptr(ref), lens_d.data_ptr(), lag.data_ptr(), B, L, _lib.ptr(eo), _lib.ptr(xo), L, lens_o.data_ptr(), st))
+    out = out.cpu()
+    return Alignment(lag.cpu(), out[:, 0].clone(), out[:, 1].clone(), flags.cpu(), eo, xo, lens_o.cpu(), K, fs)
+
+
+_align = align                                       # ``evaluate`` has a keyword of the same name
+
+
+def evaluate(est, ref, fs, lens=None, values=VALUES, align=None):
     """est, ref (B, L) float32 on the GPU at rate ``fs`` (an int >= 10 000): the estimates and the clean signals, row by row; ``lens`` (B ints,
-    default L): valid samples per row, the rest is ignored.  No time alignment: the pairs are scored as they are."""
+    default L): valid samples per row, the rest is ignored.  ``align`` = None: no time alignment, the pairs are scored as they are.  ``align`` = a
+    search window in ms: every pair is first shifted by its own integer lag and trimmed to the overlap (``align`` above); the result carries the
+    ``Alignment`` and ``samples`` is the overlap."""
     if not isinstance(est, torch.Tensor) or not isinstance(ref, torch.Tensor) or not est.is_cuda or not ref.is_cuda:
         raise _lib.BuddyHipError("evaluate: the metrics run on the MI355X only (got a CPU tensor)")
     lib = _lib.require_gpu()
@@ -66,6 +117,10 @@ def evaluate(est, ref, fs, lens=None, values=VALUES):
     if unknown:
         raise ValueError(f"evaluate: unknown values {unknown}; known: {list(VALUES)}")
     fs = int(fs)
+    alignment = None
+    if align is not None:
+        alignment = _align(est, ref, fs, lens=lens, max_lag_ms=float(align))
+        est, ref, lens = alignment.est, alignment.ref, alignment.lens
     est, ref = est.contiguous(), ref.contiguous()
     B, L = est.shape
     dev = est.device
@@ -135,14 +190,17 @@ def evaluate(est, ref, fs, lens=None, values=VALUES):
                                  ws.data_ptr(), ws.numel() * 8, st))
         out[:, 3] = lsd.cpu()
         flags |= lsd_fl.cpu() << 3
-    return Evaluation(out, flags, kept, frames, lens_t.clone(), names)
+    return Evaluation(out, flags, kept, frames, lens_t.clone(), names, alignment)
 
 
 # ---- the CSV report ------------------------------------------------------------------------------------------------------------------------
 def report_rows(names, inp, out):
     """one dict per file from two ``Evaluation``s of the same rows against the clean signals -- ``inp``: the degraded input, ``out``: the
     reconstruction: ``<m>_in``, ``<m>_out`` and ``<m>_delta`` = out - in per value asked for, both flag words, and the frame counts of the
-    clean signal (the same in both)"""
+    clean signal (the same in both).  Where an evaluation carries an ``Alignment`` the row ends with ``lag_in`` / ``lag_out`` (samples, positive: late),
+    ``lag_ms_*``, ``xcorr_*`` (rho) and ``align_flags_*``; the side without one has empty fields and flag word 0.  Without any, the columns are those
+    above and nothing else."""
+    al = [getattr(ev, "alignment", None) for ev in (inp, out)]
     rows = []
     for b, name in enumerate(names):
         row = {"file": name, "samples": int(out.samples[b])}
@@ -152,19 +210,26 @@ def report_rows(names, inp, out):
                 row[m + "_in"], row[m + "_out"], row[m + "_delta"] = vi, vo, vo - vi
         row["flags_in"], row["flags_out"] = int(inp.flags[b]), int(out.flags[b])
         row["kept_frames"], row["frames"] = int(out.kept_frames[b]), int(out.frames[b])
+        if al[0] is not None or al[1] is not None:
+            nan = float("nan")
+            for col, get in (("lag", lambda a: int(a.lag[b])), ("lag_ms", lambda a: 1000.0 * int(a.lag[b]) / float(a.fs)), ("xcorr", lambda a: float(a.rho[b])),
+                             ("align_flags", lambda a: int(a.flags[b]))):
+                for side, a in zip(("_in", "_out"), al):
+                    row[col + side] = get(a) if a is not None else (0 if col == "align_flags" else nan)
         rows.append(row)
     return rows
 
 
 def summary_rows(rows):
     """one dict per value column of ``report_rows``: the number of files where it is defined, and their mean, median and standard deviation
-    (numpy's, population form); NaN where no file defines it"""
+    (numpy's, population form); NaN where no file defines it.  Of an aligned report the ``lag_ms_*`` and ``xcorr_*`` columns are summarised too, the
+    integer lags and the flag words are not"""
     rows = list(rows)
     out = []
     if not rows:
         return out
     for col in rows[0]:
-        if not col.endswith(("_in", "_out", "_delta")) or col.startswith("flags"):
+        if not col.endswith(("_in", "_out", "_delta")) or col.startswith(("flags", "align_flags")) or col in ("lag_in", "lag_out"):
             continue
         v = np.array([r[col] for r in rows], dtype=np.float64)
         v = v[~np.isnan(v)]

@@ -650,6 +650,35 @@ int buddy_frame_power(const float* x, const int* lens, int B, long long ld, doub
 int buddy_lsd(const float* e, const float* x, const int* lens, int B, long long ld, const double* gain, const double* delta, double* out, int* flags, void* ws,
               long long ws_bytes, void* stream);
 
+/* ---- time alignment of a pair before it is scored (buddy_amd/utils/metrics.py align; no reference counterpart): one integer lag
+ * per pair (estimate e, clean reference x) from a windowed cross-correlation, and the pair trimmed to its overlap.  The conventions of the evaluation
+ * entries above hold: ragged rows inside a common stride, DEVICE length (and lag) arrays copied to the host once to be checked, nothing behind
+ * lens[b] - 1 read, nothing outside the declared extents written, fixed-order sums without atomics, a row's result independent of its batch.
+ * BUDDY_ERR_ARG, with nothing launched, for: a null pointer (r_out may be NULL); B outside 1..65535; a length outside 1..2^30; a stride smaller than the
+ * longest row it holds; K outside 0..65535; a workspace below the size stated; a lag with |lag[b]| >= lens[b].
+ *
+ * buddy_xcorr_lag: for row b with n = lens[b]: e~ = e - mean(e), x~ = x - mean(x) in double; r[k] = sum_m e~[m + k] x~[m] over the m with 0 <= m < n and
+ *   0 <= m + k < n (zero where there is none), k = -K..K, every product and sum in double: a direct correlation, no FFT, so
+ *   |r[k] - exact| <= about (n + 4) 2^-53 sum_m |e~[m + k]| |x~[m]|.  A positive k means the estimate is late.  d = the k of the largest |r[k]|; ties go to the
+ *   smallest |k|, then to k >= 0.  lag[b] = d; out (B, 2) doubles = (rho, frac): rho = r[d] / sqrt(||e~||^2 ||x~||^2), signed; frac = 0.5 (a - c) / (a - 2 b + c)
+ *   with a, b, c = |r[d - 1]|, |r[d]|, |r[d + 1]| where |d| < K and the denominator is negative, else 0 (the vertex of the parabola through the three
+ *   points: reported, never applied).  flags[b]: bit 0 = defined (n >= 2, both energies > 0, every input finite; else d = 0, rho = NaN, frac = 0); bit 1 = the
+ *   peak lies on the edge of the window (|d| = K, K > 0); bit 2 = rho < 0 (inverted polarity).  r_out: (B, 2K + 1) doubles, r_out[b][k + K] = r[k], or NULL
+ *   (there for the unit tests; for a row that is not defined it holds whatever the sums gave).  K >= n is allowed (those lags have r = 0).
+ *   ws: buddy_xcorr_lag_workspace(B, longest row, K) bytes (-1 for arguments out of range).  Work: n (2K + 1) multiply-adds per row.
+ *   buddy_align_tile: samples per chunk, buddy_align_lag_tile: lags per tile of the correlation kernel (the sizes around which the unit tests place
+ *   their rows and windows).
+ *
+ * buddy_align_pair: lens_out[b] = lens[b] - |d|, d = lag[b] (DEVICE ints); eo[b][m] = e[b][m + max(d, 0)], xo[b][m] = x[b][m + max(-d, 0)] for m < lens_out[b],
+ *   zeros from there to ldo - 1.  eo, xo: (B, ldo), ldo >= the longest overlap. */
+int buddy_align_tile(void);
+int buddy_align_lag_tile(void);
+long long buddy_xcorr_lag_workspace(int B, long long max_len, int K);
+int buddy_xcorr_lag(const float* e, const float* x, const int* lens, int B, long long ld, int K, int* lag, double* out, int* flags, double* r_out, void* ws,
+                    long long ws_bytes, void* stream);
+int buddy_align_pair(const float* e, const float* x, const int* lens, const int* lag, int B, long long ld, float* eo, float* xo, long long ldo, int* lens_out,
+                     void* stream);
+
 /* ---- non-intrusive score of single signals (buddy_amd/utils/srmr.py): the speech-to-reverberation modulation energy ratio.
  * The conventions of the evaluation entries above hold: ragged rows inside a common stride, DEVICE length arrays copied to the host once to be checked,
  * nothing behind lens[b] read, nothing outside the declared extents written, fixed-order sums without atomics, a row's result independent of its batch.

@@ -4,9 +4,12 @@ every estimate against its clean signal, on the GPU.
 
     python tools/evaluate.py <mode dir>                                    # its original/, degraded/ and reconstructed/
     python tools/evaluate.py --reference DIR --estimate DIR [--input DIR] [--out DIR]
+    python tools/evaluate.py <mode dir> --align [MS]                       # time-align every pair first, within +-MS ms (default 50)
 
-Wavs are matched by file name; int or float wavs of any ONE rate >= 10 kHz per pair (a pair of two rates is refused, nothing is resampled to match and
-nothing is time-aligned).  A pair of different lengths is cut to the shorter, and ``samples`` says so.  Files of equal length and rate are scored as
+Wavs are matched by file name; int or float wavs of any ONE rate >= 10 kHz per pair (a pair of two rates is refused, nothing is resampled to match).  Nothing is time-aligned unless ``--align`` is given: then every estimate (and every input) is shifted by its own integer
+lag against its clean signal -- the largest |cross-correlation| within the window -- and the pair is trimmed to the overlap before it is scored; the
+lags, their correlations and flags become further columns.  The 50 ms default, about 17 m of path difference, is a choice nobody
+has measured.  A pair of different lengths is cut to the shorter, and ``samples`` says so.  Files of equal length and rate are scored as
 one batch.  Writes ``metrics.csv`` and ``metrics_summary.csv`` (the tester's files) into the mode directory or ``--out`` (default: the estimate's
 directory) and prints the summary.  Without ``--input`` the ``_in`` columns are empty.  This is the way to score a multi-rank run as a whole, or the
 output folders of another implementation."""
@@ -38,8 +41,9 @@ def wav_names(d):
     return sorted(f for f in os.listdir(d) if f.lower().endswith(".wav"))
 
 
-def score(reference, estimate, inp=None, values=metrics.VALUES, device="cuda:0"):
-    """the rows of ``metrics.report_rows`` for every wav name present in ``reference`` and ``estimate`` (and ``inp``, when given)"""
+def score(reference, estimate, inp=None, values=metrics.VALUES, device="cuda:0", align=None):
+    """the rows of ``metrics.report_rows`` for every wav name present in ``reference`` and ``estimate`` (and ``inp``, when given); ``align``: the
+    search window in ms of ``metrics.evaluate``, None = score the pairs as they are"""
     names = [n for n in wav_names(estimate) if os.path.exists(os.path.join(reference, n)) and (inp is None or os.path.exists(os.path.join(inp, n)))]
     if not names:
         raise SystemExit(f"evaluate: no wav name is common to {reference} and {estimate}" + (f" and {inp}" if inp else ""))
@@ -60,9 +64,9 @@ def score(reference, estimate, inp=None, values=metrics.VALUES, device="cuda:0")
     rows = [None] * len(items)
     for (fs, L), idx in groups.items():
         ref, est = (torch.from_numpy(np.stack([items[i][k] for i in idx])).to(device) for k in (0, 1))
-        out = metrics.evaluate(est, ref, fs, values=values)
+        out = metrics.evaluate(est, ref, fs, values=values, align=align)
         if inp:
-            before = metrics.evaluate(torch.from_numpy(np.stack([items[i][2] for i in idx])).to(device), ref, fs, values=values)
+            before = metrics.evaluate(torch.from_numpy(np.stack([items[i][2] for i in idx])).to(device), ref, fs, values=values, align=align)
         else:       # no input signals: the _in and _delta columns stay empty
             nan = torch.full_like(out.values, float("nan"))
             before = metrics.Evaluation(nan, torch.zeros_like(out.flags), out.kept_frames, out.frames, out.samples, out.names)
@@ -79,6 +83,8 @@ def main(argv=None):
     ap.add_argument("--input", help="directory of the degraded wavs (fills the _in and _delta columns)")
     ap.add_argument("--out", help="directory for metrics.csv and metrics_summary.csv")
     ap.add_argument("--values", default=",".join(metrics.VALUES), help="comma-separated subset of " + ",".join(metrics.VALUES))
+    ap.add_argument("--align", nargs="?", type=float, const=metrics.MAX_LAG_MS, default=None, metavar="MS",
+                    help="time-align every pair before it is scored: integer lag within +-MS ms (default %(const)s), pair trimmed to the overlap")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
     if a.mode_dir:
@@ -90,7 +96,7 @@ def main(argv=None):
         if not (a.reference and a.estimate):
             ap.error("give a mode directory, or both --reference and --estimate")
         ref, est, inp, out = a.reference, a.estimate, a.input, a.out or a.estimate
-    rows = score(ref, est, inp, values=tuple(v for v in a.values.split(",") if v), device=a.device)
+    rows = score(ref, est, inp, values=tuple(v for v in a.values.split(",") if v), device=a.device, align=a.align)
     os.makedirs(out, exist_ok=True)
     summary = metrics.summary_rows(rows)
     metrics.write_report(os.path.join(out, "metrics.csv"), rows)
