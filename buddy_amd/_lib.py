@@ -96,6 +96,10 @@ _SIGS = {
                                             C.c_longlong, C.c_void_p, C.c_void_p]),
     "buddy_srmr_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "buddy_ism_half_width": (C.c_int, []),
+    "buddy_ism_tile": (C.c_int, []),
+    "buddy_ism_list": (C.c_int, []),
+    "buddy_shoebox_rir": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.c_longlong, C.c_void_p, C.c_void_p]),
     "buddy_prof_collect_wino4": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                            C.POINTER(C.c_longlong)]),
     "buddy_prof_collect_hbm": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),

@@ -915,6 +915,23 @@ int buddy_srmr_scores(const double* E, const int* frames, int B, int J, int K, l
   return finish();
 }
 
+// ---- shoebox room impulse responses, image-source method (ism.hip) ----
+int buddy_ism_half_width(void) { return ism_half_width(); }
+int buddy_ism_tile(void) { return ism_tile(); }
+int buddy_ism_list(void) { return ism_list(); }
+
+int buddy_shoebox_rir(const double* rooms, int B, int fs, int N, int max_order, float* h, long long ldh, int* flags, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_shoebox_rir: ") + why); return BUDDY_ERR_ARG; };
+  if (!rooms || !h || !flags) return bad("null pointer");
+  if (B < 1 || B > 65535) return bad("B must be in 1..65535");
+  if (fs < 1000 || fs > 1000000) return bad("fs must be in 1000..1000000");
+  if (N < 1 || N > (1 << 20)) return bad("N must be in 1..2^20");
+  if (ldh < N) return bad("ldh is smaller than N");
+  if (max_order < -1) return bad("max_order must be >= -1 (-1: no cap)");
+  launch_shoebox_rir(rooms, B, fs, N, max_order, h, ldh, flags, (hipStream_t)stream);
+  return finish();
+}
+
 // ---- WPE warm start ----
 int buddy_wpe(const double* Y, double* X, double* scratch, int rows, int T, int taps, int delay, int iterations, void* stream) {
   if (!Y || !X || !scratch || rows < 1 || T < 1 || taps < 1 || taps > 56 || delay < 0 || iterations < 0) { set_error("bad wpe arguments (taps <= 56)"); return BUDDY_ERR_ARG; }

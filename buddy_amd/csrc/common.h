@@ -219,6 +219,12 @@ void launch_modulation_energies(const float* env, const int* lens, int B, int J,
                                 int* frames, hipStream_t st);
 void launch_srmr_scores(const double* E, const int* frames, int B, int J, long long ldm, const double* erb, const double* l, double* out, double* Ebar, int* flags,
                         hipStream_t st);
+// shoebox room impulse responses by the image-source method (ism.hip): rooms (B, 16) device doubles; the arguments are checked by the C entry, the
+// rows themselves by the kernel (an invalid row is zeros with flag 0)
+int ism_half_width();                        // Hw of the fractional-delay kernel
+int ism_tile();                              // output samples per workgroup
+int ism_list();                              // images per LDS chunk of a tile's list
+void launch_shoebox_rir(const double* rooms, int B, int fs, int N, int max_order, float* h, long long ldh, int* flags, hipStream_t st);
 void launch_axpy(float* dst, const float* src, float alpha, long long n, int accumulate, hipStream_t st);
 // fir=True resampling with the (1,3,3,1) kernel: (H,W)->(2H,2W) / (H,W)->(H/2,W/2); adjoints: up^T = 4 down, down^T = up / 4
 void launch_fir_up2(const float* x, float* y, int B, int H, int W, int C, float scale, int accumulate, hipStream_t st);

@@ -710,6 +710,27 @@ int buddy_modulation_energies(const float* env, const int* lens, int B, int J, l
 int buddy_srmr_scores(const double* E, const int* frames, int B, int J, int K, long long ldm, const double* erb /*host*/, const double* l /*host*/, double* out,
                       double* Ebar, int* flags, void* stream);
 
+/* ---- room impulse responses of shoebox rooms by the image-source method (buddy_amd/utils/rooms.py; Allen & Berkley 1979; no
+ * reference counterpart).  rooms: DEVICE (B, 16) doubles per row: L (3) room size [m], s (3) source, r (3) receiver, beta (6) pressure reflection
+ * coefficients of the walls x = 0, x = Lx, y = 0, y = Ly, z = 0, z = Lz, c speed of sound [m/s].  Per axis a an image (m, q), m any integer, q in {0, 1}:
+ * offset X_a = 2 m L_a + (1 - 2 q) s_a - r_a, gain g_a = beta_a0^|m - q| beta_a1^|m| (0^0 = 1), order o_a = |m - q| + |m|.  An image triple has
+ * d = sqrt(X^2 + Y^2 + Z^2), A = g_x g_y g_z / (4 pi d), tau = d fs / c, o = o_x + o_y + o_z.
+ *   h[b][n] = sum A sinc(x) (1 + cos(pi x / Hw)) / 2,  x = n - Hw - tau,  n = 0..N - 1,
+ * over the images with |x| < Hw (and o <= max_order unless max_order = -1), Hw = buddy_ism_half_width() = 40: sample n sits at time (n - Hw) / fs, the
+ * direct peak near tau_direct + Hw.  All arithmetic, the delays included, is double; the sum is rounded once to fp32.  A sample's terms are added in the
+ * ascending order of (m_x, q_x, m_y, q_y, q_z, m_z): no atomics, and a row's response does not depend on B, on the grid or on the run.
+ * flags[b] = 1 for a valid row.  A row is invalid -- zeros in h[b][0..N - 1], flags[b] = 0, no other row disturbed -- when a value is not finite, an
+ * L_a <= 0, s or r is not strictly inside the room, a |beta| > 1, c <= 0, or |s - r| < 0.01 m.
+ * BUDDY_ERR_ARG, with nothing launched, for: a null pointer; B outside 1..65535; fs outside 1000..1000000; N outside 1..2^20; ldh < N; max_order < -1.
+ * Nothing is written outside h[b][0..N - 1] and flags[0..B - 1]; no workspace.  Work: about (4/3) pi (c N / fs)^3 / (Lx Ly Lz) images of 2 Hw taps each
+ * per row when no order caps them -- the rooms are device data, so the entry cannot bound it: the CALLER does (rooms.shoebox_rir refuses above
+ * max_images).  buddy_ism_tile: output samples per workgroup; buddy_ism_list: images per LDS chunk of a tile's image list (the sizes around which
+ * the unit tests place their lengths and rooms). */
+int buddy_ism_half_width(void);
+int buddy_ism_tile(void);
+int buddy_ism_list(void);
+int buddy_shoebox_rir(const double* rooms, int B, int fs, int N, int max_order, float* h, long long ldh, int* flags, void* stream);
+
 /* ---- the small fp32 kernels of the network, one entry per launcher (unit tests: tests/test_hip_small_ops.py).  All tensors NHWC with H = time, device
  * pointers, fp32.  Each entry returns BUDDY_ERR_ARG with a message, with nothing launched, for a null required pointer, an empty shape, or a shape its
  * kernels cannot compute (named per entry).

@@ -1,0 +1,108 @@
+#!/usr/bin/env python
+"""Turn a folder of clean speech into a paired test set with simulated rooms (buddy_amd/utils/rooms.py): one shoebox room per
+file, its impulse response computed on the GPU by the image-source method.
+
+    python tools/make_paired_set.py --clean DIR --out DIR [--seed 0] [--fs 16000] [--t60 LO HI] [--dims X0 X1 Y0 Y1 Z0 Z1]
+                                    [--rir-seconds S] [--max-order K] [--num N] [--reverberant]
+
+``--clean`` holds ``<spk>/*.wav`` (a flat folder of wavs is the one speaker ``all``); int or float wavs of any rate, several channels averaged to
+mono; a file at another rate than ``--fs`` goes through the project's resampler.  Written under ``--out``, the layout ``VCTKTestPaired`` and with it
+every paired mode of the tester reads:
+
+    clean/<spk>/<id>.wav        float32 at --fs
+    rir/<spk>/<id>.wav          float32, the simulated response as computed: neither trimmed nor normalised (the loader does both)
+    rooms.csv                   per file: the room, its nominal (Eyring) T60, and EDT / T20 / T30 / C50 / DRR measured on the response
+    reverberant/<spk>/<id>.wav  with --reverberant: the clean file under the loader's form of the RIR (trimmed to its peak, peak 1), through
+                                RIROperator.degradation; what the real-recordings mode and tools/srmr.py take
+
+A file's room is a function of ``--seed`` and ``<spk>/<id>`` alone, so the same seed and names reproduce every file byte for byte, whatever else is in
+the folder.  The response is 1.5 x the nominal T60 long unless ``--rir-seconds`` fixes it."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+from scipy.io import wavfile
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from buddy_amd.datasets.vctk import _read  # noqa: E402
+from buddy_amd.utils import acoustics, resample, rooms  # noqa: E402
+
+
+def read_wav(path):
+    """(float32 mono samples, rate) through the loaders' own reader; several channels are averaged, as the real-recordings mode reads them"""
+    a, fs = _read(path)
+    if a.ndim > 1:
+        a = np.mean(a, axis=1)
+    if len(a) < 1:
+        raise SystemExit(f"make_paired_set: {path} is empty")
+    return np.ascontiguousarray(a, dtype=np.float32), int(fs)
+
+
+def list_clean(base):
+    """[(speaker, id, path)] sorted by speaker, then file"""
+    wavs = lambda d: sorted(f for f in os.listdir(d) if f.lower().endswith(".wav"))
+    out = [("all", f[:-4], os.path.join(base, f)) for f in wavs(base)]
+    for spk in sorted(d for d in os.listdir(base) if os.path.isdir(os.path.join(base, d))):
+        out += [(spk, f[:-4], os.path.join(base, spk, f)) for f in wavs(os.path.join(base, spk))]
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--clean", required=True, help="folder of <spk>/*.wav (or of wavs)")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--fs", type=int, default=16000)
+    ap.add_argument("--t60", type=float, nargs=2, default=(0.2, 1.0), metavar=("LO", "HI"), help="range of the nominal T60 [s]")
+    ap.add_argument("--dims", type=float, nargs=6, default=(3, 8, 3, 8, 2.4, 3.5), metavar=("X0", "X1", "Y0", "Y1", "Z0", "Z1"), help="ranges of the room size [m]")
+    ap.add_argument("--rir-seconds", type=float, default=None, help="length of every response (default: 1.5 x its nominal T60)")
+    ap.add_argument("--max-order", type=int, default=-1, help="cap of the reflection order (default: none)")
+    ap.add_argument("--num", type=int, default=0, help="take only the first N files")
+    ap.add_argument("--reverberant", action="store_true", help="also write reverberant/<spk>/<id>.wav")
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args(argv)
+    files = list_clean(a.clean)
+    if a.num > 0:
+        files = files[:a.num]
+    if not files:
+        raise SystemExit(f"make_paired_set: no wav under {a.clean}")
+    names = [f"{spk}/{uid}" for spk, uid, _ in files]
+    dims = tuple((a.dims[2 * k], a.dims[2 * k + 1]) for k in range(3))
+    drawn = rooms.draw_rooms(names, a.seed, t60=tuple(a.t60), dims=dims)
+    if a.reverberant:
+        from buddy_amd.config import compose
+        from buddy_amd.testing.operators.reverb import RIROperator
+        op_hp = compose().tester.informed_dereverberation.op_hp
+    rows = []
+    for (spk, uid, path), name, rm in zip(files, names, drawn):
+        x, fs_in = read_wav(path)
+        xt = torch.from_numpy(x).to(a.device)
+        if fs_in != a.fs:
+            xt = resample.resample(xt, fs_in, a.fs)
+        nominal = rooms.eyring_t60(rm[0:3], rm[9:15], rm[15])
+        n = int(round((a.rir_seconds if a.rir_seconds is not None else 1.5 * nominal) * a.fs))
+        h, flags = rooms.shoebox_rir(torch.from_numpy(rm[None]).to(a.device), a.fs, n, max_order=a.max_order)
+        ac = acoustics.rir_acoustics(h, a.fs)
+        rows += rooms.room_rows([name], rm[None], a.fs, n, ac, flags)
+        for sub, v in (("clean", xt), ("rir", h[0])):
+            os.makedirs(os.path.join(a.out, sub, spk), exist_ok=True)
+            wavfile.write(os.path.join(a.out, sub, spk, uid + ".wav"), a.fs, v.cpu().numpy().astype(np.float32))
+        if a.reverberant:
+            hc = h[0].cpu()
+            k = hc[int(torch.argmax(hc.abs())):]
+            k = k / k.abs().max()
+            op = RIROperator(op_hp, time_kernel_size=len(k), sample_rate=a.fs, device=a.device)
+            op.update_params(k)
+            y = op.degradation(xt[None])[0]
+            os.makedirs(os.path.join(a.out, "reverberant", spk), exist_ok=True)
+            wavfile.write(os.path.join(a.out, "reverberant", spk, uid + ".wav"), a.fs, y.detach().cpu().numpy().astype(np.float32))
+        print(f"{name}: {rm[0]:.2f} x {rm[1]:.2f} x {rm[2]:.2f} m, nominal T60 {nominal:.3f} s, {n} samples, measured T20 {rows[-1]['T20']:.3f} s")
+    rooms.write_rooms(os.path.join(a.out, "rooms.csv"), rows)
+    print(os.path.join(a.out, "rooms.csv"))
+    return rows
+
+
+if __name__ == "__main__":
+    main()
