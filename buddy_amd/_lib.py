@@ -96,6 +96,16 @@ _SIGS = {
                                             C.c_longlong, C.c_void_p, C.c_void_p]),
     "buddy_srmr_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "buddy_frame_spectra": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int, _f32p, C.c_longlong, C.c_void_p]),
+    "buddy_cepstral_distance_workspace": (C.c_longlong, [C.c_int, C.c_int]),
+    "buddy_cepstral_distance": (C.c_int, [_f32p, _f32p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_longlong, C.c_void_p]),
+    "buddy_fwsegsnr_workspace": (C.c_longlong, [C.c_int, C.c_int]),
+    "buddy_fwsegsnr": (C.c_int, [_f32p, _f32p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_longlong, C.c_void_p]),
+    "buddy_llr_workspace": (C.c_longlong, [C.c_int, C.c_longlong, C.c_int, C.c_int]),
+    "buddy_llr": (C.c_int, [_f32p, _f32p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                            C.c_longlong, C.c_void_p]),
     "buddy_ism_half_width": (C.c_int, []),
     "buddy_ism_tile": (C.c_int, []),
     "buddy_ism_list": (C.c_int, []),

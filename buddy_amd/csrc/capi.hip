@@ -915,6 +915,74 @@ int buddy_srmr_scores(const double* E, const int* frames, int B, int J, int K, l
   return finish();
 }
 
+// ---- spectral-envelope distortion of (estimate, clean) pairs (spectral.hip) ----
+static long long frames_at(long long len, int frame, int hop) { return len >= frame ? (len - frame) / hop + 1 : 0; }
+
+int buddy_frame_spectra(const float* x, const int* lens, int B, long long ld, int frame, int hop, float* S, long long ldf, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_frame_spectra: ") + why); return BUDDY_ERR_ARG; };
+  if (!x || !lens || !S) return bad("null pointer");
+  if (frame < 1 || frame > 512) return bad("frame must be in 1..512");
+  if (hop < 1) return bad("hop must be >= 1");
+  int longest;
+  if (int rc = check_rows(lens, B, ld, 1, stream, "buddy_frame_spectra", &longest)) return rc;
+  const long long maxF = frames_at(longest, frame, hop);
+  if (ldf < at_least_one(maxF)) return bad("ldf is smaller than the frames of the longest row");
+  launch_frame_spectra(x, lens, B, ld, maxF, frame, hop, S, ldf, (hipStream_t)stream);
+  return finish();
+}
+
+long long buddy_cepstral_distance_workspace(int B, int max_frames) {
+  if (B < 1 || max_frames < 0) return -1;
+  return 8LL * B * at_least_one(max_frames) * 2 * spectral_cepstra();
+}
+
+int buddy_cepstral_distance(const float* X, const float* E, const int* frames, int B, long long ldf, const double* g, const double* d, double* out, int* flags,
+                            void* ws, long long ws_bytes, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_cepstral_distance: ") + why); return BUDDY_ERR_ARG; };
+  if (!X || !E || !frames || !g || !d || !out || !flags || !ws) return bad("null pointer");
+  int longest;
+  if (int rc = check_rows(frames, B, ldf, 0, stream, "buddy_cepstral_distance", &longest)) return rc;
+  if (ws_bytes < buddy_cepstral_distance_workspace(B, longest)) return bad("the workspace is smaller than buddy_cepstral_distance_workspace(B, most frames)");
+  launch_cepstral_distance(X, E, frames, B, ldf, longest, g, d, out, flags, (double*)ws, (hipStream_t)stream);
+  return finish();
+}
+
+long long buddy_fwsegsnr_workspace(int B, int max_frames) {
+  if (B < 1 || max_frames < 0) return -1;
+  return 16LL * B * at_least_one(max_frames);
+}
+
+int buddy_fwsegsnr(const float* X, const float* E, const int* frames, int B, long long ldf, const double* g, const double* M, int J, double* out, int* counts,
+                   int* flags, void* ws, long long ws_bytes, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_fwsegsnr: ") + why); return BUDDY_ERR_ARG; };
+  if (!X || !E || !frames || !g || !M || !out || !counts || !flags || !ws) return bad("null pointer");
+  if (J < 1 || J > 64) return bad("J must be in 1..64");
+  int longest;
+  if (int rc = check_rows(frames, B, ldf, 0, stream, "buddy_fwsegsnr", &longest)) return rc;
+  if (ws_bytes < buddy_fwsegsnr_workspace(B, longest)) return bad("the workspace is smaller than buddy_fwsegsnr_workspace(B, most frames)");
+  launch_fwsegsnr(X, E, frames, B, ldf, longest, g, M, J, out, counts, flags, (double*)ws, (hipStream_t)stream);
+  return finish();
+}
+
+long long buddy_llr_workspace(int B, long long max_len, int frame, int hop) {
+  if (B < 1 || max_len < 1 || max_len > (1LL << 30) || frame < 1 || frame > 512 || hop < 1) return -1;
+  return 16LL * B * at_least_one(frames_at(max_len, frame, hop));
+}
+
+int buddy_llr(const float* e, const float* x, const int* lens, int B, long long ld, int frame, int hop, int order, double* out, int* counts, int* flags, void* ws,
+              long long ws_bytes, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_llr: ") + why); return BUDDY_ERR_ARG; };
+  if (!e || !x || !lens || !out || !counts || !flags || !ws) return bad("null pointer");
+  if (frame < 1 || frame > 512) return bad("frame must be in 1..512");
+  if (hop < 1) return bad("hop must be >= 1");
+  if (order < 1 || order > spectral_max_order() || order >= frame) return bad("order must be in 1..16 and below the frame length");
+  int longest;
+  if (int rc = check_rows(lens, B, ld, 1, stream, "buddy_llr", &longest)) return rc;
+  if (ws_bytes < buddy_llr_workspace(B, longest, frame, hop)) return bad("the workspace is smaller than buddy_llr_workspace(B, longest row, frame, hop)");
+  launch_llr(e, x, lens, B, ld, frames_at(longest, frame, hop), frame, hop, order, out, counts, flags, (double*)ws, (hipStream_t)stream);
+  return finish();
+}
+
 // ---- shoebox room impulse responses, image-source method (ism.hip) ----
 int buddy_ism_half_width(void) { return ism_half_width(); }
 int buddy_ism_tile(void) { return ism_tile(); }

@@ -219,6 +219,18 @@ void launch_modulation_energies(const float* env, const int* lens, int B, int J,
                                 int* frames, hipStream_t st);
 void launch_srmr_scores(const double* E, const int* frames, int B, int J, long long ldm, const double* erb, const double* l, double* out, double* Ebar, int* flags,
                         hipStream_t st);
+// spectral-envelope distortion of (estimate, clean) pairs (spectral.hip): ragged rows, device length and frame-count arrays; arguments, lengths,
+// strides and workspaces are checked by the C entries, which pass the largest frame count (max_frames) for the grids.  Spectra are (B, ldf, 257) fp32
+int spectral_bins();                         // 257
+int spectral_cepstra();                      // coefficients per signal and frame in the workspace of the cepstral distance
+int spectral_max_order();
+void launch_frame_spectra(const float* x, const int* lens, int B, long long ld, long long max_frames, int frame, int hop, float* S, long long ldf, hipStream_t st);
+void launch_cepstral_distance(const float* X, const float* E, const int* frames, int B, long long ldf, int max_frames, const double* g, const double* d, double* out,
+                              int* flags, double* ws, hipStream_t st);
+void launch_fwsegsnr(const float* X, const float* E, const int* frames, int B, long long ldf, int max_frames, const double* g, const double* M, int J, double* out,
+                     int* counts, int* flags, double* ws, hipStream_t st);
+void launch_llr(const float* e, const float* x, const int* lens, int B, long long ld, long long max_frames, int frame, int hop, int order, double* out, int* counts,
+                int* flags, double* ws, hipStream_t st);
 // shoebox room impulse responses by the image-source method (ism.hip): rooms (B, 16) device doubles; the arguments are checked by the C entry, the
 // rows themselves by the kernel (an invalid row is zeros with flag 0)
 int ism_half_width();                        // Hw of the fractional-delay kernel

@@ -16,25 +16,22 @@
 // and per-segment values go through a workspace and are summed by one workgroup per row): no atomics, and a row's result does not depend on
 // its batch.  All of it runs once per tester mode, after sampling: latency-bound, written for clarity.
 //
-// The frame FFT (frame_fft) is a radix-2 Stockham transform of 512 complex points in LDS, one wave per transform, 4 butterflies per lane and
-// stage, two buffers of 512 float2 per wave.  Reads of a stage are consecutive 8-byte words (conflict-free); the writes of the first stages
-// have a stride of 2 Ns words and run at half rate (2-way conflicts), which nine stages of four instructions do not repay removing.  The
-// stages are separated by workgroup barriers, so every wave of a workgroup runs the transform, also when its frame lies past the row's end
-// (its input is then zero and nothing is stored).
+// The frame FFT (frame_fft) lives in fft512.h, shared with spectral.hip.
 #include "common.h"
+#include "fft512.h"
 
 namespace buddy {
 namespace {
-constexpr int MT_NT = 256;                    // threads per workgroup (4 waves)
-constexpr int MT_NW = MT_NT / 64;
+constexpr int MT_NT = FFT_NT;                 // threads per workgroup (4 waves)
+constexpr int MT_NW = FFT_NW;
 constexpr int MT_PER = 4;
 constexpr int MT_TILE = MT_NT * MT_PER;       // samples per step of the row reductions (buddy_metrics_tile)
-constexpr int FR = 256, HOP = 128, NFFT = 512, NBIN = NFFT / 2 + 1, SEG = 30;
+constexpr int FR = 256, HOP = 128, NFFT = FFT_N, NBIN = NFFT / 2 + 1, SEG = 30;
 constexpr double ST_EPS = 2.220446049250313e-16;          // 2^-52
 constexpr int MAXJ = 32;
 
 __device__ __forceinline__ int frames_of(int len) { return len >= FR ? (len - FR) / HOP + 1 : 0; }
-__device__ __forceinline__ double window_d(int i) { return 0.5 - 0.5 * cospi(2.0 * (double)(i + 1) / 257.0); }      // interior of a 258-point Hann window
+__device__ __forceinline__ double window_d(int i) { return fft_window_d(i, FR); }            // interior of a 258-point Hann window
 
 template <int K>
 __device__ __forceinline__ void block_sum(double (&v)[K], double (*lds)[K], int tid) {      // the sums land in every thread
@@ -181,54 +178,7 @@ __global__ __launch_bounds__(MT_NT) void gather_ola_kernel(const float* __restri
   eo[(long long)b * ldo + n] = ae;
 }
 
-// ---- the frame FFT -----------------------------------------------------------------------------------------------------------------------
-struct FftLds {
-  float2 buf[MT_NW][2][NFFT];                 // 32 KB
-  float2 tw[NFFT / 2];                        // exp(-2 pi i t / 512)
-  float win[FR];
-};
-
-__device__ __forceinline__ void fft_tables(FftLds& s, int tid) {      // 256 threads: one twiddle and one window value each, from double
-  double sn, cs;
-  sincospi(-2.0 * (double)tid / (double)NFFT, &sn, &cs);
-  s.tw[tid] = make_float2((float)cs, (float)sn);
-  s.win[tid] = (float)window_d(tid);
-  __syncthreads();
-}
-
-// the windowed frame at xf (nullptr: zeros), zero-padded to 512, into buffer 0 of wave wv
-__device__ __forceinline__ void frame_load(FftLds& s, int wv, int lane, const float* xf) {
-#pragma unroll
-  for (int i = 0; i < FR / 64; ++i) {
-    const int n = lane + 64 * i;
-    s.buf[wv][0][n] = make_float2(xf ? __fmul_rn(s.win[n], xf[n]) : 0.f, 0.f);
-    s.buf[wv][0][FR + n] = make_float2(0.f, 0.f);
-  }
-}
-
-// in: buffer 0 of wave wv, written by this wave.  Returns the buffer that holds the spectrum in natural order (nine stages: buffer 1).  Every wave of
-// the workgroup must call it (barriers); the result may be read after it returns
-__device__ __forceinline__ const float2* frame_fft(FftLds& s, int wv, int lane) {
-  int cur = 0;
-  for (int Ns = 1; Ns < NFFT; Ns <<= 1, cur ^= 1) {
-    __syncthreads();
-    const float2* in = s.buf[wv][cur];
-    float2* out = s.buf[wv][cur ^ 1];
-    const int tstep = (NFFT / 2) / Ns;
-#pragma unroll
-    for (int i = 0; i < NFFT / 2 / 64; ++i) {
-      const int j = lane + 64 * i, k = j & (Ns - 1);
-      const float2 w = s.tw[k * tstep], v0 = in[j], u = in[j + NFFT / 2];
-      const float2 v1 = make_float2(u.x * w.x - u.y * w.y, u.x * w.y + u.y * w.x);
-      const int j0 = ((j - k) << 1) + k;
-      out[j0] = make_float2(v0.x + v1.x, v0.y + v1.y);
-      out[j0 + Ns] = make_float2(v0.x - v1.x, v0.y - v1.y);
-    }
-  }
-  __syncthreads();
-  return s.buf[wv][cur];
-}
-
+// ---- the frame FFT: fft512.h, here with frames of 256 samples ------------------------------------------------------------------------------------
 struct Bands { int J; int lo[MAXJ]; int hi[MAXJ]; };        // bins [lo, hi) within 0..257, checked by the C entry
 
 __global__ __launch_bounds__(MT_NT) void band_spectra_kernel(const float* __restrict__ x, const int* __restrict__ lens, long long ld, Bands bands,
@@ -237,8 +187,8 @@ __global__ __launch_bounds__(MT_NT) void band_spectra_kernel(const float* __rest
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, b = blockIdx.y;
   const int M = frames_of(lens[b]);
   const long long m = (long long)blockIdx.x * MT_NW + wv;
-  fft_tables(s, tid);
-  frame_load(s, wv, lane, m < M ? x + (long long)b * ld + m * HOP : nullptr);
+  fft_tables(s, tid, FR);
+  frame_load(s, wv, lane, m < M ? x + (long long)b * ld + m * HOP : nullptr, FR);
   const float2* X = frame_fft(s, wv, lane);
   if (m >= M || lane >= bands.J) return;
   double acc = 0.0;
@@ -368,8 +318,8 @@ __global__ __launch_bounds__(MT_NT) void lsd_frames_kernel(const float* __restri
   const int M = frames_of(lens[b]);
   const long long m = (long long)blockIdx.x * MT_NW + wv;
   const bool live = m < M;
-  fft_tables(s, tid);
-  frame_load(s, wv, lane, live ? x + (long long)b * ld + m * HOP : nullptr);
+  fft_tables(s, tid, FR);
+  frame_load(s, wv, lane, live ? x + (long long)b * ld + m * HOP : nullptr, FR);
   const float2* X = frame_fft(s, wv, lane);
   double P[NBIN / 64 + 1];                    // bins lane + 64 i, i < 4, and bin 256 in lane 0
 #pragma unroll
@@ -378,7 +328,7 @@ __global__ __launch_bounds__(MT_NT) void lsd_frames_kernel(const float* __restri
     P[i] = k < NBIN ? (double)X[k].x * (double)X[k].x + (double)X[k].y * (double)X[k].y : 0.0;
   }
   __syncthreads();                            // the spectrum has been read: buffer 0 is free for the second frame
-  frame_load(s, wv, lane, live ? e + (long long)b * ld + m * HOP : nullptr);
+  frame_load(s, wv, lane, live ? e + (long long)b * ld + m * HOP : nullptr, FR);
   const float2* E = frame_fft(s, wv, lane);
   if (!live) return;
   const double g = gain[b], d = delta[b], g2 = g * g;

@@ -71,6 +71,16 @@ def srmr_options(tester_cfg):
     return False if sm is None else bool(sm.get("use", False))
 
 
+def spectral_options(tester_cfg):
+    """(use, values) of the ``spectral`` block of a tester config; a config written before the block existed means (False, all three values)"""
+    from ..utils.spectral import VALUES
+    sp = tester_cfg.get("spectral", None)
+    if sp is None:
+        return False, VALUES
+    v = sp.get("values", None)
+    return bool(sp.get("use", False)), VALUES if v is None else tuple(str(s) for s in v)
+
+
 class Tester:
     def __init__(self, args, network, diff_params, test_set=None, device=None, in_training=False, batch_size=1, rank=0, world_size=1):
         self.args = args
@@ -189,7 +199,8 @@ class Tester:
         report = blind and rir_report_options(self.args.tester)[0] and not self.in_training and bool(self.paths)
         rep = []         # room-acoustics report: (name, estimated RIR, true RIR, the operator's parameters of that row) per written RIR wav
         scoring = metrics_options(self.args.tester)[0] and not self.in_training and bool(self.paths)
-        scored = []      # evaluation report: (name, clean, degraded, reconstructed) per written utterance, as written to the wavs
+        scored = []      # evaluation and spectral reports: (name, clean, degraded, reconstructed) per written utterance, as written to the wavs
+        spectral_on = spectral_options(self.args.tester)[0] and not self.in_training and bool(self.paths)
         srmr_on = srmr_options(self.args.tester) and not self.in_training and bool(self.paths)
         heard = []     # SRMR report: (name, degraded, reconstructed, clean) per written utterance, each row with the rate of its wav
         for s in range(0, len(mine), self.batch_size):
@@ -226,7 +237,7 @@ class Tester:
                         write_audio_file(est[b] if est.dim() == 2 else est, sr, name, path=self.paths[mode + "estimated_rir"])
                     if report:
                         rep.append((name, est[b] if est.dim() == 2 else est, rirs[b], {k: v if k == "freqs" else v[b] for k, v in par.items()}))
-                    if scoring:
+                    if scoring or spectral_on:
                         scored.append((name, seg[b].detach(), y[b].detach(), pred[b].detach()))
                     if srmr_on:
                         heard.append((name, (y[b].detach(), sr), (pred[b].detach(), sr), (seg[b].detach(), sr)))
@@ -235,6 +246,8 @@ class Tester:
             self._write_rir_report(mode, rep, sr)
         if scoring:
             self._write_metrics_report(mode, scored, sr)
+        if spectral_on:
+            self._write_spectral_report(mode, scored, sr)
         if srmr_on:
             self._write_srmr_report(mode, heard)
         # utterance-batch data parallelism: ONE gather at the end of the run (RCCL over xGMI on the GPU box) -- afterwards every rank, in
@@ -304,6 +317,35 @@ class Tester:
         metrics.write_report(os.path.join(self.paths[mode], f"metrics{tag}.csv"), rows)
         metrics.write_report(os.path.join(self.paths[mode], f"metrics_summary{tag}.csv"), metrics.summary_rows(rows))
         self.metrics_report = rows
+
+    def _write_spectral_report(self, mode, scored, sr):
+        """Spectral distortion report of a paired mode (``tester.spectral.use``; utils/spectral.py), once per mode after sampling:
+        ``spectral.csv`` (per written utterance the cepstral distance, LLR and fwSegSNR of the degraded and of the reconstructed signal against the clean
+        one, and the difference) and ``spectral_summary.csv`` (n, mean, median, std per column) in the mode's directory.  ``scored`` as in
+        ``_write_metrics_report``, and ``tester.metrics.align`` is honoured in the same way, so both reports score the same trimmed pairs.  Every rank
+        writes its own rows (``spectral.rank<r>.csv`` when there are several); nothing is gathered -- ``tools/spectral.py`` scores the directory of a
+        multi-rank run as a whole."""
+        from ..utils import spectral
+        self.spectral_report = None
+        if not scored:
+            return
+        values = spectral_options(self.args.tester)[1]
+        use_align, max_lag_ms = align_options(self.args.tester)
+        window = max_lag_ms if use_align else None
+        groups = {}
+        for i, r in enumerate(scored):
+            groups.setdefault(int(r[1].numel()), []).append(i)
+        rows = [None] * len(scored)
+        for idx in groups.values():
+            clean, deg, rec = (torch.stack([scored[i][k].flatten().float() for i in idx]).to(self.device) for k in (1, 2, 3))
+            inp = spectral.evaluate(deg, clean, int(sr), values=values, align=window)
+            out = spectral.evaluate(rec, clean, int(sr), values=values, align=window)
+            for i, row in zip(idx, spectral.report_rows([scored[i][0] for i in idx], inp, out)):
+                rows[i] = row
+        tag = f".rank{self.rank}" if self.world_size > 1 else ""
+        spectral.write_report(os.path.join(self.paths[mode], f"spectral{tag}.csv"), rows)
+        spectral.write_report(os.path.join(self.paths[mode], f"spectral_summary{tag}.csv"), spectral.summary_rows(rows))
+        self.spectral_report = rows
 
     def _write_srmr_report(self, mode, items):
         """SRMR report of a mode (``tester.srmr.use``; utils/srmr.py), once per mode after sampling: ``srmr.csv`` (per written

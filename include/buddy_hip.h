@@ -710,6 +710,43 @@ int buddy_modulation_energies(const float* env, const int* lens, int B, int J, l
 int buddy_srmr_scores(const double* E, const int* frames, int B, int J, int K, long long ldm, const double* erb /*host*/, const double* l /*host*/, double* out,
                       double* Ebar, int* flags, void* stream);
 
+/* ---- spectral-envelope distortion of a paired run (buddy_amd/utils/spectral.py; no reference counterpart): cepstral distance,
+ * log-likelihood ratio and frequency-weighted segmental SNR of pairs (estimate e, clean reference x).  The conventions of the evaluation entries above
+ * hold: ragged rows inside a common stride, DEVICE length and frame-count arrays copied to the host once to be checked, nothing behind a row's end read,
+ * nothing outside the declared extents written, fixed-order sums without atomics, a row's result independent of its batch.  Frames are `frame` <= 512
+ * samples at hop `hop` under the window w[i] = 0.5 - 0.5 cos(2 pi (i + 1) / (frame + 1)), all FULL frames: frames(len) = (len - frame) / hop + 1 for
+ * len >= frame, else 0.  Spectra are (B, ldf, 257) fp32: S[b][f][k], k = 0..256, the bins of one frame next to each other.
+ * BUDDY_ERR_ARG, with nothing launched, for: a null pointer; B outside 1..65535; a length outside 1..2^30 or a frame count outside 0..2^30; a stride smaller
+ * than the longest row (the most frames) it holds; frame outside 1..512; hop < 1; J outside 1..64; order outside 1..16 or >= frame; a workspace below the
+ * size its query states (the queries give -1 for arguments out of range).
+ *
+ * buddy_frame_spectra: S[b][f][k] = |X[k]| of frame f < frames(lens[b]), X the 512-point transform (fp32, radix 2, the transform of buddy_band_spectra) of
+ *   the windowed, zero-padded frame (w rounded to fp32, one fp32 product per sample); the magnitude is formed in double and rounded once.
+ *   ldf >= max(frames of the longest row, 1).
+ *
+ * buddy_cepstral_distance: X, E spectra of the clean and the estimated rows with frames[b] frames; g, d DEVICE doubles (B): the estimate's gain and the
+ *   log floor.  Per frame and signal c[n] = (1/512) sum_{k = 0..511} 0.5 ln(|X[k]|^2 + d) cos(2 pi k n / 512), n = 0..24 (bins above 256 by symmetry; the
+ *   estimate with g |E[k]|); from each coefficient its mean over the row's frames is taken, per signal; frame value (10 / ln 10) sqrt(dc_0^2 + 2 sum_{n >= 1}
+ *   dc_n^2), dc = c_x - c_e, clipped to [0, 10]; out[b] = the mean over the frames, all in double.  No frame, or d[b] not above zero: NaN and flags[b] = 0.
+ *
+ * buddy_fwsegsnr: M: DEVICE (J, 257) doubles >= 0, the band weights.  X_j = sum_k M[j][k] |X[k]|, E_j = sum_k M[j][k] g |E[k]|; num = X_j^2, den = (X_j -
+ *   E_j)^2; band SNR 35 where den <= num 10^-3.5, else -10 where num <= den / 10, else 10 log10(num / den); W_j = X_j^0.2; frame value sum_j W_j snr_j / sum_j
+ *   W_j; a frame counts when sum_j W_j > 0.  out[b] = the mean over the counted frames, counts[b] their number; none: NaN and flags[b] = 0.
+ *
+ * buddy_llr: from the signals.  s = w x in double; r[k] = sum_i s[i] s[i + k], k = 0..order, of both frames; a frame counts when r_x[0] > 0 and r_e[0] > 0;
+ *   then r[0] *= 1 + 1e-9, Levinson-Durbin gives a (a[0] = 1) of each; frame value ln((a_e R_x a_e^T) / (a_x R_x a_x^T)), R_x the Toeplitz matrix of r_x,
+ *   clipped to [0, 2]; all in double.  out[b] = the mean over the counted frames, counts[b] their number; none: NaN and flags[b] = 0. */
+int buddy_frame_spectra(const float* x, const int* lens, int B, long long ld, int frame, int hop, float* S, long long ldf, void* stream);
+long long buddy_cepstral_distance_workspace(int B, int max_frames);
+int buddy_cepstral_distance(const float* X, const float* E, const int* frames, int B, long long ldf, const double* g, const double* d, double* out, int* flags,
+                            void* ws, long long ws_bytes, void* stream);
+long long buddy_fwsegsnr_workspace(int B, int max_frames);
+int buddy_fwsegsnr(const float* X, const float* E, const int* frames, int B, long long ldf, const double* g, const double* M, int J, double* out, int* counts,
+                   int* flags, void* ws, long long ws_bytes, void* stream);
+long long buddy_llr_workspace(int B, long long max_len, int frame, int hop);
+int buddy_llr(const float* e, const float* x, const int* lens, int B, long long ld, int frame, int hop, int order, double* out, int* counts, int* flags, void* ws,
+              long long ws_bytes, void* stream);
+
 /* ---- room impulse responses of shoebox rooms by the image-source method (buddy_amd/utils/rooms.py; Allen & Berkley 1979; no
  * reference counterpart).  rooms: DEVICE (B, 16) doubles per row: L (3) room size [m], s (3) source, r (3) receiver, beta (6) pressure reflection
  * coefficients of the walls x = 0, x = Lx, y = 0, y = Ly, z = 0, z = Lz, c speed of sound [m/s].  Per axis a an image (m, q), m any integer, q in {0, 1}:
