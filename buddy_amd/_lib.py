@@ -110,6 +110,12 @@ _SIGS = {
     "buddy_ism_tile": (C.c_int, []),
     "buddy_ism_list": (C.c_int, []),
     "buddy_shoebox_rir": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, C.c_longlong, C.c_void_p, C.c_void_p]),
+    "buddy_ism_max_bands": (C.c_int, []),
+    "buddy_ism_band_list": (C.c_int, []),
+    "buddy_band_combine_tile": (C.c_int, []),
+    "buddy_shoebox_bands": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p,
+                                      C.c_void_p]),
+    "buddy_band_combine": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p, C.c_int, _f32p, C.c_longlong, C.c_void_p]),
     "buddy_prof_collect_wino4": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                            C.POINTER(C.c_longlong)]),
     "buddy_prof_collect_hbm": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),

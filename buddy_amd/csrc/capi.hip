@@ -1000,6 +1000,38 @@ int buddy_shoebox_rir(const double* rooms, int B, int fs, int N, int max_order, 
   return finish();
 }
 
+// ---- banded rooms: per-band responses in double, then the FIR-bank combination (ism.hip) ----
+int buddy_ism_max_bands(void) { return ism_max_bands(); }
+int buddy_ism_band_list(void) { return ism_band_list(); }
+int buddy_band_combine_tile(void) { return band_combine_tile(); }
+
+int buddy_shoebox_bands(const double* rooms, const double* beta, const double* air, int B, int nb, int fs, int N, int max_order, double* u, long long ldu,
+                        int* flags, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_shoebox_bands: ") + why); return BUDDY_ERR_ARG; };
+  if (!rooms || !beta || !u || !flags) return bad("null pointer");
+  if (B < 1 || B > 65535) return bad("B must be in 1..65535");
+  if (nb < 1 || nb > ism_max_bands()) return bad("nb must be in 1..buddy_ism_max_bands()");
+  if (fs < 1000 || fs > 1000000) return bad("fs must be in 1000..1000000");
+  if (N < 1 || N > (1 << 20)) return bad("N must be in 1..2^20");
+  if (ldu < N) return bad("ldu is smaller than N");
+  if (max_order < -1) return bad("max_order must be >= -1 (-1: no cap)");
+  launch_shoebox_bands(rooms, beta, air, B, nb, fs, N, max_order, u, ldu, flags, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_band_combine(const double* u, int B, int nb, long long ldu, int N, const double* bank, int Nh, float* h, long long ldh, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_band_combine: ") + why); return BUDDY_ERR_ARG; };
+  if (!u || !bank || !h) return bad("null pointer");
+  if (B < 1 || B > 65535) return bad("B must be in 1..65535");
+  if (nb < 1 || nb > ism_max_bands()) return bad("nb must be in 1..buddy_ism_max_bands()");
+  if (N < 1 || N > (1 << 20)) return bad("N must be in 1..2^20");
+  if (ldu < N) return bad("ldu is smaller than N");
+  if (ldh < N) return bad("ldh is smaller than N");
+  if (Nh < 1 || Nh > 65537 || Nh % 2 == 0) return bad("Nh must be odd and in 1..65537");
+  launch_band_combine(u, B, nb, ldu, N, bank, Nh, h, ldh, (hipStream_t)stream);
+  return finish();
+}
+
 // ---- WPE warm start ----
 int buddy_wpe(const double* Y, double* X, double* scratch, int rows, int T, int taps, int delay, int iterations, void* stream) {
   if (!Y || !X || !scratch || rows < 1 || T < 1 || taps < 1 || taps > 56 || delay < 0 || iterations < 0) { set_error("bad wpe arguments (taps <= 56)"); return BUDDY_ERR_ARG; }

@@ -237,6 +237,13 @@ int ism_half_width();                        // Hw of the fractional-delay kerne
 int ism_tile();                              // output samples per workgroup
 int ism_list();                              // images per LDS chunk of a tile's list
 void launch_shoebox_rir(const double* rooms, int B, int fs, int N, int max_order, float* h, long long ldh, int* flags, hipStream_t st);
+// banded rooms (ism.hip): beta (B, nb, 6), air (B, nb) or NULL, u (B, nb, ldu) doubles; bank (nb, Nh) doubles
+int ism_max_bands();                         // the largest nb
+int ism_band_list();                         // images per LDS chunk of a banded tile's list
+int band_combine_tile();                     // outputs per workgroup of the combination
+void launch_shoebox_bands(const double* rooms, const double* beta, const double* air, int B, int nb, int fs, int N, int max_order, double* u, long long ldu,
+                          int* flags, hipStream_t st);
+void launch_band_combine(const double* u, int B, int nb, long long ldu, int N, const double* bank, int Nh, float* h, long long ldh, hipStream_t st);
 void launch_axpy(float* dst, const float* src, float alpha, long long n, int accumulate, hipStream_t st);
 // fir=True resampling with the (1,3,3,1) kernel: (H,W)->(2H,2W) / (H,W)->(H/2,W/2); adjoints: up^T = 4 down, down^T = up / 4
 void launch_fir_up2(const float* x, float* y, int B, int H, int W, int C, float scale, int accumulate, hipStream_t st);

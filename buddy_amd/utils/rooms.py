@@ -7,7 +7,11 @@ size L (3) [m], source s (3), receiver r (3), the pressure reflection coefficien
 speed of sound c [m/s].  ``eyring_beta`` / ``eyring_t60`` convert between a nominal reverberation time and a uniform coefficient; ``draw_rooms`` draws
 one room per file name from the project's counter-based generator; ``room_rows`` / ``write_rooms`` make ``rooms.csv``: what each room is, next to what
 ``utils/acoustics.rir_acoustics`` measures on its simulated response.  The two are not expected to agree: specular images in a rectangular room decay
-more slowly than Eyring's diffuse-field formula says (a 0.30 s nominal room measured T20 = 0.43 s), which is why the file carries both."""
+more slowly than Eyring's diffuse-field formula says (a 0.30 s nominal room measured T20 = 0.43 s), which is why the file carries both.
+
+Banded rooms give the walls their own coefficients per octave band and the air an attenuation per band:
+``shoebox_rir_bands`` computes the band responses in double and combines them through ``octave_bank``; ``draw_band_rooms`` tilts the nominal T60 of
+``draw_rooms``' room over the bands; ``room_rows`` takes the band block that adds the per-band columns of ``rooms.csv``."""
 from __future__ import annotations
 
 import math
@@ -23,6 +27,9 @@ ROOMS = 4                                            # purpose number of the roo
 MIN_DISTANCE = 0.01                                  # |s - r| below this makes a row invalid [m]
 COLUMNS = ("Lx", "Ly", "Lz", "sx", "sy", "sz", "rx", "ry", "rz", "beta_x0", "beta_x1", "beta_y0", "beta_y1", "beta_z0", "beta_z1", "c")
 MEASURED = ("EDT", "T20", "T30", "C50", "DRR")       # broadband values of rir_acoustics that rooms.csv carries
+ROOM_BANDS = 5                                       # purpose number of the per-band draws (draw_band_rooms): the next free one after ROOMS
+BAND_CENTRES = (125, 250, 500, 1000, 2000, 4000)     # default octave centres of banded rooms [Hz]
+BANK_TAPS = 1023                                     # default length of octave_bank's rows: a choice (see there)
 
 
 def room_row(dims, source, receiver, beta, c=343.0):
@@ -112,6 +119,11 @@ def draw_rooms(names, seed, t60=(0.2, 1.0), dims=((3, 8), (3, 8), (2.4, 3.5)), w
     uniform in their ranges, all walls get ``eyring_beta`` of them; source and receiver are uniform at least ``wall_margin`` from every wall and are
     drawn again (at most ``max_tries`` times, then RuntimeError) until they are ``min_dist`` apart.  The numbers come from the Philox stream
     ``rng.stream_key(seed, name)``, purpose ``ROOMS``: draw 0 is the room, draw 1 + i try i of the positions."""
+    return _draw_rooms(names, seed, t60, dims, wall_margin, min_dist, c, max_tries)[0]
+
+
+def _draw_rooms(names, seed, t60, dims, wall_margin, min_dist, c, max_tries):
+    """``draw_rooms`` and, next to the rows, the nominal T60 each was drawn with"""
     lo = np.array([d[0] for d in dims], dtype=np.float64)
     hi = np.array([d[1] for d in dims], dtype=np.float64)
     if not (np.all(lo > 2.0 * wall_margin) and np.all(hi >= lo)):
@@ -119,6 +131,7 @@ def draw_rooms(names, seed, t60=(0.2, 1.0), dims=((3, 8), (3, 8), (2.4, 3.5)), w
     if not (0 < t60[0] <= t60[1]) or min_dist < MIN_DISTANCE:
         raise ValueError("draw_rooms: the T60 range must be positive and ascending, min_dist at least 0.01 m")
     out = np.empty((len(names), 16), dtype=np.float64)
+    nominal = np.empty(len(names), dtype=np.float64)
     for b, name in enumerate(names):
         key = _rng.stream_key(seed, name)
         u = _rng.uniforms(key, ROOMS, 0, 4)
@@ -133,15 +146,171 @@ def draw_rooms(names, seed, t60=(0.2, 1.0), dims=((3, 8), (3, 8), (2.4, 3.5)), w
         else:
             raise RuntimeError(f"draw_rooms: no source / receiver pair {min_dist} m apart in {max_tries} tries for {name!r}")
         out[b] = room_row(L, s, r, eyring_beta(L, T, c), c)
-    return out
+        nominal[b] = T
+    return out, nominal
 
 
-def room_rows(names, rooms, fs, n, acoustics, flags=None):
+# ---- banded rooms: wall coefficients and air attenuation per octave band ----------------------------------------------------
+def _check_centres(fs, centres):
+    cs = tuple(float(f) for f in centres)
+    if not cs or not all(math.isfinite(f) and f > 0 for f in cs):
+        raise ValueError("band centres must be positive and finite")
+    if any(abs(b / a - 2.0) > 1e-9 for a, b in zip(cs, cs[1:])):
+        raise ValueError(f"band centres must ascend by octaves, got {cs}")
+    if cs[-1] >= 0.5 * float(fs):
+        raise ValueError(f"band centres must lie below fs / 2 = {0.5 * float(fs):g} Hz, got {cs[-1]:g}")
+    return cs
+
+
+def octave_bank(fs, centres=BAND_CENTRES, Nh=BANK_TAPS):
+    """(len(centres), Nh) float64 zero-phase FIR rows, centred on tap P = (Nh - 1) / 2, that split a signal into octave bands and sum to the unit
+    impulse at tap P exactly.  Magnitudes cross-fade as cos^2(pi / 2 * log2(f / f_k)) between neighbouring centres and are 1 below the lowest and
+    above the highest centre; designed by frequency sampling on a grid of the power of two >= 4 Nh points, centred, Hann-tapered
+    (w[n] = (1 + cos(pi (n - P) / (P + 1))) / 2) to ``Nh`` taps; the LAST row is then replaced by delta_P minus the sum of the others, so a room
+    whose bands are all equal is the broadband room delayed by P.  ``Nh`` must be odd; the centres ascend by octaves and lie below fs / 2.  The
+    default Nh = 1023 is a choice: the taper's main lobe is 4 fs / (Nh + 1) wide, 62.5 Hz at 16 kHz -- half of the narrowest cross-fade (125 to
+    250 Hz) -- for a delay of P = 511 samples, 32 ms."""
+    cs = _check_centres(fs, centres)
+    Nh = int(Nh)
+    if Nh < 1 or Nh % 2 == 0 or Nh > 65537:
+        raise ValueError(f"octave_bank: Nh must be odd and in 1..65537, got {Nh}")
+    nb, P = len(cs), (Nh - 1) // 2
+    G = 8
+    while G < 4 * Nh:
+        G *= 2
+    f = np.arange(G // 2 + 1, dtype=np.float64) * float(fs) / G
+    taper = 0.5 * (1.0 + np.cos(np.pi * np.arange(-P, P + 1, dtype=np.float64) / (P + 1)))
+    bank = np.zeros((nb, Nh), dtype=np.float64)
+    for k, fc in enumerate(cs[:-1]):
+        with np.errstate(divide="ignore"):
+            x = np.log2(f / fc)                                          # -inf at f = 0
+        x = np.clip(x, 0.0 if k == 0 else -1.0, 1.0)
+        mag = np.cos(0.5 * np.pi * x) ** 2
+        t = np.fft.irfft(mag, G)                                         # real and even: zero phase
+        bank[k] = t[np.arange(-P, P + 1) % G] * taper
+    bank[nb - 1] = -bank[:nb - 1].sum(axis=0)
+    bank[nb - 1, P] += 1.0
+    return bank
+
+
+def eyring_beta_bands(dims, t60s, c=343.0):
+    """(len(t60s), 6) float64: per band the uniform coefficient ``eyring_beta(dims, t60s[k], c)`` on all six walls"""
+    return np.array([[eyring_beta(dims, float(t), c)] * 6 for t in t60s], dtype=np.float64).reshape(-1, 6)
+
+
+def nearest_band(centres, f=1000.0):
+    """index of the centre nearest ``f`` on the octave axis (the lower one of a tie)"""
+    return int(np.argmin([abs(math.log2(float(v) / f)) for v in centres]))
+
+
+def draw_band_rooms(names, seed, centres=BAND_CENTRES, t60=(0.2, 1.0), slope=(0.0, 0.3), t60_clip=(0.05, 4.0), dims=((3, 8), (3, 8), (2.4, 3.5)),
+                    wall_margin=0.5, min_dist=0.5, c=343.0, max_tries=1000):
+    """(rooms (n, 16), beta (n, nb, 6), t60s (n, nb)) float64.  Geometry, positions and the nominal T60 are exactly ``draw_rooms``' for the same seed
+    and name; the nominal T60 is the value at 1 kHz.  One further uniform, draw 0 of purpose ``ROOM_BANDS`` of the same stream, gives a slope ``s``
+    per octave in ``slope``: T60_k = T60 * 2^(-s log2(f_k / 1000)), clipped to ``t60_clip`` [s] -- a positive slope shortens the high bands -- and
+    beta[k] = ``eyring_beta(dims, T60_k)`` on all six walls.  The row's own six coefficients are those of the band nearest 1 kHz."""
+    cs = tuple(float(f) for f in centres)
+    if not cs or not all(f > 0 for f in cs):
+        raise ValueError("draw_band_rooms: band centres must be positive")
+    if not (slope[0] <= slope[1]) or not (0 < t60_clip[0] <= t60_clip[1]):
+        raise ValueError("draw_band_rooms: the slope range must be ascending, the clip range positive and ascending")
+    rows, nominal = _draw_rooms(names, seed, t60, dims, wall_margin, min_dist, c, max_tries)
+    beta = np.empty((len(names), len(cs), 6), dtype=np.float64)
+    t60s = np.empty((len(names), len(cs)), dtype=np.float64)
+    k1 = nearest_band(cs)
+    for b, name in enumerate(names):
+        v = float(_rng.uniforms(_rng.stream_key(seed, name), ROOM_BANDS, 0, 1)[0])
+        s = slope[0] + v * (slope[1] - slope[0])
+        t60s[b] = np.clip([nominal[b] * 2.0 ** (-s * math.log2(f / 1000.0)) for f in cs], t60_clip[0], t60_clip[1])
+        beta[b] = eyring_beta_bands(rows[b, 0:3], t60s[b], c)
+        rows[b, 9:15] = beta[b, k1]
+    return rows, beta, t60s
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def shoebox_rir_bands(rooms, beta, fs, n, bank, air=None, max_order=-1, max_images=2e8, return_bands=False):
+    """``rooms`` (B, 16), ``beta`` (B, nb, 6) pressure reflection coefficients per band and wall, ``air`` (nb,) or (B, nb) pressure attenuations in
+    Np/m (None: zeros), all float64 arrays or GPU tensors; ``bank`` (nb, Nh) float64 (``octave_bank``) -> (h (B, n) float32 on the GPU, flags (B,)
+    int32 on the CPU[, u (B, nb, n) float64 on the GPU, the band responses]).  The rows' own six coefficients are not read.  h = sum_k bank[k] * u_k
+    applied causally: sample n sits at time (n - Hw - P) / fs, P = (Nh - 1) / 2.  An invalid row is zeros with flag 0.  Refuses above ``max_images``
+    exactly as ``shoebox_rir`` does.  No CPU form."""
+    is_tensor = isinstance(rooms, torch.Tensor)
+    host = _host(rooms)
+    if host.ndim != 2 or host.shape[1] != 16 or host.dtype != np.float64:
+        raise ValueError(f"shoebox_rir_bands takes (B, 16) float64 rooms, got {host.dtype} {tuple(host.shape)}")
+    B = host.shape[0]
+    bh = _host(beta)
+    if bh.ndim != 3 or bh.shape[0] != B or bh.shape[2] != 6 or bh.dtype != np.float64:
+        raise ValueError(f"shoebox_rir_bands takes (B, nb, 6) float64 beta, got {bh.dtype} {tuple(bh.shape)}")
+    nb = bh.shape[1]
+    lib = _lib.load()
+    if not 1 <= nb <= lib.buddy_ism_max_bands():
+        raise ValueError(f"shoebox_rir_bands: nb must be in 1..{lib.buddy_ism_max_bands()}, got {nb}")
+    bk = np.asarray(bank)
+    if bk.ndim != 2 or bk.shape[0] != nb or bk.dtype != np.float64 or bk.shape[1] % 2 == 0 or bk.shape[1] > 65537:
+        raise ValueError(f"shoebox_rir_bands takes a (nb = {nb}, Nh odd, at most 65537) float64 bank, got {bk.dtype} {tuple(bk.shape)}")
+    ah = None
+    if air is not None:
+        ah = _host(air)
+        if ah.dtype != np.float64 or ah.shape not in ((nb,), (B, nb)):
+            raise ValueError(f"shoebox_rir_bands takes (nb,) or (B, nb) float64 air, got {ah.dtype} {tuple(ah.shape)}")
+        ah = np.array(np.broadcast_to(ah, (B, nb)))
+    fs, n, max_order = int(fs), int(n), int(max_order)
+    est = estimated_images(host, fs, n, max_order)
+    for b, v in enumerate(est):
+        if v > float(max_images):
+            raise ValueError(f"shoebox_rir_bands: row {b} would sum about {v:.3g} images, above max_images = {float(max_images):.3g}; "
+                             "shorten the response, cap the order or raise the limit")
+    if is_tensor and not rooms.is_cuda:
+        raise _lib.BuddyHipError("shoebox_rir_bands: the simulator runs on the MI355X only (got a CPU tensor)")
+    lib = _lib.require_gpu()
+    dev = rooms.device if is_tensor else torch.device("cuda")
+    on = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    r = (rooms.detach() if is_tensor else on(host)).contiguous()
+    bt = (beta.detach().to(dev) if isinstance(beta, torch.Tensor) else on(bh)).contiguous()
+    at = None if ah is None else on(ah)
+    kt = on(bk)
+    u = torch.empty(B, nb, n, dtype=torch.float64, device=dev)
+    h = torch.empty(B, n, dtype=torch.float32, device=dev)
+    flags = torch.empty(B, dtype=torch.int32, device=dev)
+    st = _lib.stream_ptr()
+    _lib.check(lib.buddy_shoebox_bands(r.data_ptr(), bt.data_ptr(), None if at is None else at.data_ptr(), B, nb, fs, n, max_order, u.data_ptr(), n,
+                                       flags.data_ptr(), st))
+    _lib.check(lib.buddy_band_combine(u.data_ptr(), B, nb, n, n, kt.data_ptr(), bk.shape[1], _lib.ptr(h), n, st))
+    return (h, flags.cpu(), u) if return_bands else (h, flags.cpu())
+
+
+def band_label(f):
+    return f"{float(f):g}"
+
+
+def _equivalent_beta(dims, beta6):
+    """the uniform coefficient with the area-weighted mean absorption of six unequal walls: sqrt(1 - mean(1 - beta^2))"""
+    lx, ly, lz = (float(v) for v in dims)
+    areas = np.array([ly * lz, ly * lz, lx * lz, lx * lz, lx * ly, lx * ly])
+    return float(math.sqrt(max(0.0, float(np.sum(areas * np.asarray(beta6, dtype=np.float64) ** 2) / np.sum(areas)))))
+
+
+def room_rows(names, rooms, fs, n, acoustics, flags=None, bands=None):
     """one dict per room for ``rooms.csv``: the 16 numbers of the room, the nominal (Eyring) T60, |s - r|, the rate, the response length ``n`` (one
     int, or one per row) and the simulator's flag, then the broadband EDT / T20 / T30 / C50 / DRR that ``rir_acoustics`` (``acoustics``, rows in the
-    order of ``names``) measured on the simulated response, with its validity bits"""
-    rooms = np.asarray(rooms, dtype=np.float64).reshape(-1, 16)
+    order of ``names``) measured on the simulated response, with its validity bits.  ``bands`` = (centres, beta (B, nb, 6)) of banded rooms adds per
+    band ``beta_<f>`` (the coefficient of the walls; for unequal walls the uniform one of the same area-weighted absorption), ``eyring_T60_<f>``, and
+    the ``T20_<f>`` / ``T30_<f>`` / ``acoustics_flags_<f>`` that ``acoustics`` holds for that centre (it must have been analysed at these centres);
+    the row's own six coefficients are then those of the band nearest 1 kHz, so the columns above stay meaningful."""
+    rooms = np.array(rooms, dtype=np.float64).reshape(-1, 16)
     ns = [int(n)] * len(names) if np.isscalar(n) else [int(v) for v in n]
+    if bands is not None:
+        centres, bbeta = tuple(float(f) for f in bands[0]), np.asarray(bands[1], dtype=np.float64)
+        if bbeta.shape != (len(names), len(centres), 6):
+            raise ValueError(f"room_rows: the band block takes beta of shape ({len(names)}, {len(centres)}, 6), got {tuple(bbeta.shape)}")
+        where = [list(acoustics.bands).index(f) if f in acoustics.bands else -1 for f in centres]
+        if min(where) < 0:
+            raise ValueError(f"room_rows: the acoustics were analysed at {tuple(acoustics.bands)}, not at every centre of {centres}")
+        rooms[:, 9:15] = bbeta[:, nearest_band(centres)]
     rows = []
     for b, name in enumerate(names):
         rm = rooms[b]
@@ -155,6 +324,14 @@ def room_rows(names, rooms, fs, n, acoustics, flags=None):
         for q, v in enumerate(MEASURED):
             row[v] = float(acoustics.values[b, 0, q])
         row["acoustics_flags"] = int(acoustics.flags[b, 0])
+        if bands is not None:
+            for k, f in enumerate(centres):
+                bk, tag = bbeta[b, k], band_label(f)
+                row["beta_" + tag] = float(bk[0]) if np.all(bk == bk[0]) else _equivalent_beta(rm[0:3], bk)
+                row["eyring_T60_" + tag] = eyring_t60(rm[0:3], bk, rm[15])
+                row["T20_" + tag] = float(acoustics.values[b, where[k], 1])
+                row["T30_" + tag] = float(acoustics.values[b, where[k], 2])
+                row["acoustics_flags_" + tag] = int(acoustics.flags[b, where[k]])
         rows.append(row)
     return rows
 

@@ -768,6 +768,32 @@ int buddy_ism_tile(void);
 int buddy_ism_list(void);
 int buddy_shoebox_rir(const double* rooms, int B, int fs, int N, int max_order, float* h, long long ldh, int* flags, void* stream);
 
+/* ---- banded rooms: frequency-dependent walls and air absorption (buddy_amd/utils/rooms.py; no reference counterpart).  A banded
+ * room is the row of 16 doubles above, whose own six coefficients are NOT read, plus DEVICE beta (B, nb, 6) doubles, pressure reflection coefficients
+ * per band k and wall (the walls in the order above), and DEVICE air (B, nb) doubles, pressure attenuations in Np/m (NULL: zeros); nb in
+ * 1..buddy_ism_max_bands() = 8.  Images, offsets, d, tau, o, the order cap and the kernel (Hw = 40) are those of buddy_shoebox_rir; per band
+ *   A_k = g_x,k g_y,k g_z,k exp(-air[k] d) / (4 pi d),  g_a,k = beta[k][a0]^|m - q| beta[k][a1]^|m| (0^0 = 1),
+ *   u[b][k][n] = sum A_k sinc(x) (1 + cos(pi x / Hw)) / 2,  x = n - Hw - tau,  |x| < Hw,  n = 0..N - 1,
+ * all in double and stored in double; per band a sample's terms are added in the ascending order of (m_x, q_x, m_y, q_y, q_z, m_z): no atomics, and a
+ * row does not depend on B, on the grid or on the run.  The powers are products (repeated squaring), not pow calls: at most o roundings per axis pair.
+ * A row is invalid -- zeros in u[b][k][0..N - 1] for every k, flags[b] = 0, no other row disturbed -- for everything buddy_shoebox_rir names, tested on
+ * the row without its own six coefficients, a |beta[k][w]| that is not finite or above 1, or an air[k] that is negative or not finite.
+ * BUDDY_ERR_ARG, with nothing launched, for: a null rooms, beta, u or flags; B outside 1..65535; nb outside 1..buddy_ism_max_bands(); fs outside
+ * 1000..1000000; N outside 1..2^20; ldu < N; max_order < -1.  Nothing is written outside u[b][k][0..N - 1] and flags[0..B - 1]; no workspace.  The
+ * work is that of buddy_shoebox_rir plus nb multiply-adds per tap, and again the CALLER bounds it (rooms.shoebox_rir_bands refuses above max_images).
+ *   buddy_band_combine: h[b][n] = sum_k sum_j bank[k][j] u[b][k][n - j], n = 0..N - 1, u zero below sample 0; bank DEVICE (nb, Nh) doubles, Nh odd.
+ * The application is causal: with P = (Nh - 1) / 2 and zero-phase rows centred on tap P, sample n of h sits at time (n - Hw - P) / fs.  Accumulated in
+ * double in the fixed order k ascending, then j ascending, rounded once to fp32.  BUDDY_ERR_ARG, with nothing launched, for: a null u, bank or h; B
+ * outside 1..65535; nb outside 1..buddy_ism_max_bands(); N outside 1..2^20; ldu < N; ldh < N; Nh even or outside 1..65537.  Nothing is written
+ * outside h[b][0..N - 1].  buddy_ism_band_list: images per LDS chunk of a banded tile's list; buddy_band_combine_tile: outputs per workgroup of the
+ * combination (the sizes around which the unit tests place their rooms and lengths). */
+int buddy_ism_max_bands(void);
+int buddy_ism_band_list(void);
+int buddy_band_combine_tile(void);
+int buddy_shoebox_bands(const double* rooms, const double* beta, const double* air /* NULL: none */, int B, int nb, int fs, int N, int max_order,
+                        double* u /* (B, nb, ldu) */, long long ldu, int* flags, void* stream);
+int buddy_band_combine(const double* u, int B, int nb, long long ldu, int N, const double* bank /* (nb, Nh) */, int Nh, float* h, long long ldh, void* stream);
+
 /* ---- the small fp32 kernels of the network, one entry per launcher (unit tests: tests/test_hip_small_ops.py).  All tensors NHWC with H = time, device
  * pointers, fp32.  Each entry returns BUDDY_ERR_ARG with a message, with nothing launched, for a null required pointer, an empty shape, or a shape its
  * kernels cannot compute (named per entry).

@@ -4,6 +4,7 @@ file, its impulse response computed on the GPU by the image-source method.
 
     python tools/make_paired_set.py --clean DIR --out DIR [--seed 0] [--fs 16000] [--t60 LO HI] [--dims X0 X1 Y0 Y1 Z0 Z1]
                                     [--rir-seconds S] [--max-order K] [--num N] [--reverberant]
+                                    [--bands [F0 F1 ...]] [--t60-slope LO HI] [--air A0 A1 ...]
 
 ``--clean`` holds ``<spk>/*.wav`` (a flat folder of wavs is the one speaker ``all``); int or float wavs of any rate, several channels averaged to
 mono; a file at another rate than ``--fs`` goes through the project's resampler.  Written under ``--out``, the layout ``VCTKTestPaired`` and with it
@@ -16,7 +17,13 @@ every paired mode of the tester reads:
                                 RIROperator.degradation; what the real-recordings mode and tools/srmr.py take
 
 A file's room is a function of ``--seed`` and ``<spk>/<id>`` alone, so the same seed and names reproduce every file byte for byte, whatever else is in
-the folder.  The response is 1.5 x the nominal T60 long unless ``--rir-seconds`` fixes it."""
+the folder.  The response is 1.5 x the nominal T60 long unless ``--rir-seconds`` fixes it.
+
+``--bands`` gives every room frequency-dependent walls: the nominal T60 holds at 1 kHz and tilts by a drawn slope per octave
+(``--t60-slope``), each octave band gets the Eyring coefficient of its own T60, ``--air`` adds a pressure attenuation per band in Np/m (no humidity
+model), and the band responses are combined by ``rooms.octave_bank``.  The response then is 1.5 x the longest band's T60 (or ``--rir-seconds``) plus
+the bank's delay of (Nh - 1) / 2 samples, which the loader trims with everything else before the peak; ``rooms.csv`` gains per band ``beta_<f>``,
+``eyring_T60_<f>`` and the measured ``T20_<f>`` / ``T30_<f>`` / ``acoustics_flags_<f>``.  Without ``--bands`` nothing changes."""
 import argparse
 import os
 import sys
@@ -61,8 +68,15 @@ def main(argv=None):
     ap.add_argument("--max-order", type=int, default=-1, help="cap of the reflection order (default: none)")
     ap.add_argument("--num", type=int, default=0, help="take only the first N files")
     ap.add_argument("--reverberant", action="store_true", help="also write reverberant/<spk>/<id>.wav")
+    ap.add_argument("--bands", type=float, nargs="*", default=None, metavar="F",
+                    help="banded rooms: octave centres [Hz] with their own wall coefficients (bare: 125 250 500 1000 2000 4000)")
+    ap.add_argument("--t60-slope", type=float, nargs=2, default=(0.0, 0.3), metavar=("LO", "HI"),
+                    help="with --bands: range of the slope s per octave, T60_k = T60 2^(-s log2(f_k / 1000))")
+    ap.add_argument("--air", type=float, nargs="+", default=None, metavar="A", help="with --bands: pressure attenuation of the air per band [Np/m] (default: zeros)")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
+    if a.bands is None and a.air is not None:
+        raise SystemExit("make_paired_set: --air needs --bands")
     files = list_clean(a.clean)
     if a.num > 0:
         files = files[:a.num]
@@ -70,22 +84,37 @@ def main(argv=None):
         raise SystemExit(f"make_paired_set: no wav under {a.clean}")
     names = [f"{spk}/{uid}" for spk, uid, _ in files]
     dims = tuple((a.dims[2 * k], a.dims[2 * k + 1]) for k in range(3))
-    drawn = rooms.draw_rooms(names, a.seed, t60=tuple(a.t60), dims=dims)
+    if a.bands is None:
+        drawn = rooms.draw_rooms(names, a.seed, t60=tuple(a.t60), dims=dims)
+    else:
+        centres = tuple(a.bands) if a.bands else tuple(float(f) for f in rooms.BAND_CENTRES)
+        bank = rooms.octave_bank(a.fs, centres)
+        delay = (bank.shape[1] - 1) // 2
+        air = np.zeros(len(centres)) if a.air is None else np.array(a.air, dtype=np.float64)
+        if air.shape != (len(centres),):
+            raise SystemExit(f"make_paired_set: --air takes one value per band ({len(centres)}), got {len(air)}")
+        drawn, band_beta, band_t60 = rooms.draw_band_rooms(names, a.seed, centres, t60=tuple(a.t60), slope=tuple(a.t60_slope), dims=dims)
     if a.reverberant:
         from buddy_amd.config import compose
         from buddy_amd.testing.operators.reverb import RIROperator
         op_hp = compose().tester.informed_dereverberation.op_hp
     rows = []
-    for (spk, uid, path), name, rm in zip(files, names, drawn):
+    for u, ((spk, uid, path), name, rm) in enumerate(zip(files, names, drawn)):
         x, fs_in = read_wav(path)
         xt = torch.from_numpy(x).to(a.device)
         if fs_in != a.fs:
             xt = resample.resample(xt, fs_in, a.fs)
         nominal = rooms.eyring_t60(rm[0:3], rm[9:15], rm[15])
-        n = int(round((a.rir_seconds if a.rir_seconds is not None else 1.5 * nominal) * a.fs))
-        h, flags = rooms.shoebox_rir(torch.from_numpy(rm[None]).to(a.device), a.fs, n, max_order=a.max_order)
-        ac = acoustics.rir_acoustics(h, a.fs)
-        rows += rooms.room_rows([name], rm[None], a.fs, n, ac, flags)
+        if a.bands is None:
+            n = int(round((a.rir_seconds if a.rir_seconds is not None else 1.5 * nominal) * a.fs))
+            h, flags = rooms.shoebox_rir(torch.from_numpy(rm[None]).to(a.device), a.fs, n, max_order=a.max_order)
+            ac = acoustics.rir_acoustics(h, a.fs)
+            rows += rooms.room_rows([name], rm[None], a.fs, n, ac, flags)
+        else:           # the longest band decides the length, and the bank's delay comes on top of it
+            n = int(round((a.rir_seconds if a.rir_seconds is not None else 1.5 * float(band_t60[u].max())) * a.fs)) + delay
+            h, flags = rooms.shoebox_rir_bands(torch.from_numpy(rm[None]).to(a.device), band_beta[u:u + 1], a.fs, n, bank, air=air, max_order=a.max_order)
+            ac = acoustics.rir_acoustics(h, a.fs, centres=centres)
+            rows += rooms.room_rows([name], rm[None], a.fs, n, ac, flags, bands=(centres, band_beta[u:u + 1]))
         for sub, v in (("clean", xt), ("rir", h[0])):
             os.makedirs(os.path.join(a.out, sub, spk), exist_ok=True)
             wavfile.write(os.path.join(a.out, sub, spk, uid + ".wav"), a.fs, v.cpu().numpy().astype(np.float32))
