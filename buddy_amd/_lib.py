@@ -96,6 +96,15 @@ _SIGS = {
                                             C.c_longlong, C.c_void_p, C.c_void_p]),
     "buddy_srmr_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "buddy_level_tile": (C.c_int, []),
+    "buddy_level_counts_tile": (C.c_int, []),
+    "buddy_level_stats_workspace": (C.c_longlong, [C.c_int, C.c_longlong]),
+    "buddy_level_classes_workspace": (C.c_longlong, [C.c_int, C.c_longlong]),
+    "buddy_level_counts_workspace": (C.c_longlong, [C.c_int, C.c_longlong]),
+    "buddy_level_stats": (C.c_int, [_f32p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "buddy_level_classes": (C.c_int, [_f32p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_longlong,
+                                      C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "buddy_level_counts": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]),
     "buddy_frame_spectra": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_int, _f32p, C.c_longlong, C.c_void_p]),
     "buddy_cepstral_distance_workspace": (C.c_longlong, [C.c_int, C.c_int]),
     "buddy_cepstral_distance": (C.c_int, [_f32p, _f32p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

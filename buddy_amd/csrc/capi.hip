@@ -3,6 +3,7 @@
 #include "common.h"
 #include "net.h"
 
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -912,6 +913,68 @@ int buddy_srmr_scores(const double* E, const int* frames, int B, int J, int K, l
   int longest;
   if (int rc = check_rows(frames, B, ldm, 0, stream, "buddy_srmr_scores", &longest)) return rc;
   launch_srmr_scores(E, frames, B, J, ldm, erb, l, out, Ebar, flags, (hipStream_t)stream);
+  return finish();
+}
+
+// ---- active speech level of single signals (level.hip) ----
+int buddy_level_tile(void) { return level_tile(); }
+int buddy_level_counts_tile(void) { return level_counts_tile(); }
+static bool level_shape_ok(int B, long long max_len) { return B >= 1 && B <= 65535 && max_len >= 0 && max_len <= (1LL << 30); }
+long long buddy_level_stats_workspace(int B, long long max_len) { return level_shape_ok(B, max_len) ? level_stats_ws_bytes(B, max_len) : -1; }
+long long buddy_level_classes_workspace(int B, long long max_len) { return level_shape_ok(B, max_len) ? level_classes_ws_bytes(B, max_len) : -1; }
+long long buddy_level_counts_workspace(int B, long long max_len) { return level_shape_ok(B, max_len) ? level_counts_ws_bytes(B, max_len) : -1; }
+
+int buddy_level_stats(const float* x, long long ldx, const int* lengths, int B, double* out, void* ws, long long ws_bytes, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_level_stats: ") + why); return BUDDY_ERR_ARG; };
+  if (!x || !lengths || !out || !ws) return bad("null pointer");
+  int longest;
+  if (int rc = check_rows(lengths, B, ldx, 0, stream, "buddy_level_stats", &longest)) return rc;
+  if (ws_bytes < level_stats_ws_bytes(B, longest)) return bad("the workspace is smaller than buddy_level_stats_workspace(B, longest row)");
+  launch_level_stats(x, ldx, lengths, B, longest, out, ws, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_level_classes(const float* x, long long ldx, const int* lengths, const double* offset, const double* ref, int B, double fs, double tc,
+                        unsigned char* klass, long long ldk, double* sq, void* ws, long long ws_bytes, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_level_classes: ") + why); return BUDDY_ERR_ARG; };
+  if (!x || !lengths || !ref || !klass || !sq || !ws) return bad("null pointer");
+  if (!(fs > 0.0) || !std::isfinite(fs)) return bad("fs must be finite and > 0");
+  if (!(tc > 0.0) || !std::isfinite(tc)) return bad("tc must be finite and > 0");
+  int longest;
+  if (int rc = check_rows(lengths, B, ldx, 0, stream, "buddy_level_classes", &longest)) return rc;
+  if (ldk < 1 || ldk < longest) return bad("ldk is smaller than the longest row");
+  if (ws_bytes < level_classes_ws_bytes(B, longest)) return bad("the workspace is smaller than buddy_level_classes_workspace(B, longest row)");
+  std::vector<double> rh((size_t)B * 2, 0.0);  // ref, then offset: device doubles, read like the lengths
+  int ndev = 0;
+  const bool on_host = hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1;
+  if (on_host) {
+    (void)hipGetLastError();
+    std::memcpy(rh.data(), ref, sizeof(double) * (size_t)B);
+    if (offset) std::memcpy(rh.data() + B, offset, sizeof(double) * (size_t)B);
+  } else {
+    hipError_t e = hipMemcpyAsync(rh.data(), ref, sizeof(double) * (size_t)B, hipMemcpyDefault, (hipStream_t)stream);
+    if (e == hipSuccess && offset) e = hipMemcpyAsync(rh.data() + B, offset, sizeof(double) * (size_t)B, hipMemcpyDefault, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e != hipSuccess) { set_error(std::string("buddy_level_classes: reading ref / offset: ") + hipGetErrorString(e)); return BUDDY_ERR_HIP; }
+  }
+  for (int b = 0; b < B; ++b) {
+    if (!(rh[b] > 0.0) || !std::isfinite(rh[b])) return bad("every ref[b] must be finite and > 0");
+    if (!std::isfinite(rh[B + b])) return bad("every offset[b] must be finite");
+  }
+  const double g = std::exp(-1.0 / (fs * tc));
+  launch_level_classes(x, ldx, lengths, offset, ref, B, longest, g, klass, ldk, sq, ws, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_level_counts(const unsigned char* klass, long long ldk, const int* lengths, int B, int I, long long* counts, void* ws, long long ws_bytes,
+                       void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_level_counts: ") + why); return BUDDY_ERR_ARG; };
+  if (!klass || !lengths || !counts || !ws) return bad("null pointer");
+  if (I < 0) return bad("I must be >= 0");
+  int longest;
+  if (int rc = check_rows(lengths, B, ldk, 0, stream, "buddy_level_counts", &longest)) return rc;
+  if (ws_bytes < level_counts_ws_bytes(B, longest)) return bad("the workspace is smaller than buddy_level_counts_workspace(B, longest row)");
+  launch_level_counts(klass, ldk, lengths, B, longest, I, counts, ws, (hipStream_t)stream);
   return finish();
 }
 

@@ -219,6 +219,17 @@ void launch_modulation_energies(const float* env, const int* lens, int B, int J,
                                 int* frames, hipStream_t st);
 void launch_srmr_scores(const double* E, const int* frames, int B, int J, long long ldm, const double* erb, const double* l, double* out, double* Ebar, int* flags,
                         hipStream_t st);
+// active speech level of single signals (level.hip): ragged rows, device length arrays; arguments, lengths, strides and
+// workspaces are checked by the C entries, which pass the longest row (max_len) for the grids.  offset (or null), ref: device doubles per row
+int level_tile();                            // samples per workgroup of the envelope kernels
+int level_counts_tile();                     // samples per workgroup of the hangover kernels
+long long level_stats_ws_bytes(int B, long long max_len);
+long long level_classes_ws_bytes(int B, long long max_len);
+long long level_counts_ws_bytes(int B, long long max_len);
+void launch_level_stats(const float* x, long long ldx, const int* lens, int B, int max_len, double* out, void* ws, hipStream_t st);
+void launch_level_classes(const float* x, long long ldx, const int* lens, const double* offset, const double* ref, int B, int max_len, double g,
+                          unsigned char* klass, long long ldk, double* sq, void* ws, hipStream_t st);
+void launch_level_counts(const unsigned char* klass, long long ldk, const int* lens, int B, int max_len, int hang, long long* counts, void* ws, hipStream_t st);
 // spectral-envelope distortion of (estimate, clean) pairs (spectral.hip): ragged rows, device length and frame-count arrays; arguments, lengths,
 // strides and workspaces are checked by the C entries, which pass the largest frame count (max_frames) for the grids.  Spectra are (B, ldf, 257) fp32
 int spectral_bins();                         // 257

@@ -422,7 +422,8 @@ class Tester:
     # ---- real recordings: any rate, any length, no clean signal or true RIR (no reference counterpart) -----------------------------------------
     def test_real_recordings(self, mode):
         """Every file of an ``AudioFolder`` -> its dereverberated version.  Per file, on the GPU: resample to the model's rate, scale to
-        ``gain * scaling_factor / std``; files of at least one chunk are cut into equal overlapping chunks (testing/longform.py) and the chunks of
+        ``gain * scaling_factor / std`` (``real_recordings.level: active``: by the active speech level instead, ``utils/level.py``, with one line per
+        file in ``levels.csv``); files of at least one chunk are cut into equal overlapping chunks (testing/longform.py) and the chunks of
         ALL files are sampled as one pool of independent utterances in batches of ``batch_size``; then level match, cross-fade, undo the scaling,
         resample back.  Files go to ranks by index; every rank writes its own, nothing is gathered.  ``real_recordings.shared_rir``: the chunks
         of a file are tied rows of one operator -- one RIR estimate per file, fitted to all its chunks; a batch then never splits a file
@@ -435,6 +436,8 @@ class Tester:
         rr = self.args.tester.real_recordings
         ps = self.args.tester.posterior_sampling
         sr = int(self.args.exp.sample_rate)
+        from ..utils import level as lv
+        level_rule, ref_activity = lv.level_options(rr)      # level=active without a reference activity stops here, before anything is sampled
         chunk = int(self.args.exp.audio_len) if rr.get("chunk_seconds", None) is None else int(round(float(rr.chunk_seconds) * sr))
         overlap = int(round(float(rr.get("overlap_seconds", 0.5)) * sr))
         out_rate = str(rr.get("output_rate", "input"))
@@ -444,6 +447,7 @@ class Tester:
         level = bool(csm is not None and csm.get("use", False))      # the condition of dereverberate_long
         self.skipped = []
         files = []
+        levels = []    # level=active: one line of levels.csv per file
         for i in range(self.rank, len(self.test_set), self.world_size):
             audio, fs, filename = self.test_set[i]
             y = resample(torch.from_numpy(np.asarray(audio)).float().to(self.device), fs, sr)
@@ -453,6 +457,15 @@ class Tester:
                 self.skipped.append(filename)
                 continue
             g = float(rr.get("gain", 1.0)) * float(ps.warm_initialization.scaling_factor) / std
+            if level_rule == "active":      # scale by the level while speech is active (utils/level.py), not by a std that falls with every pause
+                m = lv.speech_level(y[None], sr)
+                rule = "active"
+                if int(m.flags[0]) != 0:
+                    rule = "std"
+                    print(f"{filename}: the active level is flagged {lv.flag_text(m.flags[0])}: scaled by its std instead")
+                else:
+                    g = lv.active_gain(rr.get("gain", 1.0), ps.warm_initialization.scaling_factor, float(m.active_rms[0]), ref_activity)
+                levels += lv.report_rows([os.path.basename(filename)[:-4]], m, [{"rule": rule, "g": g}])
             files.append(dict(name=os.path.basename(filename)[:-4], fs=int(fs), n_in=len(audio), y=g * y, g=g))
         shared, max_rows = shared_rir_options(rr)
         lengths = [f["y"].numel() for f in files]
@@ -468,6 +481,9 @@ class Tester:
             f["parts"] = torch.stack([f["y"][s:s + clen] for s in starts])
             f["est"], f["rir"], f["par"] = [None] * len(starts), [None] * len(starts), [None] * len(starts)
         writing = not self.in_training and bool(self.paths)
+        self.levels = levels if level_rule == "active" else None
+        if writing and level_rule == "active":
+            lv.write_report(os.path.join(self.paths[mode], "levels.csv" if self.world_size == 1 else f"levels.rank{self.rank}.csv"), levels)
         report = writing and rir_report_options(self.args.tester)[0]
         srmr_on = writing and srmr_options(self.args.tester)
         heard = []     # SRMR report: (name, degraded at the model's rate, reconstructed at its own rate, no clean signal) per written file

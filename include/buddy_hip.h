@@ -710,6 +710,37 @@ int buddy_modulation_energies(const float* env, const int* lens, int B, int J, l
 int buddy_srmr_scores(const double* E, const int* frames, int B, int J, int K, long long ldm, const double* erb /*host*/, const double* l /*host*/, double* out,
                       double* Ebar, int* flags, void* stream);
 
+/* ---- active speech level of single signals (buddy_amd/utils/level.py; ITU-T P.56 method B as restated there; no reference
+ * counterpart).  The conventions of the evaluation entries above hold: ragged rows inside a common stride, DEVICE length arrays copied to the host once
+ * to be checked, nothing at or behind lengths[b] read or written, fixed-order sums without atomics, a row's result independent of B, of the grid and of
+ * the run.  A length may be 0 (the row then gives sq = 0 and zero counts).
+ * BUDDY_ERR_ARG, with nothing launched, for: a null pointer (offset may be NULL: zeros); B outside 1..65535; a length outside 0..2^30; a stride smaller
+ * than the longest row (or below 1); fs or tc not finite and above zero; I < 0; a ref[b] that is not finite and positive or an offset[b] that is not
+ * finite; a workspace below the size its query states (the queries give -1 for B outside 1..65535 or max_len outside 0..2^30).
+ *
+ * buddy_level_stats: out (B, 2) doubles = (sum of x[b][i], max |x[b][i]|), i < lengths[b]; the sum in double in a fixed order (a NaN sample gives a NaN
+ *   sum; the maximum skips it).
+ *
+ * buddy_level_classes: offset, ref: DEVICE doubles (B), copied to the host once to be checked.  With o = offset[b], R = ref[b], g = exp(-1 / (fs tc))
+ *   (formed once, on the host), v_i = |x_i - o| in double: p_i = g p_(i-1) + (1 - g) v_i, q_i = g q_(i-1) + (1 - g) p_i from p = q = 0, all in double;
+ *   klass[b][i] = #{j in 0..15 : q_i >= R 2^(j - 15)} for i < lengths[b]; sq[b] = sum_i (x_i - o)^2 in double in a fixed order.  The recurrence runs
+ *   as a scan over tiles of buddy_level_tile() samples; q differs from the sequential evaluation by no more than the bound of section 23.  A sample
+ *   that is not finite makes sq[b] not finite and the row's classes meaningless, and disturbs no other row.
+ *
+ * buddy_level_counts: counts (B, 16) int64, counts[b][j] = #{i < lengths[b] : some i' in [max(0, i - I), i] has klass[b][i'] >= j + 1}: the P.56
+ *   hangover of I samples.  Integer arithmetic throughout; any I >= 0.  buddy_level_counts_tile(): samples per workgroup.
+ * buddy_level_tile / buddy_level_counts_tile: the sizes around which the unit tests place their rows. */
+int buddy_level_tile(void);
+int buddy_level_counts_tile(void);
+long long buddy_level_stats_workspace(int B, long long max_len);
+long long buddy_level_classes_workspace(int B, long long max_len);
+long long buddy_level_counts_workspace(int B, long long max_len);
+int buddy_level_stats(const float* x, long long ldx, const int* lengths, int B, double* out, void* ws, long long ws_bytes, void* stream);
+int buddy_level_classes(const float* x, long long ldx, const int* lengths, const double* offset /* NULL: zeros */, const double* ref, int B, double fs, double tc,
+                        unsigned char* klass, long long ldk, double* sq, void* ws, long long ws_bytes, void* stream);
+int buddy_level_counts(const unsigned char* klass, long long ldk, const int* lengths, int B, int I, long long* counts /* (B, 16) */, void* ws, long long ws_bytes,
+                       void* stream);
+
 /* ---- spectral-envelope distortion of a paired run (buddy_amd/utils/spectral.py; no reference counterpart): cepstral distance,
  * log-likelihood ratio and frequency-weighted segmental SNR of pairs (estimate e, clean reference x).  The conventions of the evaluation entries above
  * hold: ragged rows inside a common stride, DEVICE length and frame-count arrays copied to the host once to be checked, nothing behind a row's end read,
