@@ -8,6 +8,7 @@
 // Rows are ragged inside a common stride; the lengths are device arrays (arguments, lengths and strides are checked by the C entries, which
 // fetch the lengths once).  All of it runs once per tester mode, after sampling: latency-bound, written for clarity.
 #include "common.h"
+#include "reduce.h"                           // block_sum
 
 namespace buddy {
 namespace {
@@ -80,22 +81,6 @@ __global__ __launch_bounds__(AC_NT) void fir_bank_kernel(const float* __restrict
 }
 
 // ---- decay analysis -----------------------------------------------------------------------------------------------------------------
-template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double (*lds)[K], int tid) {      // the sums land in thread 0
-#pragma unroll
-  for (int q = 0; q < K; ++q)
-    for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_down(v[q], off);
-  if ((tid & 63) == 0)
-#pragma unroll
-    for (int q = 0; q < K; ++q) lds[tid >> 6][q] = v[q];
-  __syncthreads();
-  if (tid == 0)
-    for (int w = 1; w < AC_NW; ++w)
-#pragma unroll
-      for (int q = 0; q < K; ++q) v[q] += lds[w][q];
-  __syncthreads();
-}
-
 struct DecayRange { double lo, hi; };        // dB, lo <= D <= hi
 
 __global__ __launch_bounds__(AC_NT) void decay_metrics_kernel(const float* __restrict__ g, const int* __restrict__ lens_g, const int* __restrict__ n0s, int nb,

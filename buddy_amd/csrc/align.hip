@@ -19,6 +19,7 @@
 // for 64 fused multiply-adds.  Lanes read e~ at a stride of 8 doubles, which would put a 32-lane group on 4 banks of 64; the e~ array therefore keeps
 // one unused double behind every 8 (index i lives at i + i / 8): the stride becomes 18 dwords and the 32 lanes of a group cover all 64 banks once.
 #include "common.h"
+#include "reduce.h"                           // block_sum
 
 namespace buddy {
 namespace {
@@ -32,24 +33,6 @@ constexpr int AL_NE = AL_T + AL_LT;           // e~ values a workgroup stages
 constexpr int AL_STATS = 5;                   // doubles per row: mean e, mean x, ||e~||^2, ||x~||^2, defined (1 or 0)
 
 __device__ __forceinline__ int pad8(int i) { return i + (i >> 3); }
-
-template <int Q>
-__device__ __forceinline__ void block_sum(double (&v)[Q], double (*lds)[Q], int tid) {      // the sums land in every thread
-#pragma unroll
-  for (int q = 0; q < Q; ++q)
-    for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_down(v[q], off);
-  __syncthreads();                            // the previous use of lds has been read
-  if ((tid & 63) == 0)
-#pragma unroll
-    for (int q = 0; q < Q; ++q) lds[tid >> 6][q] = v[q];
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < Q; ++q) {
-    double s = lds[0][q];
-    for (int w = 1; w < AL_NW; ++w) s += lds[w][q];
-    v[q] = s;
-  }
-}
 
 __global__ __launch_bounds__(AL_NT) void xcorr_stats_kernel(const float* __restrict__ e, const float* __restrict__ x, const int* __restrict__ lens, long long ld,
                                                             double* __restrict__ stats) {

@@ -7,7 +7,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-gpu-rdc -Wno-unused-resul
 mkdir -p obj
 pids=()
 for f in options igemm wgemm wgemm16 wprep wino wino4 wino6 ops attn attn16 sampler net operator wpe resample acoustics metrics align srmr level spectral ism wgrad optim rng capi; do
-  if [ ! -f obj/$f.o ] || [ $f.hip -nt obj/$f.o ] || [ common.h -nt obj/$f.o ] || [ wgemm_tile.h -nt obj/$f.o ] || [ net.h -nt obj/$f.o ] || [ fft512.h -nt obj/$f.o ] || [ ../../include/buddy_hip.h -nt obj/$f.o ]; then
+  if [ ! -f obj/$f.o ] || [ $f.hip -nt obj/$f.o ] || [ common.h -nt obj/$f.o ] || [ wgemm_tile.h -nt obj/$f.o ] || [ net.h -nt obj/$f.o ] || [ fft512.h -nt obj/$f.o ] || [ reduce.h -nt obj/$f.o ] || [ ../../include/buddy_hip.h -nt obj/$f.o ]; then
     hipcc $FLAGS -c $f.hip -o obj/$f.o &
     pids+=($!)
   fi

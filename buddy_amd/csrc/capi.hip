@@ -2,6 +2,7 @@
 #include "../../include/buddy_hip.h"
 #include "common.h"
 #include "net.h"
+#include "reduce.h"                           // frames_of
 
 #include <cmath>
 #include <cstring>
@@ -979,8 +980,6 @@ int buddy_level_counts(const unsigned char* klass, long long ldk, const int* len
 }
 
 // ---- spectral-envelope distortion of (estimate, clean) pairs (spectral.hip) ----
-static long long frames_at(long long len, int frame, int hop) { return len >= frame ? (len - frame) / hop + 1 : 0; }
-
 int buddy_frame_spectra(const float* x, const int* lens, int B, long long ld, int frame, int hop, float* S, long long ldf, void* stream) {
   auto bad = [](const char* why) { set_error(std::string("buddy_frame_spectra: ") + why); return BUDDY_ERR_ARG; };
   if (!x || !lens || !S) return bad("null pointer");
@@ -988,7 +987,7 @@ int buddy_frame_spectra(const float* x, const int* lens, int B, long long ld, in
   if (hop < 1) return bad("hop must be >= 1");
   int longest;
   if (int rc = check_rows(lens, B, ld, 1, stream, "buddy_frame_spectra", &longest)) return rc;
-  const long long maxF = frames_at(longest, frame, hop);
+  const long long maxF = frames_of(longest, frame, hop);
   if (ldf < at_least_one(maxF)) return bad("ldf is smaller than the frames of the longest row");
   launch_frame_spectra(x, lens, B, ld, maxF, frame, hop, S, ldf, (hipStream_t)stream);
   return finish();
@@ -1029,7 +1028,7 @@ int buddy_fwsegsnr(const float* X, const float* E, const int* frames, int B, lon
 
 long long buddy_llr_workspace(int B, long long max_len, int frame, int hop) {
   if (B < 1 || max_len < 1 || max_len > (1LL << 30) || frame < 1 || frame > 512 || hop < 1) return -1;
-  return 16LL * B * at_least_one(frames_at(max_len, frame, hop));
+  return 16LL * B * at_least_one(frames_of(max_len, frame, hop));
 }
 
 int buddy_llr(const float* e, const float* x, const int* lens, int B, long long ld, int frame, int hop, int order, double* out, int* counts, int* flags, void* ws,
@@ -1042,7 +1041,7 @@ int buddy_llr(const float* e, const float* x, const int* lens, int B, long long 
   int longest;
   if (int rc = check_rows(lens, B, ld, 1, stream, "buddy_llr", &longest)) return rc;
   if (ws_bytes < buddy_llr_workspace(B, longest, frame, hop)) return bad("the workspace is smaller than buddy_llr_workspace(B, longest row, frame, hop)");
-  launch_llr(e, x, lens, B, ld, frames_at(longest, frame, hop), frame, hop, order, out, counts, flags, (double*)ws, (hipStream_t)stream);
+  launch_llr(e, x, lens, B, ld, frames_of(longest, frame, hop), frame, hop, order, out, counts, flags, (double*)ws, (hipStream_t)stream);
   return finish();
 }
 

@@ -16,9 +16,10 @@
 // and per-segment values go through a workspace and are summed by one workgroup per row): no atomics, and a row's result does not depend on
 // its batch.  All of it runs once per tester mode, after sampling: latency-bound, written for clarity.
 //
-// The frame FFT (frame_fft) lives in fft512.h, shared with spectral.hip.
+// The frame FFT (frame_fft) lives in fft512.h, the sums (wave_sum, block_sum) and the frame and tile counts in reduce.h; spectral.hip uses both too.
 #include "common.h"
 #include "fft512.h"
+#include "reduce.h"
 
 namespace buddy {
 namespace {
@@ -30,31 +31,8 @@ constexpr int FR = 256, HOP = 128, NFFT = FFT_N, NBIN = NFFT / 2 + 1, SEG = 30;
 constexpr double ST_EPS = 2.220446049250313e-16;          // 2^-52
 constexpr int MAXJ = 32;
 
-__device__ __forceinline__ int frames_of(int len) { return len >= FR ? (len - FR) / HOP + 1 : 0; }
+__device__ __forceinline__ int frames_of(int len) { return buddy::frames_of(len, FR, HOP); }
 __device__ __forceinline__ double window_d(int i) { return fft_window_d(i, FR); }            // interior of a 258-point Hann window
-
-template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double (*lds)[K], int tid) {      // the sums land in every thread
-#pragma unroll
-  for (int q = 0; q < K; ++q)
-    for (int off = 32; off > 0; off >>= 1) v[q] += __shfl_down(v[q], off);
-  __syncthreads();                            // the previous use of lds has been read
-  if ((tid & 63) == 0)
-#pragma unroll
-    for (int q = 0; q < K; ++q) lds[tid >> 6][q] = v[q];
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < K; ++q) {
-    double s = lds[0][q];
-    for (int w = 1; w < MT_NW; ++w) s += lds[w][q];
-    v[q] = s;
-  }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {       // the sum lands in every lane: butterfly, the same order in every lane
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
 
 // ---- SI-SDR ------------------------------------------------------------------------------------------------------------------------------
 // three passes over the row: means; zero-mean moments; with a = <e,x> / max(||x||^2, 1e-30) the target and residual energies, element by element
@@ -360,11 +338,10 @@ __global__ __launch_bounds__(MT_NT) void lsd_finalize_kernel(const double* __res
   flags[b] = ok ? 1 : 0;
 }
 
-inline unsigned tiles_of(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 }  // namespace
 
 int metrics_tile() { return MT_TILE; }
-long long metrics_frames(long long len) { return len >= FR ? (len - FR) / HOP + 1 : 0; }
+long long metrics_frames(long long len) { return frames_of(len, FR, HOP); }
 
 void launch_pair_moments(const float* e, const float* x, const int* lens, int B, long long ld, double* out, int* flags, hipStream_t st) {
   hipLaunchKernelGGL(pair_moments_kernel, dim3((unsigned)B), dim3(MT_NT), 0, st, e, x, lens, ld, out, flags);

@@ -13,8 +13,11 @@
 // nothing outside the declared extents is written.  Every reduction runs in a fixed order (strided partial sums, wave shuffles, one LDS exchange;
 // per-frame values go through a workspace and are summed by one workgroup per row): no atomics, and a row's result does not depend on its batch.
 // All of it runs once per tester mode, after sampling: latency-bound, written for clarity.
+//
+// The frame FFT lives in fft512.h, the sums (wave_sum, block_sum) and the frame and tile counts (frames_of, tiles_of) in reduce.h.
 #include "common.h"
 #include "fft512.h"
+#include "reduce.h"
 
 namespace buddy {
 namespace {
@@ -24,30 +27,6 @@ constexpr int NBIN = FFT_N / 2 + 1;           // 257
 constexpr int NCEP = 25;                      // cepstral coefficients 0..24
 constexpr int MAXORD = 16;
 constexpr double DB_PER_NEPER = 4.342944819032518;           // 10 / ln 10
-
-__device__ __forceinline__ int frames_of(int len, int frame, int hop) { return len >= frame ? (len - frame) / hop + 1 : 0; }
-
-__device__ __forceinline__ double wave_sum(double v) {       // the sum lands in every lane: butterfly, the same order in every lane
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-
-template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double (*lds)[K], int tid) {      // the sums land in every thread
-#pragma unroll
-  for (int q = 0; q < K; ++q) v[q] = wave_sum(v[q]);
-  __syncthreads();                            // the previous use of lds has been read
-  if ((tid & 63) == 0)
-#pragma unroll
-    for (int q = 0; q < K; ++q) lds[tid >> 6][q] = v[q];
-  __syncthreads();
-#pragma unroll
-  for (int q = 0; q < K; ++q) {
-    double s = lds[0][q];
-    for (int w = 1; w < SP_NW; ++w) s += lds[w][q];
-    v[q] = s;
-  }
-}
 
 // ---- magnitude spectra -------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(SP_NT) void frame_spectra_kernel(const float* __restrict__ x, const int* __restrict__ lens, long long ld, int frame, int hop,
@@ -270,7 +249,6 @@ __global__ __launch_bounds__(SP_NT) void mean_rows_kernel(const double* __restri
   flags[b] = ok ? 1 : 0;
 }
 
-inline unsigned tiles_of(long long n, int per) { return (unsigned)((n + per - 1) / per); }
 }  // namespace
 
 int spectral_bins() { return NBIN; }

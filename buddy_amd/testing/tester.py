@@ -43,14 +43,19 @@ def rir_report_options(tester_cfg):
     return bool(rp.get("use", False)), OCTAVES if c is None else tuple(float(v) for v in c)
 
 
+def _values_options(tester_cfg, block, all_values):
+    """(use, values) of the report block ``block`` of a tester config; a config written before the block existed means (False, ``all_values``)"""
+    bl = tester_cfg.get(block, None)
+    if bl is None:
+        return False, all_values
+    v = bl.get("values", None)
+    return bool(bl.get("use", False)), all_values if v is None else tuple(str(s) for s in v)
+
+
 def metrics_options(tester_cfg):
     """(use, values) of the ``metrics`` block of a tester config; a config written before the block existed means (False, all four values)"""
     from ..utils.metrics import VALUES
-    mt = tester_cfg.get("metrics", None)
-    if mt is None:
-        return False, VALUES
-    v = mt.get("values", None)
-    return bool(mt.get("use", False)), VALUES if v is None else tuple(str(s) for s in v)
+    return _values_options(tester_cfg, "metrics", VALUES)
 
 
 def align_options(tester_cfg):
@@ -74,11 +79,7 @@ def srmr_options(tester_cfg):
 def spectral_options(tester_cfg):
     """(use, values) of the ``spectral`` block of a tester config; a config written before the block existed means (False, all three values)"""
     from ..utils.spectral import VALUES
-    sp = tester_cfg.get("spectral", None)
-    if sp is None:
-        return False, VALUES
-    v = sp.get("values", None)
-    return bool(sp.get("use", False)), VALUES if v is None else tuple(str(s) for s in v)
+    return _values_options(tester_cfg, "spectral", VALUES)
 
 
 class Tester:
@@ -297,10 +298,14 @@ class Tester:
         correlations and flags are further columns.  Every rank writes its own rows (``metrics.rank<r>.csv`` when there are
         several); nothing is gathered -- ``tools/evaluate.py`` scores the directory of a multi-rank run as a whole."""
         from ..utils import metrics
-        self.metrics_report = None
+        self.metrics_report = self._write_pair_report(mode, scored, sr, metrics, "metrics", metrics_options(self.args.tester)[1])
+
+    def _write_pair_report(self, mode, scored, sr, module, stem, values):
+        """the body of the two paired reports: ``module`` (utils/metrics.py or utils/spectral.py) scores the degraded and the reconstructed rows of
+        ``scored`` against the clean ones, equal lengths as one batch, after ``tester.metrics.align`` where it is in use, and writes ``<stem>.csv`` and
+        ``<stem>_summary.csv`` into the mode's directory -> the rows, or None where nothing was scored"""
         if not scored:
-            return
-        values = metrics_options(self.args.tester)[1]
+            return None
         use_align, max_lag_ms = align_options(self.args.tester)
         window = max_lag_ms if use_align else None
         groups = {}
@@ -309,14 +314,14 @@ class Tester:
         rows = [None] * len(scored)
         for idx in groups.values():
             clean, deg, rec = (torch.stack([scored[i][k].flatten().float() for i in idx]).to(self.device) for k in (1, 2, 3))
-            inp = metrics.evaluate(deg, clean, int(sr), values=values, align=window)
-            out = metrics.evaluate(rec, clean, int(sr), values=values, align=window)
-            for i, row in zip(idx, metrics.report_rows([scored[i][0] for i in idx], inp, out)):
+            inp = module.evaluate(deg, clean, int(sr), values=values, align=window)
+            out = module.evaluate(rec, clean, int(sr), values=values, align=window)
+            for i, row in zip(idx, module.report_rows([scored[i][0] for i in idx], inp, out)):
                 rows[i] = row
         tag = f".rank{self.rank}" if self.world_size > 1 else ""
-        metrics.write_report(os.path.join(self.paths[mode], f"metrics{tag}.csv"), rows)
-        metrics.write_report(os.path.join(self.paths[mode], f"metrics_summary{tag}.csv"), metrics.summary_rows(rows))
-        self.metrics_report = rows
+        module.write_report(os.path.join(self.paths[mode], f"{stem}{tag}.csv"), rows)
+        module.write_report(os.path.join(self.paths[mode], f"{stem}_summary{tag}.csv"), module.summary_rows(rows))
+        return rows
 
     def _write_spectral_report(self, mode, scored, sr):
         """Spectral distortion report of a paired mode (``tester.spectral.use``; utils/spectral.py), once per mode after sampling:
@@ -326,26 +331,7 @@ class Tester:
         writes its own rows (``spectral.rank<r>.csv`` when there are several); nothing is gathered -- ``tools/spectral.py`` scores the directory of a
         multi-rank run as a whole."""
         from ..utils import spectral
-        self.spectral_report = None
-        if not scored:
-            return
-        values = spectral_options(self.args.tester)[1]
-        use_align, max_lag_ms = align_options(self.args.tester)
-        window = max_lag_ms if use_align else None
-        groups = {}
-        for i, r in enumerate(scored):
-            groups.setdefault(int(r[1].numel()), []).append(i)
-        rows = [None] * len(scored)
-        for idx in groups.values():
-            clean, deg, rec = (torch.stack([scored[i][k].flatten().float() for i in idx]).to(self.device) for k in (1, 2, 3))
-            inp = spectral.evaluate(deg, clean, int(sr), values=values, align=window)
-            out = spectral.evaluate(rec, clean, int(sr), values=values, align=window)
-            for i, row in zip(idx, spectral.report_rows([scored[i][0] for i in idx], inp, out)):
-                rows[i] = row
-        tag = f".rank{self.rank}" if self.world_size > 1 else ""
-        spectral.write_report(os.path.join(self.paths[mode], f"spectral{tag}.csv"), rows)
-        spectral.write_report(os.path.join(self.paths[mode], f"spectral_summary{tag}.csv"), spectral.summary_rows(rows))
-        self.spectral_report = rows
+        self.spectral_report = self._write_pair_report(mode, scored, sr, spectral, "spectral", spectral_options(self.args.tester)[1])
 
     def _write_srmr_report(self, mode, items):
         """SRMR report of a mode (``tester.srmr.use``; utils/srmr.py), once per mode after sampling: ``srmr.csv`` (per written

@@ -7,7 +7,6 @@ the analysis is three library calls (``buddy_row_argmax_abs``, ``buddy_fir_bank`
 form: a CPU tensor raises ``BuddyHipError``."""
 from __future__ import annotations
 
-import csv
 import functools
 import math
 
@@ -15,6 +14,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .report import write_report
 
 OCTAVES = (125, 250, 500, 1000, 2000, 4000)
 VALUES = ("EDT", "T20", "T30", "C50", "DRR", "Ts")        # order of the last axis of ``values``; flag bit q = value q is defined
@@ -105,15 +105,7 @@ def rir_acoustics(h, fs, lens=None, centres=OCTAVES, return_edc=False):
     return RirAcoustics((0.0,) + tuple(float(c) for c in centres), out.cpu(), flags.cpu(), n0.cpu(), edc)
 
 
-# ---- CSV reports: plain text through the csv module, NaN as an empty field, flags as an integer -----------------------------------------------
-def _field(v):
-    if isinstance(v, (float, np.floating)):
-        return "" if math.isnan(v) else repr(float(v))
-    if isinstance(v, (np.integer,)):
-        return int(v)
-    return v
-
-
+# ---- CSV reports (written by utils/report.py: NaN as an empty field, flags as an integer) ---------------------------------------------------------
 def band_label(band):
     return "broadband" if float(band) == 0.0 else f"{float(band):g}"
 
@@ -136,18 +128,6 @@ def report_rows(names, est, true=None):
                     row["err_" + v] = row[v] - row["true_" + v]
             rows.append(row)
     return rows
-
-
-def write_report(path, rows):
-    """``rows``: dicts with the same keys (``report_rows``); the header is the keys of the first row"""
-    rows = list(rows)
-    with open(path, "w", newline="") as f:
-        wr = csv.writer(f)
-        if rows:
-            cols = list(rows[0].keys())
-            wr.writerow(cols)
-            for r in rows:
-                wr.writerow([_field(r[c]) for c in cols])
 
 
 def parameter_rows(names, params):

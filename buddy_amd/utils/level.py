@@ -13,7 +13,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .acoustics import write_report  # noqa: F401  -- the CSV conventions of the acoustics report: NaN as an empty field, repr(float)
+from . import report
+from .report import write_report  # noqa: F401  -- the CSV conventions of every report: NaN as an empty field, repr(float)
 
 THRESHOLDS = 16                                      # c_j = R 2^(j - 15)
 MARGIN_DB, TIME_CONSTANT, HANGOVER = 15.9, 0.03, 0.2
@@ -195,19 +196,10 @@ def report_rows(names, res, extra=None):
 def summary_rows(rows):
     """n, mean, median and standard deviation (numpy's, population form) of ``level_db``, ``activity`` and ``rms_db - level_db`` over the rows where
     the level is defined; NaN where there is none"""
-    rows = list(rows)
-    nan = float("nan")
-    cols = {"level_db": [r["level_db"] for r in rows], "activity": [r["activity"] for r in rows],
-            "rms_db-level_db": [r["rms_db"] - r["level_db"] for r in rows]}
-    out = []
-    for col, v in cols.items():
-        v = np.array(v, dtype=np.float64)
-        v = v[~np.isnan(v)]
-        out.append({"value": col, "n": int(v.size), "mean": float(np.mean(v)) if v.size else nan, "median": float(np.median(v)) if v.size else nan,
-                    "std": float(np.std(v)) if v.size else nan})
-    return out
+    return report.summarise(rows, {"level_db": lambda r: r["level_db"], "activity": lambda r: r["activity"],
+                                   "rms_db-level_db": lambda r: r["rms_db"] - r["level_db"]})
 
 
 def format_summary(summary):
     """the summary as lines of text (what the tool prints)"""
-    return "\n".join(f"{r['value']:>16}  n {r['n']:5d}  mean {r['mean']:10.4f}  median {r['median']:10.4f}  std {r['std']:9.4f}" for r in summary)
+    return report.format_summary(summary, 16, 5)

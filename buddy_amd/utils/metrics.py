@@ -11,8 +11,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from . import resample as _rs
-from .acoustics import write_report  # noqa: F401  -- the CSV conventions of the acoustics report: NaN as an empty field, repr(float)
+from . import _rows, report
+from .report import write_report  # noqa: F401  -- the CSV conventions of every report: NaN as an empty field, repr(float)
 
 
 def si_sdr(est, ref):
@@ -53,6 +53,11 @@ class Evaluation:
         self.values, self.flags, self.kept_frames, self.frames, self.samples, self.names = values, flags, kept_frames, frames, samples, names
         self.alignment = alignment                   # the ``Alignment`` the rows were scored after (``evaluate(..., align=ms)``), or None
 
+    @classmethod
+    def blank_like(cls, out):
+        """the "before" side of a report without input signals: no value, no flag, the clean signal's frame counts and the samples of ``out``"""
+        return cls(torch.full_like(out.values, float("nan")), torch.zeros_like(out.flags), out.kept_frames, out.frames, out.samples, out.names)
+
 
 ALIGN_FLAGS = ("defined", "edge", "inverted")        # bits 0..2 of ``Alignment.flags``
 MAX_LAG_MS = 50.0                                    # default search window: +-50 ms, about 17 m of path difference.  A choice, not a measurement
@@ -73,18 +78,13 @@ def align(est, ref, fs, lens=None, max_lag_ms=MAX_LAG_MS):
     """Time-align (B, L) float32 estimates to their clean signals on the GPU (``csrc/align.hip``): one integer lag per row, the
     largest |cross-correlation| of the zero-mean signals within +-K = round(max_lag_ms fs / 1000) samples, and both signals trimmed to the
     overlap.  ``lens`` as in ``evaluate``.  Returns an ``Alignment``."""
-    if not isinstance(est, torch.Tensor) or not isinstance(ref, torch.Tensor) or not est.is_cuda or not ref.is_cuda:
-        raise _lib.BuddyHipError("align: the alignment runs on the MI355X only (got a CPU tensor)")
-    lib = _lib.require_gpu()
-    assert est.dim() == 2 and est.shape == ref.shape and est.dtype == ref.dtype == torch.float32, "align takes two (B, L) float32 tensors"
+    lib, (est, ref), lens_t = _rows.enter((est, ref), lens, "align: the alignment runs on the MI355X only (got a CPU tensor)",
+                                          "align takes two (B, L) float32 tensors")
     K = int(round(float(max_lag_ms) * float(fs) / 1000.0))
     if not 0 <= K <= 65535:
         raise ValueError(f"align: max_lag_ms = {max_lag_ms} at {fs} Hz is a window of {K} samples; it must be in 0..65535")
-    est, ref = est.contiguous(), ref.contiguous()
     B, L = est.shape
     dev = est.device
-    lens_t = torch.full((B,), L, dtype=torch.int32) if lens is None else torch.as_tensor(lens, dtype=torch.int32).reshape(B).cpu()
-    assert int(lens_t.min()) >= 1 and int(lens_t.max()) <= L, "every length must be in 1..L"
     lens_d = lens_t.to(dev)
     st = _lib.stream_ptr()
     lag, flags, lens_o = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
@@ -106,26 +106,20 @@ def evaluate(est, ref, fs, lens=None, values=VALUES, align=None):
     default L): valid samples per row, the rest is ignored.  ``align`` = None: no time alignment, the pairs are scored as they are.  ``align`` = a
     search window in ms: every pair is first shifted by its own integer lag and trimmed to the overlap (``align`` above); the result carries the
     ``Alignment`` and ``samples`` is the overlap."""
-    if not isinstance(est, torch.Tensor) or not isinstance(ref, torch.Tensor) or not est.is_cuda or not ref.is_cuda:
-        raise _lib.BuddyHipError("evaluate: the metrics run on the MI355X only (got a CPU tensor)")
-    lib = _lib.require_gpu()
-    assert est.dim() == 2 and est.shape == ref.shape and est.dtype == ref.dtype == torch.float32, "evaluate takes two (B, L) float32 tensors"
-    if int(fs) != fs or int(fs) < STOI_FS:
-        raise ValueError(f"evaluate: the sample rate must be an integer >= {STOI_FS} Hz (STOI is defined at 10 kHz and nothing here upsamples to it), got {fs}")
+    lib, (est, ref), lens_t = _rows.enter(
+        (est, ref), lens, "evaluate: the metrics run on the MI355X only (got a CPU tensor)", "evaluate takes two (B, L) float32 tensors", fs, STOI_FS,
+        f"evaluate: the sample rate must be an integer >= {STOI_FS} Hz (STOI is defined at 10 kHz and nothing here upsamples to it), got {fs}")
     names = tuple(v for v in VALUES if v in tuple(values))
     unknown = sorted(set(values) - set(VALUES))
     if unknown:
         raise ValueError(f"evaluate: unknown values {unknown}; known: {list(VALUES)}")
     fs = int(fs)
-    alignment = None
-    if align is not None:
-        alignment = _align(est, ref, fs, lens=lens, max_lag_ms=float(align))
-        est, ref, lens = alignment.est, alignment.ref, alignment.lens
-    est, ref = est.contiguous(), ref.contiguous()
     B, L = est.shape
     dev = est.device
-    lens_t = torch.full((B,), L, dtype=torch.int32) if lens is None else torch.as_tensor(lens, dtype=torch.int32).reshape(B).cpu()
-    assert int(lens_t.min()) >= 1 and int(lens_t.max()) <= L, "every length must be in 1..L"
+    alignment = None
+    if align is not None:
+        alignment = _align(est, ref, fs, lens=lens_t, max_lag_ms=float(align))
+        est, ref, lens_t = alignment.est, alignment.ref, _rows.lengths(alignment.lens, B, L)
     lens_d = lens_t.to(dev)
     st = _lib.stream_ptr()
     out = torch.full((B, 4), float("nan"), dtype=torch.float64)
@@ -140,15 +134,7 @@ def evaluate(est, ref, fs, lens=None, values=VALUES, align=None):
         flags |= mom_fl.cpu()
 
     if "stoi" in names or "estoi" in names:
-        e10, x10, lens10 = est, ref, lens_t
-        if fs != STOI_FS:
-            up, down = _rs.ratio(fs, STOI_FS)
-            if int(lens_t.min()) < L:            # the resampler takes whole rows: zero behind each row's end (zero extension is what it assumes there)
-                live = torch.arange(L, device=dev)[None, :] < lens_d[:, None]
-                zero = torch.zeros((), dtype=torch.float32, device=dev)
-                e10, x10 = torch.where(live, est, zero), torch.where(live, ref, zero)
-            e10, x10 = _rs.resample(e10, fs, STOI_FS), _rs.resample(x10, fs, STOI_FS)
-            lens10 = torch.tensor([_rs.out_length(int(n), up, down) for n in lens_t], dtype=torch.int32)
+        (e10, x10), lens10 = _rows.to_rate((est, ref), lens_t, fs, STOI_FS)
         L10 = x10.shape[1]
         lens10_d = lens10.to(dev)
         maxF = frames_of(int(lens10.max()))
@@ -181,8 +167,7 @@ def evaluate(est, ref, fs, lens=None, values=VALUES, align=None):
         ws = torch.empty(lib.buddy_lsd_workspace(B, int(lens_t.max())) // 8, dtype=torch.float64, device=dev)
         mean_p = torch.empty(B, dtype=torch.float64, device=dev)
         _lib.check(lib.buddy_frame_power(_lib.ptr(ref), lens_d.data_ptr(), B, L, mean_p.data_ptr(), ws.data_ptr(), ws.numel() * 8, st))
-        ee, xx = mom[:, 0], mom[:, 1]
-        gain = torch.where(ee > 0, torch.sqrt(xx / ee), torch.ones_like(ee)).contiguous()      # the estimate scaled to the clean signal's energy
+        gain = _rows.pair_gain(mom)
         delta = (1e-8 * mean_p).contiguous()
         lsd = torch.empty(B, dtype=torch.float64, device=dev)
         lsd_fl = torch.empty(B, dtype=torch.int32, device=dev)
@@ -200,22 +185,12 @@ def report_rows(names, inp, out):
     clean signal (the same in both).  Where an evaluation carries an ``Alignment`` the row ends with ``lag_in`` / ``lag_out`` (samples, positive: late),
     ``lag_ms_*``, ``xcorr_*`` (rho) and ``align_flags_*``; the side without one has empty fields and flag word 0.  Without any, the columns are those
     above and nothing else."""
-    al = [getattr(ev, "alignment", None) for ev in (inp, out)]
     rows = []
     for b, name in enumerate(names):
-        row = {"file": name, "samples": int(out.samples[b])}
-        for q, m in enumerate(VALUES):
-            if m in out.names:
-                vi, vo = float(inp.values[b, q]), float(out.values[b, q])
-                row[m + "_in"], row[m + "_out"], row[m + "_delta"] = vi, vo, vo - vi
+        row = {"file": name, "samples": int(out.samples[b]), **report.delta_columns(VALUES, out.names, inp, out, b)}
         row["flags_in"], row["flags_out"] = int(inp.flags[b]), int(out.flags[b])
         row["kept_frames"], row["frames"] = int(out.kept_frames[b]), int(out.frames[b])
-        if al[0] is not None or al[1] is not None:
-            nan = float("nan")
-            for col, get in (("lag", lambda a: int(a.lag[b])), ("lag_ms", lambda a: 1000.0 * int(a.lag[b]) / float(a.fs)), ("xcorr", lambda a: float(a.rho[b])),
-                             ("align_flags", lambda a: int(a.flags[b]))):
-                for side, a in zip(("_in", "_out"), al):
-                    row[col + side] = get(a) if a is not None else (0 if col == "align_flags" else nan)
+        row.update(report.alignment_columns(inp, out, b))
         rows.append(row)
     return rows
 
@@ -224,21 +199,9 @@ def summary_rows(rows):
     """one dict per value column of ``report_rows``: the number of files where it is defined, and their mean, median and standard deviation
     (numpy's, population form); NaN where no file defines it.  Of an aligned report the ``lag_ms_*`` and ``xcorr_*`` columns are summarised too, the
     integer lags and the flag words are not"""
-    rows = list(rows)
-    out = []
-    if not rows:
-        return out
-    for col in rows[0]:
-        if not col.endswith(("_in", "_out", "_delta")) or col.startswith(("flags", "align_flags")) or col in ("lag_in", "lag_out"):
-            continue
-        v = np.array([r[col] for r in rows], dtype=np.float64)
-        v = v[~np.isnan(v)]
-        nan = float("nan")
-        out.append({"value": col, "n": int(v.size), "mean": float(np.mean(v)) if v.size else nan, "median": float(np.median(v)) if v.size else nan,
-                    "std": float(np.std(v)) if v.size else nan})
-    return out
+    return report.summarise(rows, report.paired)
 
 
 def format_summary(summary):
     """the summary as lines of text (what the tool prints)"""
-    return "\n".join(f"{r['value']:>14}  n {r['n']:4d}  mean {r['mean']:10.4f}  median {r['median']:10.4f}  std {r['std']:9.4f}" for r in summary)
+    return report.format_summary(summary, 14, 4)

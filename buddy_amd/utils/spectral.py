@@ -11,9 +11,9 @@ import numpy as np
 import torch
 
 from .. import _lib
-from . import resample as _rs
-from .acoustics import write_report  # noqa: F401  -- the CSV conventions of the acoustics report: NaN as an empty field, repr(float)
+from . import _rows, report
 from .metrics import align as _align
+from .report import write_report  # noqa: F401  -- the CSV conventions of every report: NaN as an empty field, repr(float)
 
 VALUES = ("cd", "llr", "fwsegsnr")                   # order of the last axis of ``SpectralEvaluation.values``; flag bit q = value q is defined
 FS = 16000                                           # the rate the three measures are defined at
@@ -67,42 +67,33 @@ class SpectralEvaluation:
         self.values, self.flags, self.frames, self.llr_frames, self.fwsegsnr_frames = values, flags, frames, llr_frames, fwsegsnr_frames
         self.samples, self.names, self.alignment = samples, names, alignment
 
+    @classmethod
+    def blank_like(cls, out):
+        """the "before" side of a report without input signals: no value, no flag, no counted frame, the frames and the samples of ``out``"""
+        zero = torch.zeros_like(out.flags)
+        return cls(torch.full_like(out.values, float("nan")), zero, out.frames, zero, zero, out.samples, out.names)
+
 
 def evaluate(est, ref, fs, lens=None, values=VALUES, align=None):
     """est, ref (B, L) float32 on the GPU at rate ``fs`` (an int >= 16 000): the estimates and the clean signals, row by row; ``lens`` (B ints, default
     L): valid samples per row, the rest is ignored.  Above 16 kHz both signals go through the project's resampler first.  ``align`` as in
     ``metrics.evaluate``: None scores the pairs as they are, a search window in ms shifts every pair by its own integer lag and trims it to the
     overlap first (at the input's rate); the result carries the ``Alignment`` and ``samples`` is the overlap."""
-    if not isinstance(est, torch.Tensor) or not isinstance(ref, torch.Tensor) or not est.is_cuda or not ref.is_cuda:
-        raise _lib.BuddyHipError("spectral.evaluate: the measures run on the MI355X only (got a CPU tensor)")
-    lib = _lib.require_gpu()
-    assert est.dim() == 2 and est.shape == ref.shape and est.dtype == ref.dtype == torch.float32, "evaluate takes two (B, L) float32 tensors"
-    if int(fs) != fs or int(fs) < FS:
-        raise ValueError(f"spectral.evaluate: the sample rate must be an integer >= {FS} Hz (the measures are defined at 16 kHz and nothing here upsamples "
-                         f"to it), got {fs}")
+    lib, (est, ref), lens_t = _rows.enter(
+        (est, ref), lens, "spectral.evaluate: the measures run on the MI355X only (got a CPU tensor)", "evaluate takes two (B, L) float32 tensors", fs, FS,
+        f"spectral.evaluate: the sample rate must be an integer >= {FS} Hz (the measures are defined at 16 kHz and nothing here upsamples to it), got {fs}")
     unknown = sorted(set(values) - set(VALUES))
     if unknown:
         raise ValueError(f"spectral.evaluate: unknown values {unknown}; known: {list(VALUES)}")
     names = tuple(v for v in VALUES if v in tuple(values))
     fs = int(fs)
-    alignment = None
-    if align is not None:
-        alignment = _align(est, ref, fs, lens=lens, max_lag_ms=float(align))
-        est, ref, lens = alignment.est, alignment.ref, alignment.lens
-    est, ref = est.contiguous(), ref.contiguous()
     B, L = est.shape
     dev = est.device
-    lens_t = torch.full((B,), L, dtype=torch.int32) if lens is None else torch.as_tensor(lens, dtype=torch.int32).reshape(B).cpu()
-    assert int(lens_t.min()) >= 1 and int(lens_t.max()) <= L, "every length must be in 1..L"
-    e16, x16, lens16 = est, ref, lens_t
-    if fs != FS:
-        up, down = _rs.ratio(fs, FS)
-        if int(lens_t.min()) < L:                # the resampler takes whole rows: zero behind each row's end (zero extension is what it assumes there)
-            live = torch.arange(L, device=dev)[None, :] < lens_t.to(dev)[:, None]
-            zero = torch.zeros((), dtype=torch.float32, device=dev)
-            e16, x16 = torch.where(live, est, zero), torch.where(live, ref, zero)
-        e16, x16 = _rs.resample(e16, fs, FS).contiguous(), _rs.resample(x16, fs, FS).contiguous()
-        lens16 = torch.tensor([_rs.out_length(int(n), up, down) for n in lens_t], dtype=torch.int32)
+    alignment = None
+    if align is not None:
+        alignment = _align(est, ref, fs, lens=lens_t, max_lag_ms=float(align))
+        est, ref, lens_t = alignment.est, alignment.ref, _rows.lengths(alignment.lens, B, L)
+    (e16, x16), lens16 = _rows.to_rate((est, ref), lens_t, fs, FS)
     L16 = x16.shape[1]
     lens_d = lens16.to(dev)
     st = _lib.stream_ptr()
@@ -119,9 +110,8 @@ def evaluate(est, ref, fs, lens=None, values=VALUES, align=None):
         mom = torch.empty(B, 4, dtype=torch.float64, device=dev)
         mom_fl = torch.empty(B, dtype=torch.int32, device=dev)
         _lib.check(lib.buddy_pair_moments(_lib.ptr(e16), _lib.ptr(x16), lens_d.data_ptr(), B, L16, mom.data_ptr(), mom_fl.data_ptr(), st))
-        ee, xx = mom[:, 0], mom[:, 1]
-        gain = torch.where(ee > 0, torch.sqrt(xx / ee), torch.ones_like(ee)).contiguous()      # the estimate scaled to the clean signal's energy
-        delta = (FLOOR * (xx / lens_d.double()) * _window_energy()).contiguous()
+        gain = _rows.pair_gain(mom)
+        delta = (FLOOR * (mom[:, 1] / lens_d.double()) * _window_energy()).contiguous()
         frames_d = frames.to(dev)
         X, E = (torch.empty(B, ldf, BINS, dtype=torch.float32, device=dev) for _ in range(2))
         for sig, S in ((x16, X), (e16, E)):
@@ -157,24 +147,14 @@ def report_rows(names, inp, out):
     reconstruction: ``<m>_in``, ``<m>_out`` and ``<m>_delta`` = out - in per value asked for, both flag words, the frames at 16 kHz and the frames the
     LLR and fwSegSNR means were taken over, per side.  Where an evaluation carries an ``Alignment`` the row ends with the ``lag_*``, ``lag_ms_*``,
     ``xcorr_*`` and ``align_flags_*`` columns of ``metrics.report_rows``."""
-    al = [getattr(ev, "alignment", None) for ev in (inp, out)]
     rows = []
     for b, name in enumerate(names):
-        row = {"file": name, "samples": int(out.samples[b])}
-        for q, m in enumerate(VALUES):
-            if m in out.names:
-                vi, vo = float(inp.values[b, q]), float(out.values[b, q])
-                row[m + "_in"], row[m + "_out"], row[m + "_delta"] = vi, vo, vo - vi
+        row = {"file": name, "samples": int(out.samples[b]), **report.delta_columns(VALUES, out.names, inp, out, b)}
         row["flags_in"], row["flags_out"] = int(inp.flags[b]), int(out.flags[b])
         row["frames"] = int(out.frames[b])
         row["llr_frames_in"], row["llr_frames_out"] = int(inp.llr_frames[b]), int(out.llr_frames[b])
         row["fwsegsnr_frames_in"], row["fwsegsnr_frames_out"] = int(inp.fwsegsnr_frames[b]), int(out.fwsegsnr_frames[b])
-        if al[0] is not None or al[1] is not None:
-            nan = float("nan")
-            for col, get in (("lag", lambda a: int(a.lag[b])), ("lag_ms", lambda a: 1000.0 * int(a.lag[b]) / float(a.fs)), ("xcorr", lambda a: float(a.rho[b])),
-                             ("align_flags", lambda a: int(a.flags[b]))):
-                for side, a in zip(("_in", "_out"), al):
-                    row[col + side] = get(a) if a is not None else (0 if col == "align_flags" else nan)
+        row.update(report.alignment_columns(inp, out, b))
         rows.append(row)
     return rows
 
@@ -183,21 +163,9 @@ def summary_rows(rows):
     """one dict per value column of ``report_rows``: the number of files where it is defined, and their mean, median and standard deviation
     (numpy's, population form); NaN where no file defines it.  Of an aligned report the ``lag_ms_*`` and ``xcorr_*`` columns are summarised too; the
     integer lags, the frame counts and the flag words are not"""
-    rows = list(rows)
-    out = []
-    if not rows:
-        return out
-    nan = float("nan")
-    for col in rows[0]:
-        if not col.endswith(("_in", "_out", "_delta")) or col.startswith(("flags", "align_flags", "llr_frames", "fwsegsnr_frames")) or col in ("lag_in", "lag_out"):
-            continue
-        v = np.array([r[col] for r in rows], dtype=np.float64)
-        v = v[~np.isnan(v)]
-        out.append({"value": col, "n": int(v.size), "mean": float(np.mean(v)) if v.size else nan, "median": float(np.median(v)) if v.size else nan,
-                    "std": float(np.std(v)) if v.size else nan})
-    return out
+    return report.summarise(rows, lambda col: report.paired(col) and not col.startswith(("llr_frames", "fwsegsnr_frames")))
 
 
 def format_summary(summary):
     """the summary as lines of text (what the tool prints)"""
-    return "\n".join(f"{r['value']:>16}  n {r['n']:4d}  mean {r['mean']:10.4f}  median {r['median']:10.4f}  std {r['std']:9.4f}" for r in summary)
+    return report.format_summary(summary, 16, 4)

@@ -13,9 +13,9 @@ import numpy as np
 import torch
 
 from .. import _lib
-from . import resample as _rs
-from .acoustics import write_report  # noqa: F401  -- the CSV conventions of the acoustics report: NaN as an empty field, repr(float)
+from . import _rows, report
 from .metrics import format_summary  # noqa: F401  -- the summary as lines of text (what the tool prints)
+from .report import write_report  # noqa: F401  -- the CSV conventions of every report: NaN as an empty field, repr(float)
 
 FS = 16000                                           # the rate the analysis runs at
 MIN_FS = 8000
@@ -120,26 +120,10 @@ class Srmr:
 def srmr(x, fs, lens=None, return_envelope=False):
     """x (B, L) float32 on the GPU at rate ``fs`` (an int >= 8000); ``lens`` (B ints, default L): valid samples per row, the rest is ignored.
     ``return_envelope`` keeps the gammatone envelopes (23 floats per sample) in the result."""
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise _lib.BuddyHipError("srmr: the score runs on the MI355X only (got a CPU tensor)")
-    lib = _lib.require_gpu()
-    assert x.dim() == 2 and x.dtype == torch.float32, "srmr takes a (B, L) float32 tensor"
-    if int(fs) != fs or int(fs) < MIN_FS:
-        raise ValueError(f"srmr: the sample rate must be an integer >= {MIN_FS} Hz, got {fs}")
-    fs = int(fs)
-    x = x.contiguous()
-    B, L = x.shape
-    dev = x.device
-    lens_t = torch.full((B,), L, dtype=torch.int32) if lens is None else torch.as_tensor(lens, dtype=torch.int32).reshape(B).cpu()
-    assert int(lens_t.min()) >= 1 and int(lens_t.max()) <= L, "every length must be in 1..L"
-    x16, lens16 = x, lens_t
-    if fs != FS:
-        up, down = _rs.ratio(fs, FS)
-        if int(lens_t.min()) < L:                # the resampler takes whole rows: zero behind each row's end (zero extension is what it assumes there)
-            live = torch.arange(L, device=dev)[None, :] < lens_t.to(dev)[:, None]
-            x16 = torch.where(live, x, torch.zeros((), dtype=torch.float32, device=dev))
-        x16 = _rs.resample(x16, fs, FS)
-        lens16 = torch.tensor([_rs.out_length(int(n), up, down) for n in lens_t], dtype=torch.int32)
+    lib, (x,), lens_t = _rows.enter((x,), lens, "srmr: the score runs on the MI355X only (got a CPU tensor)", "srmr takes a (B, L) float32 tensor", fs, MIN_FS,
+                                    f"srmr: the sample rate must be an integer >= {MIN_FS} Hz, got {fs}")
+    B, dev = x.shape[0], x.device
+    (x16,), lens16 = _rows.to_rate((x,), lens_t, int(fs), FS)
     L16 = x16.shape[1]
     lens_d = lens16.to(dev)
     st = _lib.stream_ptr()
@@ -219,16 +203,4 @@ def report_rows(names, inp, out, clean=None):
 def summary_rows(rows):
     """one dict per ``srmr_*`` column of ``report_rows``: the number of files where it is defined, and their mean, median and standard deviation
     (numpy's, population form); NaN where no file defines it"""
-    rows = list(rows)
-    out = []
-    if not rows:
-        return out
-    nan = float("nan")
-    for col in rows[0]:
-        if not col.startswith("srmr_"):
-            continue
-        v = np.array([r[col] for r in rows], dtype=np.float64)
-        v = v[~np.isnan(v)]
-        out.append({"value": col, "n": int(v.size), "mean": float(np.mean(v)) if v.size else nan, "median": float(np.median(v)) if v.size else nan,
-                    "std": float(np.std(v)) if v.size else nan})
-    return out
+    return report.summarise(rows, lambda col: col.startswith("srmr_"))

@@ -14,6 +14,7 @@ one batch.  Writes ``metrics.csv`` and ``metrics_summary.csv`` (the tester's fil
 directory) and prints the summary.  Without ``--input`` the ``_in`` columns are empty.  This is the way to score a multi-rank run as a whole, or the
 output folders of another implementation."""
 import argparse
+import collections
 import os
 import sys
 
@@ -41,48 +42,61 @@ def wav_names(d):
     return sorted(f for f in os.listdir(d) if f.lower().endswith(".wav"))
 
 
-def score(reference, estimate, inp=None, values=metrics.VALUES, device="cuda:0", align=None):
-    """the rows of ``metrics.report_rows`` for every wav name present in ``reference`` and ``estimate`` (and ``inp``, when given); ``align``: the
-    search window in ms of ``metrics.evaluate``, None = score the pairs as they are"""
+# what tells this tool from tools/spectral.py: the module that scores, the lowest rate it takes, the prefix of the messages and what they call the
+# values, and the stem of the two files
+Kind = collections.namedtuple("Kind", "module min_fs who noun stem")
+METRICS = Kind(metrics, metrics.STOI_FS, "evaluate", "metrics", "metrics")
+
+
+def score_pairs(kind, reference, estimate, inp, values, device, align):
+    """the rows of ``kind.module.report_rows`` for every wav name present in ``reference`` and ``estimate`` (and ``inp``, when given); ``align``: the
+    search window in ms of its ``evaluate``, None = score the pairs as they are"""
+    module, who = kind.module, kind.who
     names = [n for n in wav_names(estimate) if os.path.exists(os.path.join(reference, n)) and (inp is None or os.path.exists(os.path.join(inp, n)))]
     if not names:
-        raise SystemExit(f"evaluate: no wav name is common to {reference} and {estimate}" + (f" and {inp}" if inp else ""))
+        raise SystemExit(f"{who}: no wav name is common to {reference} and {estimate}" + (f" and {inp}" if inp else ""))
     items, groups = [], {}
     for n in names:
         sigs = [read_wav(os.path.join(d, n)) for d in (reference, estimate) + ((inp,) if inp else ())]
         rates = {fs for fs, _ in sigs}
         if len(rates) > 1:
-            raise SystemExit(f"evaluate: {n} has the rates {sorted(rates)}; the signals of a pair must share one rate")
+            raise SystemExit(f"{who}: {n} has the rates {sorted(rates)}; the signals of a pair must share one rate")
         fs = rates.pop()
-        if fs < metrics.STOI_FS:
-            raise SystemExit(f"evaluate: {n} is at {fs} Hz; the metrics need at least {metrics.STOI_FS} Hz")
+        if fs < kind.min_fs:
+            raise SystemExit(f"{who}: {n} is at {fs} Hz; the {kind.noun} need at least {kind.min_fs} Hz")
         L = min(len(a) for _, a in sigs)
         if L < 1:
-            raise SystemExit(f"evaluate: {n} is empty")
+            raise SystemExit(f"{who}: {n} is empty")
         groups.setdefault((fs, L), []).append(len(items))
         items.append([a[:L] for _, a in sigs])
     rows = [None] * len(items)
     for (fs, L), idx in groups.items():
         ref, est = (torch.from_numpy(np.stack([items[i][k] for i in idx])).to(device) for k in (0, 1))
-        out = metrics.evaluate(est, ref, fs, values=values, align=align)
+        out = module.evaluate(est, ref, fs, values=values, align=align)
         if inp:
-            before = metrics.evaluate(torch.from_numpy(np.stack([items[i][2] for i in idx])).to(device), ref, fs, values=values, align=align)
+            before = module.evaluate(torch.from_numpy(np.stack([items[i][2] for i in idx])).to(device), ref, fs, values=values, align=align)
         else:       # no input signals: the _in and _delta columns stay empty
-            nan = torch.full_like(out.values, float("nan"))
-            before = metrics.Evaluation(nan, torch.zeros_like(out.flags), out.kept_frames, out.frames, out.samples, out.names)
-        for i, row in zip(idx, metrics.report_rows([names[i][:-4] for i in idx], before, out)):
+            before = type(out).blank_like(out)
+        for i, row in zip(idx, module.report_rows([names[i][:-4] for i in idx], before, out)):
             rows[i] = row
     return rows
 
 
-def main(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+def score(reference, estimate, inp=None, values=metrics.VALUES, device="cuda:0", align=None):
+    """``score_pairs`` with ``metrics.evaluate``"""
+    return score_pairs(METRICS, reference, estimate, inp, values, device, align)
+
+
+def run(kind, doc, argv=None):
+    """the command line of this tool and of tools/spectral.py; ``doc``: the tool's own module docstring"""
+    module, stem = kind.module, kind.stem
+    ap = argparse.ArgumentParser(description=doc.split("\n\n")[0])
     ap.add_argument("mode_dir", nargs="?", help="a mode directory of a test run: holds original/, degraded/ and reconstructed/")
     ap.add_argument("--reference", help="directory of the clean wavs")
     ap.add_argument("--estimate", help="directory of the wavs to score")
     ap.add_argument("--input", help="directory of the degraded wavs (fills the _in and _delta columns)")
-    ap.add_argument("--out", help="directory for metrics.csv and metrics_summary.csv")
-    ap.add_argument("--values", default=",".join(metrics.VALUES), help="comma-separated subset of " + ",".join(metrics.VALUES))
+    ap.add_argument("--out", help=f"directory for {stem}.csv and {stem}_summary.csv")
+    ap.add_argument("--values", default=",".join(module.VALUES), help="comma-separated subset of " + ",".join(module.VALUES))
     ap.add_argument("--align", nargs="?", type=float, const=metrics.MAX_LAG_MS, default=None, metavar="MS",
                     help="time-align every pair before it is scored: integer lag within +-MS ms (default %(const)s), pair trimmed to the overlap")
     ap.add_argument("--device", default="cuda:0")
@@ -96,14 +110,18 @@ def main(argv=None):
         if not (a.reference and a.estimate):
             ap.error("give a mode directory, or both --reference and --estimate")
         ref, est, inp, out = a.reference, a.estimate, a.input, a.out or a.estimate
-    rows = score(ref, est, inp, values=tuple(v for v in a.values.split(",") if v), device=a.device, align=a.align)
+    rows = score_pairs(kind, ref, est, inp, tuple(v for v in a.values.split(",") if v), a.device, a.align)
     os.makedirs(out, exist_ok=True)
-    summary = metrics.summary_rows(rows)
-    metrics.write_report(os.path.join(out, "metrics.csv"), rows)
-    metrics.write_report(os.path.join(out, "metrics_summary.csv"), summary)
-    print(metrics.format_summary(summary))
-    print(os.path.join(out, "metrics.csv"))
+    summary = module.summary_rows(rows)
+    module.write_report(os.path.join(out, f"{stem}.csv"), rows)
+    module.write_report(os.path.join(out, f"{stem}_summary.csv"), summary)
+    print(module.format_summary(summary))
+    print(os.path.join(out, f"{stem}.csv"))
     return rows
+
+
+def main(argv=None):
+    return run(METRICS, __doc__, argv)
 
 
 if __name__ == "__main__":
