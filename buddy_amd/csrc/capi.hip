@@ -1094,6 +1094,30 @@ int buddy_band_combine(const double* u, int B, int nb, long long ldu, int N, con
   return finish();
 }
 
+// ---- multichannel WPE ----
+static int wpe_mc_args(int D, int taps, int delay, int iterations) {
+  if (!wpe_mc_supported(D, taps) || delay < 0 || iterations < 0) {
+    set_error("bad multichannel wpe arguments (1 <= D <= 8, taps >= 1, D * taps <= 96, delay >= 0, iterations >= 0)"); return BUDDY_ERR_ARG;
+  }
+  return BUDDY_OK;
+}
+
+int buddy_wpe_mc(const double* Y, double* X, double* scratch, int rows, int D, int T, int taps, int delay, int iterations, void* stream) {
+  if (!Y || !X || !scratch || rows < 1 || T < 1) { set_error("bad multichannel wpe arguments (null pointer, rows < 1 or T < 1)"); return BUDDY_ERR_ARG; }
+  if (wpe_mc_args(D, taps, delay, iterations)) return BUDDY_ERR_ARG;
+  if (launch_wpe_mc(Y, X, scratch, rows, D, T, taps, delay, iterations, (hipStream_t)stream)) { set_error("multichannel wpe: LDS request refused"); return BUDDY_ERR_HIP; }
+  return finish();
+}
+
+long long buddy_wpe_mc_workspace_bytes(int B, int D, int L) { return (B < 1 || D < 1 || L < 1) ? 0 : (long long)wpe_mc_workspace_bytes(B, D, L); }
+
+int buddy_wpe_mc_dereverb(const float* y, float* out, void* workspace, int B, int D, int L, int taps, int delay, int iterations, void* stream) {
+  if (!y || !out || !workspace || B < 1 || L < 1) { set_error("bad multichannel wpe arguments (null pointer, B < 1 or L < 1)"); return BUDDY_ERR_ARG; }
+  if (wpe_mc_args(D, taps, delay, iterations)) return BUDDY_ERR_ARG;
+  if (launch_wpe_mc_dereverb(y, out, workspace, B, D, L, taps, delay, iterations, (hipStream_t)stream)) { set_error("multichannel wpe: LDS request refused"); return BUDDY_ERR_HIP; }
+  return finish();
+}
+
 // ---- WPE warm start ----
 int buddy_wpe(const double* Y, double* X, double* scratch, int rows, int T, int taps, int delay, int iterations, void* stream) {
   if (!Y || !X || !scratch || rows < 1 || T < 1 || taps < 1 || taps > 56 || delay < 0 || iterations < 0) { set_error("bad wpe arguments (taps <= 56)"); return BUDDY_ERR_ARG; }

@@ -174,6 +174,13 @@ void launch_wpe(const double* Y, double* X, double* inv_scratch, int rows, int T
 size_t wpe_workspace_bytes(int B, int L);
 int wpe_frames(int L);
 void launch_wpe_dereverb(const float* y, float* out, void* work, int B, int L, int taps, int delay, int iters, hipStream_t st);
+void launch_wpe_stft(const float* y, double* Y, int rows, int L, int T, hipStream_t st);
+void launch_wpe_istft(const double* Z, float* out, int rows, int L, int T, hipStream_t st);
+// multichannel WPE (wpe_mc.hip): one problem per row = D channels x T frames; the launchers return nonzero when the LDS request is refused
+bool wpe_mc_supported(int D, int taps);
+int launch_wpe_mc(const double* Y, double* X, double* scratch, int rows, int D, int T, int taps, int delay, int iters, hipStream_t st);
+size_t wpe_mc_workspace_bytes(int B, int D, int L);
+int launch_wpe_mc_dereverb(const float* y, float* out, void* work, int B, int D, int L, int taps, int delay, int iters, hipStream_t st);
 // rational polyphase resampler (resample.hip): y[b][n] = sum_m x[b][m] h[n*down - m*up + (Nh-1)/2], Lout = ceil(Lin*up/down); arguments checked by the C entry
 long long resample_tiles(long long Lout);
 void launch_resample(const float* x, int B, long long Lin, const float* h, int Nh, int up, int down, float* y, long long Lout, hipStream_t st);

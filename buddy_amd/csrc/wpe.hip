@@ -174,6 +174,15 @@ void launch_wpe(const double* Y, double* X, double* inv_scratch, int rows, int T
                      inv_scratch, T, taps, delay, iters);
 }
 
+// the two transforms for other callers (wpe_mc.hip): rows x L float32 <-> (rows, 257, T) complex128 as interleaved doubles
+void launch_wpe_stft(const float* y, double* Y, int rows, int L, int T, hipStream_t st) {
+  hipLaunchKernelGGL(wpe_stft_kernel, dim3(T, rows), dim3(256), 0, st, y, reinterpret_cast<c128*>(Y), L, T);
+}
+
+void launch_wpe_istft(const double* Z, float* out, int rows, int L, int T, hipStream_t st) {
+  hipLaunchKernelGGL(wpe_istft_kernel, dim3((L + WH - 1) / WH, rows), dim3(512), 0, st, reinterpret_cast<const c128*>(Z), out, L, T);
+}
+
 int wpe_frames(int L) {                                      // frames of nara_wpe.utils.stft(size 512, shift 128, fading, pad)
   long long n = (long long)L + 2 * WPAD;
   if (n < WS) n = WS;

@@ -26,5 +26,12 @@ class AudioFolder:
             audio = np.mean(audio, axis=1)
         return audio, int(fs), os.path.basename(self.files[idx])
 
+    def channels(self, idx):
+        """the file's channels unmixed: ``((C, n) float64 at the file's own rate, fs, filename)``; a mono file is C = 1.  ``__getitem__`` is their
+        mean.  For ``tester.real_recordings.channels: reference | wpe`` and ``tools/wpe.py``."""
+        audio, fs = _read(self.files[idx])
+        audio = audio[None, :] if audio.ndim == 1 else np.ascontiguousarray(audio.T)
+        return audio, int(fs), os.path.basename(self.files[idx])
+
     def __len__(self):
         return len(self.files)

@@ -33,6 +33,18 @@ def shared_rir_options(rr):
     return bool(rr.get("shared_rir", False)), int(rr.get("shared_rir_max_chunks", 32))
 
 
+def channel_options(rr):
+    """(channels, reference_channel, (taps, delay, iterations)) of a ``real_recordings`` block; a config written before the keys existed means
+    ("mean", 0, nara_wpe's defaults).  channels: mean = the channel mean, as always | reference = one channel | wpe = multichannel WPE on all
+    channels (utils/wpe.py), its reference channel observed."""
+    mode = str(rr.get("channels", "mean"))
+    assert mode in ("mean", "reference", "wpe"), "real_recordings.channels is 'mean', 'reference' or 'wpe'"
+    ref = int(rr.get("reference_channel", 0))
+    assert ref >= 0, "real_recordings.reference_channel is a channel index >= 0"
+    hp = rr.get("wpe", None) or {}
+    return mode, ref, (int(hp.get("taps", 10)), int(hp.get("delay", 3)), int(hp.get("iterations", 3)))
+
+
 def rir_report_options(tester_cfg):
     """(use, octave centres) of the ``rir_report`` block of a tester config; a config written before the block existed means (False, the octaves)"""
     from ..utils.acoustics import OCTAVES
@@ -434,9 +446,17 @@ class Tester:
         self.skipped = []
         files = []
         levels = []    # level=active: one line of levels.csv per file
+        ch_mode, ref_ch, wpe_hp = channel_options(rr)
         for i in range(self.rank, len(self.test_set), self.world_size):
-            audio, fs, filename = self.test_set[i]
-            y = resample(torch.from_numpy(np.asarray(audio)).float().to(self.device), fs, sr)
+            recorded = None      # channels != mean: the reference channel as recorded, at the model's rate (y is then what the sampler observes)
+            if ch_mode == "mean":
+                audio, fs, filename = self.test_set[i]
+                y = resample(torch.from_numpy(np.asarray(audio)).float().to(self.device), fs, sr)
+            else:
+                y, recorded, audio, fs, filename = self._observed_channel(i, ch_mode, ref_ch, wpe_hp, sr)
+                if y is None:
+                    self.skipped.append(filename)
+                    continue
             std = float(y.std()) if y.numel() > 1 else 0.0
             if y.numel() < 1024 or not std > 0.0:       # below what the HIP STFT / loss kernels take (operators/reverb.py), or digital silence
                 print(f"skipping {filename}: {y.numel()} samples at {sr} Hz" + ("" if y.numel() < 1024 else ", silent"))
@@ -453,6 +473,8 @@ class Tester:
                     g = lv.active_gain(rr.get("gain", 1.0), ps.warm_initialization.scaling_factor, float(m.active_rms[0]), ref_activity)
                 levels += lv.report_rows([os.path.basename(filename)[:-4]], m, [{"rule": rule, "g": g}])
             files.append(dict(name=os.path.basename(filename)[:-4], fs=int(fs), n_in=len(audio), y=g * y, g=g))
+            if recorded is not None:
+                files[-1]["recorded"] = g * recorded
         shared, max_rows = shared_rir_options(rr)
         lengths = [f["y"].numel() for f in files]
         if shared:
@@ -495,10 +517,13 @@ class Tester:
             self.results.append((f["name"], pred.detach().cpu()))
             if not writing:
                 continue
-            write_audio_file(f["y"], sr, f["name"], path=self.paths[mode + "degraded"])
+            degraded = f.get("recorded", f["y"])      # channels != mean: the reference channel as recorded, with the file's gain
+            write_audio_file(degraded, sr, f["name"], path=self.paths[mode + "degraded"])
+            if ch_mode == "wpe":                      # what the sampler observed
+                write_audio_file(f["y"], sr, f["name"], path=self.paths[mode + "wpe"])
             p = write_audio_file(pred, f["fs"] if to_input_rate else sr, f["name"], path=self.paths[mode + "reconstructed"])
             if srmr_on:
-                heard.append((f["name"], (f["y"].detach(), sr), (pred.detach(), f["fs"] if to_input_rate else sr), None))
+                heard.append((f["name"], (degraded.detach(), sr), (pred.detach(), f["fs"] if to_input_rate else sr), None))
             if shared:       # one estimate per file (per run where shared_rir_max_chunks cut it): the chunks of a run hold the same RIR
                 for j, (lo, _) in enumerate(f["runs"]):
                     write_audio_file(f["rir"][lo], sr, f["name"] if len(f["runs"]) == 1 else f"{f['name']}_r{j}", path=self.paths[mode + "estimated_rir"])
@@ -512,6 +537,35 @@ class Tester:
             self._write_rir_report(mode, rep, sr)
         if srmr_on:
             self._write_srmr_report(mode, heard)
+
+    def _observed_channel(self, i, ch_mode, ref_ch, wpe_hp, sr):
+        """file ``i`` read with its channels unmixed (``real_recordings.channels: reference | wpe``) -> (observed signal, reference channel as
+        recorded, the reference channel at the file's rate, fs, filename), the first two at the model's rate on the GPU; the observed signal is
+        None for a file to skip.  wpe: ALL channels through one ``wpe_mc_dereverb`` call (B = 1, the whole file), the reference channel of the
+        result observed; a mono file is D = 1 through the same entry.  A file the entry cannot take is skipped; a file with fewer frames than
+        D * taps + delay (R rank-deficient) is processed as ``reference``."""
+        from ..utils import wpe as W
+        from ..utils.resample import resample
+        chans, fs, filename = self.test_set.channels(i)
+        C = chans.shape[0]
+        if ref_ch >= C:
+            print(f"skipping {filename}: {C} channel(s), reference_channel is {ref_ch}")
+            return None, None, None, fs, filename
+        taps, delay, iterations = wpe_hp
+        if ch_mode == "wpe" and not W.supported(C, taps):
+            print(f"skipping {filename}: {C} channels x {taps} taps is outside what the WPE kernel takes (at most {W.MAX_CHANNELS} channels, "
+                  f"channels x taps <= {W.MAX_FILTER})")
+            return None, None, None, fs, filename
+        if ch_mode == "reference":
+            y = resample(torch.from_numpy(chans[ref_ch]).float().to(self.device), fs, sr)
+            return y, y, chans[ref_ch], fs, filename
+        ya = resample(torch.from_numpy(chans).float().to(self.device), fs, sr)                     # (C, n) at the model's rate
+        recorded = ya[ref_ch]
+        if W.frames(ya.shape[1]) < C * taps + delay:
+            print(f"{filename}: {W.frames(ya.shape[1])} frames, fewer than channels x taps + delay = {C * taps + delay}: processed as its reference channel, without WPE")
+            return recorded, recorded, chans[ref_ch], fs, filename
+        y = W.wpe_mc_dereverb(ya[None].contiguous(), taps=taps, delay=delay, iterations=iterations)[0, ref_ch]
+        return y, recorded, chans[ref_ch], fs, filename
 
     def dereverberate_long(self, original, rir, blind, chunk_seconds=8.0, overlap_seconds=1.0, noise=None, shared_rir=False):
         """Long-form policy (testing/longform.py): one long clean/RIR pair -> the reverberant signal cut into overlapping equal chunks,
@@ -561,6 +615,8 @@ class Tester:
             subs = ["original", "degraded", "reconstructed"]
             if mode == "real_blind_dereverberation":         # no clean signal, no true RIR
                 subs = ["degraded", "reconstructed", "estimated_rir"]
+                if channel_options(self.args.tester.get("real_recordings", None) or {})[0] == "wpe":
+                    subs.append("wpe")              # what the sampler observed: the reference channel after multichannel WPE
             elif "dereverberation" in mode:
                 subs.append("true_rir")
                 if mode == "blind_dereverberation":

@@ -11,7 +11,10 @@ more slowly than Eyring's diffuse-field formula says (a 0.30 s nominal room meas
 
 Banded rooms give the walls their own coefficients per octave band and the air an attenuation per band:
 ``shoebox_rir_bands`` computes the band responses in double and combines them through ``octave_bank``; ``draw_band_rooms`` tilts the nominal T60 of
-``draw_rooms``' room over the bands; ``room_rows`` takes the band block that adds the per-band columns of ``rooms.csv``."""
+``draw_rooms``' room over the bands; ``room_rows`` takes the band block that adds the per-band columns of ``rooms.csv``.
+
+Arrays: ``array_rows`` turns one room into the rows of a uniform circular microphone array around its receiver (``tools/make_paired_set.py --mics``),
+``draw_array_angle`` draws its orientation."""
 from __future__ import annotations
 
 import math
@@ -28,6 +31,8 @@ MIN_DISTANCE = 0.01                                  # |s - r| below this makes 
 COLUMNS = ("Lx", "Ly", "Lz", "sx", "sy", "sz", "rx", "ry", "rz", "beta_x0", "beta_x1", "beta_y0", "beta_y1", "beta_z0", "beta_z1", "c")
 MEASURED = ("EDT", "T20", "T30", "C50", "DRR")       # broadband values of rir_acoustics that rooms.csv carries
 ROOM_BANDS = 5                                       # purpose number of the per-band draws (draw_band_rooms): the next free one after ROOMS
+ARRAY = 6                                            # purpose number of a file's array orientation (draw_array_angle): the next free one
+ARRAY_RADIUS = 0.1                                   # default radius of a circular array [m]: the REVERB challenge's 8-microphone array
 BAND_CENTRES = (125, 250, 500, 1000, 2000, 4000)     # default octave centres of banded rooms [Hz]
 BANK_TAPS = 1023                                     # default length of octave_bank's rows: a choice (see there)
 
@@ -151,6 +156,31 @@ def _draw_rooms(names, seed, t60, dims, wall_margin, min_dist, c, max_tries):
 
 
 # ---- banded rooms: wall coefficients and air attenuation per octave band ----------------------------------------------------
+def array_rows(room, mics, radius=ARRAY_RADIUS, angle=0.0):
+    """(mics, 16) float64: the room's row repeated with the receivers of a uniform circular array, one receiver per row (an array is ``mics`` rows
+    of one room for ``shoebox_rir``).  The receivers sit on a horizontal circle of ``radius`` [m] around the room's receiver, microphone m at the
+    angle ``angle + 2 pi m / mics`` from the x axis, at the receiver's height.  ValueError for a radius that leaves the room."""
+    room = np.asarray(room, dtype=np.float64)
+    mics, radius, angle = int(mics), float(radius), float(angle)
+    if room.shape != (16,):
+        raise ValueError(f"array_rows takes one room of 16 doubles, got {tuple(room.shape)}")
+    if mics < 1 or not (radius > 0.0 and math.isfinite(radius)) or not math.isfinite(angle):
+        raise ValueError("array_rows: mics >= 1, a positive finite radius and a finite angle")
+    out = np.tile(room, (mics, 1))
+    phi = angle + 2.0 * np.pi * np.arange(mics) / mics
+    out[:, 6] = room[6] + radius * np.cos(phi)
+    out[:, 7] = room[7] + radius * np.sin(phi)
+    if not (np.all(out[:, 6] > 0.0) and np.all(out[:, 6] < room[0]) and np.all(out[:, 7] > 0.0) and np.all(out[:, 7] < room[1])):
+        raise ValueError(f"array_rows: an array of radius {radius} m around ({room[6]:.3f}, {room[7]:.3f}) leaves the room of {room[0]:.3f} x {room[1]:.3f} m")
+    return out
+
+
+def draw_array_angle(seed, name):
+    """the orientation of a file's array, uniform in [0, 2 pi): draw 0 of purpose ``ARRAY`` of the Philox stream ``rng.stream_key(seed, name)`` --
+    a function of (seed, name) alone, as the room is"""
+    return float(2.0 * np.pi * _rng.uniforms(_rng.stream_key(seed, name), ARRAY, 0, 1)[0])
+
+
 def _check_centres(fs, centres):
     cs = tuple(float(f) for f in centres)
     if not cs or not all(math.isfinite(f) and f > 0 for f in cs):

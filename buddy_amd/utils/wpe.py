@@ -8,7 +8,13 @@ restates its published algorithm (Nakatani et al. 2010; Drude et al. 2018, batch
 UNPINNED against the package itself; checked on the GPU against the independent numpy oracle ``oracle/wpe_ref.py``.
 The whole estimate is ONE library call (``buddy_wpe_dereverb``, ``csrc/wpe.hip``): hand-written complex128 STFT, the iterations (inverse
 power, correlation matrix, Cholesky solve, prediction filter; one workgroup per (utterance, bin) row) and the overlap-add iSTFT.  There is
-no CPU form in the product: a CPU tensor raises ``BuddyHipError`` (the torch restatement used by host-logic tests lives in ``oracle/batched``)."""
+no CPU form in the product: a CPU tensor raises ``BuddyHipError`` (the torch restatement used by host-logic tests lives in ``oracle/batched``).
+
+Multichannel WPE (``wpe_mc_hip``, ``wpe_mc_dereverb``; ``csrc/wpe_mc.hip``) is the same algorithm for D channels, ``oracle/wpe_ref.py:91-120``
+as written for any D: the front end of the real-recordings mode for microphone-array files (``tester.real_recordings.channels: wpe``) and the
+WPE-alone baseline of the reports (``tools/wpe.py``).  Its defaults are nara_wpe's (taps 10, delay 3, 3 iterations).  Parity with nara_wpe
+itself is unpinned for D > 1 as for D = 1, and whether the cascade WPE -> BUDDy scores better than the channel mean on a trained checkpoint is
+UNMEASURED: there is no trained checkpoint here."""
 from __future__ import annotations
 
 import torch
@@ -39,4 +45,69 @@ def wpe_dereverb(y, taps=50, delay=2, iterations=5, size=512, shift=128):
     out = torch.empty_like(yc)
     work = torch.empty(int(lib.buddy_wpe_workspace_bytes(B, L)) // 8, dtype=torch.float64, device=y.device)
     _lib.check(lib.buddy_wpe_dereverb(_lib.ptr(yc), _lib.ptr(out), _lib.ptr(work), B, L, int(taps), int(delay), int(iterations), _lib.stream_ptr()))
+    return out
+
+
+# ---------------------------------------------------------------------------- multichannel WPE (csrc/wpe_mc.hip)
+MAX_CHANNELS = 8
+MAX_FILTER = 96          # D * taps: R (packed triangle) and P of one (utterance, bin) problem stay in the LDS of one workgroup
+
+
+def supported(D, taps):
+    """the shapes ``buddy_wpe_mc`` takes: 1 <= D <= 8 channels, taps >= 1, D * taps <= 96"""
+    return 1 <= int(D) <= MAX_CHANNELS and int(taps) >= 1 and int(D) * int(taps) <= MAX_FILTER
+
+
+def frames(L):
+    """frame count of the STFT (size 512, shift 128, fading, tail padded to a whole frame) for L samples"""
+    size, shift = 512, 128
+    n = int(L) + 2 * (size - shift)
+    if n < size:
+        n = size
+    elif (n + shift - size) % shift:
+        n += shift - (n + shift - size) % shift
+    return (n - size) // shift + 1
+
+
+def _check_mc(name, D, taps, delay, iterations):
+    if not 1 <= D <= MAX_CHANNELS:
+        raise ValueError(f"{name}: {D} channels; the kernel takes 1 to {MAX_CHANNELS}")
+    if taps < 1 or delay < 0 or iterations < 0:
+        raise ValueError(f"{name}: taps >= 1, delay >= 0, iterations >= 0 (got {taps}, {delay}, {iterations})")
+    if not supported(D, taps):
+        raise ValueError(f"{name}: D * taps = {D * taps} is over the limit of {MAX_FILTER}")
+
+
+def wpe_mc_hip(Y, taps=10, delay=3, iterations=3):
+    """The WPE iterations for D channels (``buddy_wpe_mc``): Y (F, D, T) complex128 on the GPU -> (F, D, T); every row a problem of its own."""
+    taps, delay, iterations = int(taps), int(delay), int(iterations)
+    if Y.dim() != 3 or Y.dtype != torch.complex128 or Y.shape[0] < 1 or Y.shape[2] < 1:
+        raise ValueError(f"wpe_mc_hip: Y must be (F, D, T) complex128, got {tuple(Y.shape)} {Y.dtype}")
+    F, D, T = Y.shape
+    _check_mc("wpe_mc_hip", D, taps, delay, iterations)
+    lib = _lib.require_gpu()
+    if not Y.is_cuda:
+        raise _lib.BuddyHipError("wpe_mc_hip: runs on the MI355X only (got a CPU tensor)")
+    Yr = torch.view_as_real(Y.contiguous()).contiguous()                    # (F, D, T, 2) float64
+    Xr = torch.empty_like(Yr)
+    scratch = torch.empty(F * T, dtype=torch.float64, device=Y.device)
+    _lib.check(lib.buddy_wpe_mc(_lib.ptr(Yr), _lib.ptr(Xr), _lib.ptr(scratch), F, D, T, taps, delay, iterations, _lib.stream_ptr()))
+    return torch.view_as_complex(Xr)
+
+
+def wpe_mc_dereverb(y, taps=10, delay=3, iterations=3):
+    """y (B, D, L) float32 on the GPU -> (B, D, L) float32: stft -> D-channel WPE per item and bin -> istft, all channels out, one library
+    call.  Its workspace is B * 257 * frames(L) * (32 * D + 8) bytes: linear in D * L, the whole signal goes in one call."""
+    taps, delay, iterations = int(taps), int(delay), int(iterations)
+    if y.dim() != 3 or y.shape[0] < 1 or y.shape[2] < 1 or y.dtype != torch.float32:
+        raise ValueError(f"wpe_mc_dereverb: y must be (B, D, L) float32, got {tuple(y.shape)} {y.dtype}")
+    B, D, L = y.shape
+    _check_mc("wpe_mc_dereverb", D, taps, delay, iterations)
+    lib = _lib.require_gpu()
+    if not y.is_cuda:
+        raise _lib.BuddyHipError("wpe_mc_dereverb: runs on the MI355X only (got a CPU tensor)")
+    yc = y.contiguous()
+    out = torch.empty_like(yc)
+    work = torch.empty(int(lib.buddy_wpe_mc_workspace_bytes(B, D, L)) // 8, dtype=torch.float64, device=y.device)
+    _lib.check(lib.buddy_wpe_mc_dereverb(_lib.ptr(yc), _lib.ptr(out), _lib.ptr(work), B, D, L, taps, delay, iterations, _lib.stream_ptr()))
     return out

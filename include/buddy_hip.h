@@ -469,6 +469,20 @@ int buddy_wpe(const double* Y, double* X, double* scratch, int rows, int T, int 
 long long buddy_wpe_workspace_bytes(int B, int L);
 int buddy_wpe_dereverb(const float* y, float* out, void* workspace, int B, int L, int taps, int delay, int iterations, void* stream);
 
+/* ---- multichannel WPE (oracle/wpe_ref.py:91-120 for any channel count D; Nakatani et al. 2010, Drude et al. 2018, batch "full
+ * statistics" form): the front end for microphone-array recordings and the WPE-alone baseline.  Y, X: (rows, D, T) complex128 as interleaved
+ * doubles, one problem per row (= utterance x frequency bin); scratch: rows*T doubles.  Per problem and iteration, N = D*taps:
+ * lambda_t = max(mean_d |x_dt|^2, 1e-10 max_t), R = sum_t yt yt^H / lambda_t (N x N), P = sum_t yt y_t^H / lambda_t (N x D), G = R^-1 P by
+ * Cholesky, X = Y - G^H Yt; everything in double, fixed-order sums, a problem's bits independent of the other rows.  A pivot <= 0 (silent
+ * channel or bin) gives a zero row of G.  Shapes: 1 <= D <= 8, taps >= 1, delay >= 0, iterations >= 0, D*taps <= 96 (R and P of one problem
+ * stay in the LDS of a workgroup); anything else: BUDDY_ERR_ARG before any launch. ---- */
+int buddy_wpe_mc(const double* Y, double* X, double* scratch, int rows, int D, int T, int taps, int delay, int iterations, void* stream);
+/* y (B, D, L) float32 -> out (B, D, L) float32 = istft(wpe(stft(y))) with the transforms of buddy_wpe_dereverb (size 512, shift 128), every
+ * item on its own, all D channels out.  workspace: buddy_wpe_mc_workspace_bytes(B, D, L) = B * 257 * T * (32 * D + 8) bytes with T the frame
+ * count of the STFT for L samples: it grows linearly with D * L, the whole file goes in one call. */
+long long buddy_wpe_mc_workspace_bytes(int B, int D, int L);
+int buddy_wpe_mc_dereverb(const float* y, float* out, void* workspace, int B, int D, int L, int taps, int delay, int iterations, void* stream);
+
 /* ---- blind subband-filtering reverb operator, batched over U utterances; replaces testing/operators/subband_filtering.py
  * (BlindSubbandFiltering :142-351 incl. SubbandFiltering :8-136), utils/reverb_utils.py:3-23, utils/losses.py:59-64 and the
  * torch.optim.Adam loop of EulerHeunSamplerDPS.optimize_op (testing/EulerHeunSamplerDPS.py:71-113) with hand-written

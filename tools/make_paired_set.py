@@ -5,6 +5,7 @@ file, its impulse response computed on the GPU by the image-source method.
     python tools/make_paired_set.py --clean DIR --out DIR [--seed 0] [--fs 16000] [--t60 LO HI] [--dims X0 X1 Y0 Y1 Z0 Z1]
                                     [--rir-seconds S] [--max-order K] [--num N] [--reverberant]
                                     [--bands [F0 F1 ...]] [--t60-slope LO HI] [--air A0 A1 ...]
+                                    [--mics N] [--array-radius R]
 
 ``--clean`` holds ``<spk>/*.wav`` (a flat folder of wavs is the one speaker ``all``); int or float wavs of any rate, several channels averaged to
 mono; a file at another rate than ``--fs`` goes through the project's resampler.  Written under ``--out``, the layout ``VCTKTestPaired`` and with it
@@ -23,7 +24,19 @@ the folder.  The response is 1.5 x the nominal T60 long unless ``--rir-seconds``
 (``--t60-slope``), each octave band gets the Eyring coefficient of its own T60, ``--air`` adds a pressure attenuation per band in Np/m (no humidity
 model), and the band responses are combined by ``rooms.octave_bank``.  The response then is 1.5 x the longest band's T60 (or ``--rir-seconds``) plus
 the bank's delay of (Nh - 1) / 2 samples, which the loader trims with everything else before the peak; ``rooms.csv`` gains per band ``beta_<f>``,
-``eyring_T60_<f>`` and the measured ``T20_<f>`` / ``T30_<f>`` / ``acoustics_flags_<f>``.  Without ``--bands`` nothing changes."""
+``eyring_T60_<f>`` and the measured ``T20_<f>`` / ``T30_<f>`` / ``acoustics_flags_<f>``.  Without ``--bands`` nothing changes.
+
+``--mics N`` (N > 1) simulates a uniform circular microphone array of radius ``--array-radius`` (default 0.1 m, the REVERB challenge's array) around
+the room's receiver, horizontal, its orientation drawn from the file's own stream (``rooms.draw_array_angle``): microphone m sits at
+``angle + 2 pi m / N``.  ``rir/`` stays mono -- the response of microphone 0, which the paired modes read as before -- and
+
+    rir_array/<spk>/<id>.wav    all N responses as one N-channel wav, as computed (channel 0 = rir/)
+    reverberant/<spk>/<id>.wav  with --reverberant: N channels; all responses are cut at the EARLIEST peak among them and divided by the LARGEST
+                                peak, so the delays and level differences between the microphones stay (what MC-WPE and a beamformer use)
+
+``rooms.csv`` gains ``mics``, ``array_radius`` and ``array_angle``; its measured columns are microphone 0's.  Such a folder of N-channel wavs is what
+``tester.real_recordings.channels: wpe`` and ``tools/wpe.py`` take.  ``--mics`` with ``--bands`` is refused.  Without ``--mics``, or with
+``--mics 1``, nothing changes."""
 import argparse
 import os
 import sys
@@ -73,10 +86,16 @@ def main(argv=None):
     ap.add_argument("--t60-slope", type=float, nargs=2, default=(0.0, 0.3), metavar=("LO", "HI"),
                     help="with --bands: range of the slope s per octave, T60_k = T60 2^(-s log2(f_k / 1000))")
     ap.add_argument("--air", type=float, nargs="+", default=None, metavar="A", help="with --bands: pressure attenuation of the air per band [Np/m] (default: zeros)")
+    ap.add_argument("--mics", type=int, default=1, help="microphones of a uniform circular array around the receiver (default 1: the receiver itself)")
+    ap.add_argument("--array-radius", type=float, default=rooms.ARRAY_RADIUS, help="with --mics: radius of the array [m]")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
     if a.bands is None and a.air is not None:
         raise SystemExit("make_paired_set: --air needs --bands")
+    if a.mics < 1:
+        raise SystemExit("make_paired_set: --mics takes a count >= 1")
+    if a.mics > 1 and a.bands is not None:
+        raise SystemExit("make_paired_set: --mics with --bands is not supported (banded rooms are simulated for one receiver)")
     files = list_clean(a.clean)
     if a.num > 0:
         files = files[:a.num]
@@ -107,9 +126,22 @@ def main(argv=None):
         nominal = rooms.eyring_t60(rm[0:3], rm[9:15], rm[15])
         if a.bands is None:
             n = int(round((a.rir_seconds if a.rir_seconds is not None else 1.5 * nominal) * a.fs))
-            h, flags = rooms.shoebox_rir(torch.from_numpy(rm[None]).to(a.device), a.fs, n, max_order=a.max_order)
-            ac = acoustics.rir_acoustics(h, a.fs)
+            if a.mics > 1:          # an array is a.mics rows of one room; everything below that reads h[0] reads microphone 0
+                angle = rooms.draw_array_angle(a.seed, name)
+                try:
+                    rm_all = rooms.array_rows(rm, a.mics, a.array_radius, angle)
+                except ValueError as e:
+                    raise SystemExit(f"make_paired_set: {name}: {e}")
+                rm = rm_all[0]
+            else:
+                rm_all = rm[None]
+            h, flags = rooms.shoebox_rir(torch.from_numpy(np.ascontiguousarray(rm_all)).to(a.device), a.fs, n, max_order=a.max_order)
+            ac = acoustics.rir_acoustics(h[:1], a.fs)
             rows += rooms.room_rows([name], rm[None], a.fs, n, ac, flags)
+            if a.mics > 1:
+                rows[-1].update(mics=a.mics, array_radius=float(a.array_radius), array_angle=angle)
+                os.makedirs(os.path.join(a.out, "rir_array", spk), exist_ok=True)
+                wavfile.write(os.path.join(a.out, "rir_array", spk, uid + ".wav"), a.fs, np.ascontiguousarray(h.cpu().numpy().astype(np.float32).T))
         else:           # the longest band decides the length, and the bank's delay comes on top of it
             n = int(round((a.rir_seconds if a.rir_seconds is not None else 1.5 * float(band_t60[u].max())) * a.fs)) + delay
             h, flags = rooms.shoebox_rir_bands(torch.from_numpy(rm[None]).to(a.device), band_beta[u:u + 1], a.fs, n, bank, air=air, max_order=a.max_order)
@@ -118,7 +150,18 @@ def main(argv=None):
         for sub, v in (("clean", xt), ("rir", h[0])):
             os.makedirs(os.path.join(a.out, sub, spk), exist_ok=True)
             wavfile.write(os.path.join(a.out, sub, spk, uid + ".wav"), a.fs, v.cpu().numpy().astype(np.float32))
-        if a.reverberant:
+        if a.reverberant and a.mics > 1:      # one cut and one scale for all microphones: the differences between them are the array's signal
+            hc = h.cpu()
+            start = int(torch.argmax(hc.abs(), dim=1).min())
+            hc = hc[:, start:] / hc.abs().max()
+            ys = []
+            for k in hc:
+                op = RIROperator(op_hp, time_kernel_size=len(k), sample_rate=a.fs, device=a.device)
+                op.update_params(k)
+                ys.append(op.degradation(xt[None])[0].detach().cpu().numpy().astype(np.float32))
+            os.makedirs(os.path.join(a.out, "reverberant", spk), exist_ok=True)
+            wavfile.write(os.path.join(a.out, "reverberant", spk, uid + ".wav"), a.fs, np.ascontiguousarray(np.stack(ys, axis=1)))
+        elif a.reverberant:
             hc = h[0].cpu()
             k = hc[int(torch.argmax(hc.abs())):]
             k = k / k.abs().max()
