@@ -68,6 +68,10 @@ _SIGS = {
     "buddy_wpe_mc": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "buddy_wpe_mc_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     "buddy_wpe_mc_dereverb": (C.c_int, [_f32p, _f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "buddy_mpdr": (C.c_int, [_f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]),
+    "buddy_wpe_mc_mpdr_workspace_bytes": (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    "buddy_wpe_mc_mpdr_dereverb": (C.c_int, [_f32p, _f32p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double,
+                                             C.c_void_p]),
     "buddy_resample": (C.c_int, [_f32p, C.c_int, C.c_longlong, _f32p, C.c_int, C.c_int, C.c_int, _f32p, C.c_longlong, C.c_void_p]),
     "buddy_row_argmax_abs": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
     "buddy_fir_bank": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_longlong, _f32p, C.c_int, C.c_int, _f32p, C.c_longlong, C.c_void_p]),

@@ -1118,6 +1118,33 @@ int buddy_wpe_mc_dereverb(const float* y, float* out, void* workspace, int B, in
   return finish();
 }
 
+// ---- wMPDR beamformer after multichannel WPE ----
+static int mpdr_args(int D, int reference, int iterations, double loading) {
+  if (!mpdr_supported(D) || reference < 0 || reference >= D || iterations < 1 || !(loading >= 0.0) || !std::isfinite(loading)) {
+    set_error("bad beamformer arguments (1 <= D <= 8, 0 <= reference < D, iterations >= 1, loading >= 0 and finite)"); return BUDDY_ERR_ARG;
+  }
+  return BUDDY_OK;
+}
+
+int buddy_mpdr(const double* X, double* Z, double* scratch, int rows, int D, int T, int reference, int iterations, double loading, void* stream) {
+  if (!X || !Z || !scratch || rows < 1 || T < 1) { set_error("bad beamformer arguments (null pointer, rows < 1 or T < 1)"); return BUDDY_ERR_ARG; }
+  if (mpdr_args(D, reference, iterations, loading)) return BUDDY_ERR_ARG;
+  launch_mpdr(X, Z, scratch, rows, D, T, reference, iterations, loading, (hipStream_t)stream);
+  return finish();
+}
+
+long long buddy_wpe_mc_mpdr_workspace_bytes(int B, int D, int L) { return buddy_wpe_mc_workspace_bytes(B, D, L); }
+
+int buddy_wpe_mc_mpdr_dereverb(const float* y, float* out, void* workspace, int B, int D, int L, int taps, int delay, int wpe_iterations,
+                               int reference, int bf_iterations, double loading, void* stream) {
+  if (!y || !out || !workspace || B < 1 || L < 1) { set_error("bad multichannel wpe arguments (null pointer, B < 1 or L < 1)"); return BUDDY_ERR_ARG; }
+  if (wpe_mc_args(D, taps, delay, wpe_iterations) || mpdr_args(D, reference, bf_iterations, loading)) return BUDDY_ERR_ARG;
+  if (launch_wpe_mc_mpdr_dereverb(y, out, workspace, B, D, L, taps, delay, wpe_iterations, reference, bf_iterations, loading, (hipStream_t)stream)) {
+    set_error("multichannel wpe: LDS request refused"); return BUDDY_ERR_HIP;
+  }
+  return finish();
+}
+
 // ---- WPE warm start ----
 int buddy_wpe(const double* Y, double* X, double* scratch, int rows, int T, int taps, int delay, int iterations, void* stream) {
   if (!Y || !X || !scratch || rows < 1 || T < 1 || taps < 1 || taps > 56 || delay < 0 || iterations < 0) { set_error("bad wpe arguments (taps <= 56)"); return BUDDY_ERR_ARG; }

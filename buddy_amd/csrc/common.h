@@ -181,6 +181,13 @@ bool wpe_mc_supported(int D, int taps);
 int launch_wpe_mc(const double* Y, double* X, double* scratch, int rows, int D, int T, int taps, int delay, int iters, hipStream_t st);
 size_t wpe_mc_workspace_bytes(int B, int D, int L);
 int launch_wpe_mc_dereverb(const float* y, float* out, void* work, int B, int D, int L, int taps, int delay, int iters, hipStream_t st);
+// the pieces of launch_wpe_mc_dereverb for the fused WPE + beamformer entry (mpdr.hip): the (B * D, 257, T) layout, Fq = 257
+int launch_wpe_mc_rows(const double* Y, double* X, double* scratch, int rows, int Fq, int D, int T, int taps, int delay, int iters, hipStream_t st);
+// wMPDR beamformer (mpdr.hip): one problem per row = D channels x T frames -> one channel; X (rows, D, T), Z (rows, T) complex128, scratch rows*T doubles
+bool mpdr_supported(int D);
+void launch_mpdr(const double* X, double* Z, double* scratch, int rows, int D, int T, int reference, int iters, double loading, hipStream_t st);
+int launch_wpe_mc_mpdr_dereverb(const float* y, float* out, void* work, int B, int D, int L, int taps, int delay, int wpe_iters, int reference,
+                                int bf_iters, double loading, hipStream_t st);
 // rational polyphase resampler (resample.hip): y[b][n] = sum_m x[b][m] h[n*down - m*up + (Nh-1)/2], Lout = ceil(Lin*up/down); arguments checked by the C entry
 long long resample_tiles(long long Lout);
 void launch_resample(const float* x, int B, long long Lin, const float* h, int Nh, int up, int down, float* y, long long Lout, hipStream_t st);

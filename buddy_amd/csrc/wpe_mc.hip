@@ -235,7 +235,11 @@ int launch_wpe_mc(const double* Y, double* X, double* scratch, int rows, int D, 
   return launch_mc(reinterpret_cast<const cd*>(Y), reinterpret_cast<cd*>(X), scratch, rows, 1, D, T, taps, delay, iters, st);
 }
 
-size_t wpe_mc_workspace_bytes(int B, int D, int L) {          // Y, X: (B * D, 257, T) complex128; power: (B * 257, T) doubles
+int launch_wpe_mc_rows(const double* Y, double* X, double* scratch, int rows, int Fq, int D, int T, int taps, int delay, int iters, hipStream_t st) {
+  return launch_mc(reinterpret_cast<const cd*>(Y), reinterpret_cast<cd*>(X), scratch, rows, Fq, D, T, taps, delay, iters, st);
+}
+
+size_t wpe_mc_workspace_bytes(int B, int D, int L) {         // Y, X: (B * D, 257, T) complex128; power: (B * 257, T) doubles
   const size_t T = (size_t)wpe_frames(L);
   return (size_t)B * MC_WF * T * (2 * (size_t)D * sizeof(cd) + sizeof(double));
 }

@@ -45,6 +45,18 @@ def channel_options(rr):
     return mode, ref, (int(hp.get("taps", 10)), int(hp.get("delay", 3)), int(hp.get("iterations", 3)))
 
 
+def beamformer_options(rr):
+    """(use, iterations, loading) of the ``beamformer`` block of a ``real_recordings`` block; a config written before the block existed means
+    (False, 2, 1e-6).  use: the wMPDR beamformer after multichannel WPE (utils/wpe.py); it needs ``channels: wpe``."""
+    bf = rr.get("beamformer", None) or {}
+    use, iterations, loading = bool(bf.get("use", False)), int(bf.get("iterations", 2)), float(bf.get("loading", 1e-6))
+    assert iterations >= 1, "real_recordings.beamformer.iterations is >= 1"
+    assert 0.0 <= loading < float("inf"), "real_recordings.beamformer.loading is finite and >= 0"
+    mode = str(rr.get("channels", "mean"))
+    assert not use or mode == "wpe", f"real_recordings.beamformer.use needs real_recordings.channels: wpe (it is '{mode}'): the beamformer works on the WPE output of all channels"
+    return use, iterations, loading
+
+
 def rir_report_options(tester_cfg):
     """(use, octave centres) of the ``rir_report`` block of a tester config; a config written before the block existed means (False, the octaves)"""
     from ..utils.acoustics import OCTAVES
@@ -447,13 +459,14 @@ class Tester:
         files = []
         levels = []    # level=active: one line of levels.csv per file
         ch_mode, ref_ch, wpe_hp = channel_options(rr)
+        bf_use, bf_iterations, bf_loading = beamformer_options(rr)      # use: true without channels: wpe stops here, before anything is sampled
         for i in range(self.rank, len(self.test_set), self.world_size):
             recorded = None      # channels != mean: the reference channel as recorded, at the model's rate (y is then what the sampler observes)
             if ch_mode == "mean":
                 audio, fs, filename = self.test_set[i]
                 y = resample(torch.from_numpy(np.asarray(audio)).float().to(self.device), fs, sr)
             else:
-                y, recorded, audio, fs, filename = self._observed_channel(i, ch_mode, ref_ch, wpe_hp, sr)
+                y, recorded, audio, fs, filename = self._observed_channel(i, ch_mode, ref_ch, wpe_hp, sr, (bf_iterations, bf_loading) if bf_use else None)
                 if y is None:
                     self.skipped.append(filename)
                     continue
@@ -538,12 +551,13 @@ class Tester:
         if srmr_on:
             self._write_srmr_report(mode, heard)
 
-    def _observed_channel(self, i, ch_mode, ref_ch, wpe_hp, sr):
+    def _observed_channel(self, i, ch_mode, ref_ch, wpe_hp, sr, bf_hp=None):
         """file ``i`` read with its channels unmixed (``real_recordings.channels: reference | wpe``) -> (observed signal, reference channel as
         recorded, the reference channel at the file's rate, fs, filename), the first two at the model's rate on the GPU; the observed signal is
         None for a file to skip.  wpe: ALL channels through one ``wpe_mc_dereverb`` call (B = 1, the whole file), the reference channel of the
         result observed; a mono file is D = 1 through the same entry.  A file the entry cannot take is skipped; a file with fewer frames than
-        D * taps + delay (R rank-deficient) is processed as ``reference``."""
+        D * taps + delay (R rank-deficient) is processed as ``reference``.  ``bf_hp`` = (iterations, loading): the wMPDR beamformer towards the
+        reference channel follows the WPE in the same library call (``wpe_mc_mpdr_dereverb``) and its one output is what is observed."""
         from ..utils import wpe as W
         from ..utils.resample import resample
         chans, fs, filename = self.test_set.channels(i)
@@ -564,6 +578,10 @@ class Tester:
         if W.frames(ya.shape[1]) < C * taps + delay:
             print(f"{filename}: {W.frames(ya.shape[1])} frames, fewer than channels x taps + delay = {C * taps + delay}: processed as its reference channel, without WPE")
             return recorded, recorded, chans[ref_ch], fs, filename
+        if bf_hp is not None:
+            y = W.wpe_mc_mpdr_dereverb(ya[None].contiguous(), taps=taps, delay=delay, iterations=iterations, reference=ref_ch, bf_iterations=bf_hp[0],
+                                       loading=bf_hp[1])[0]
+            return y, recorded, chans[ref_ch], fs, filename
         y = W.wpe_mc_dereverb(ya[None].contiguous(), taps=taps, delay=delay, iterations=iterations)[0, ref_ch]
         return y, recorded, chans[ref_ch], fs, filename
 
@@ -616,7 +634,7 @@ class Tester:
             if mode == "real_blind_dereverberation":         # no clean signal, no true RIR
                 subs = ["degraded", "reconstructed", "estimated_rir"]
                 if channel_options(self.args.tester.get("real_recordings", None) or {})[0] == "wpe":
-                    subs.append("wpe")              # what the sampler observed: the reference channel after multichannel WPE
+                    subs.append("wpe")              # what the sampler observed: the reference channel after multichannel WPE, or the beamformer's output
             elif "dereverberation" in mode:
                 subs.append("true_rir")
                 if mode == "blind_dereverberation":

@@ -14,7 +14,11 @@ Multichannel WPE (``wpe_mc_hip``, ``wpe_mc_dereverb``; ``csrc/wpe_mc.hip``) is t
 as written for any D: the front end of the real-recordings mode for microphone-array files (``tester.real_recordings.channels: wpe``) and the
 WPE-alone baseline of the reports (``tools/wpe.py``).  Its defaults are nara_wpe's (taps 10, delay 3, 3 iterations).  Parity with nara_wpe
 itself is unpinned for D > 1 as for D = 1, and whether the cascade WPE -> BUDDy scores better than the channel mean on a trained checkpoint is
-UNMEASURED: there is no trained checkpoint here."""
+UNMEASURED: there is no trained checkpoint here.
+
+The wMPDR beamformer (``mpdr_hip``, ``wpe_mc_mpdr_dereverb``; ``csrc/mpdr.hip``) turns the D WPE outputs into one channel:
+steering vector from the bin's covariance, weights that minimise the power weighted by 1 / |z_t|^2 under a distortionless constraint towards
+the reference channel.  ``real_recordings.beamformer.use`` and ``tools/wpe.py --beamformer wmpdr`` reach it through the fused entry."""
 from __future__ import annotations
 
 import torch
@@ -110,4 +114,56 @@ def wpe_mc_dereverb(y, taps=10, delay=3, iterations=3):
     out = torch.empty_like(yc)
     work = torch.empty(int(lib.buddy_wpe_mc_workspace_bytes(B, D, L)) // 8, dtype=torch.float64, device=y.device)
     _lib.check(lib.buddy_wpe_mc_dereverb(_lib.ptr(yc), _lib.ptr(out), _lib.ptr(work), B, D, L, taps, delay, iterations, _lib.stream_ptr()))
+    return out
+
+
+# ---------------------------------------------------------------------------- wMPDR beamformer after multichannel WPE (csrc/mpdr.hip)
+def _check_bf(name, D, reference, iterations, loading):
+    if not 1 <= D <= MAX_CHANNELS:
+        raise ValueError(f"{name}: {D} channels; the kernel takes 1 to {MAX_CHANNELS}")
+    if not 0 <= reference < D:
+        raise ValueError(f"{name}: reference channel {reference} of {D}")
+    if iterations < 1:
+        raise ValueError(f"{name}: the beamformer needs iterations >= 1 (got {iterations})")
+    if not (loading >= 0.0 and loading != float("inf")):
+        raise ValueError(f"{name}: loading must be finite and >= 0 (got {loading})")
+
+
+def mpdr_hip(X, reference=0, iterations=2, loading=1e-6):
+    """The wMPDR beamformer alone (``buddy_mpdr``): X (F, D, T) complex128 on the GPU -> (F, T); every row a problem of
+    its own.  The steering vector is the principal eigenvector of sum_t x x^H relative to ``reference``; ``loading`` (relative diagonal
+    loading of the weighted covariance) defaults to 1e-6, a choice and not a measurement."""
+    reference, iterations, loading = int(reference), int(iterations), float(loading)
+    if X.dim() != 3 or X.dtype != torch.complex128 or X.shape[0] < 1 or X.shape[2] < 1:
+        raise ValueError(f"mpdr_hip: X must be (F, D, T) complex128, got {tuple(X.shape)} {X.dtype}")
+    F, D, T = X.shape
+    _check_bf("mpdr_hip", D, reference, iterations, loading)
+    lib = _lib.require_gpu()
+    if not X.is_cuda:
+        raise _lib.BuddyHipError("mpdr_hip: runs on the MI355X only (got a CPU tensor)")
+    Xr = torch.view_as_real(X.contiguous()).contiguous()                    # (F, D, T, 2) float64
+    Zr = torch.empty(F, T, 2, dtype=torch.float64, device=X.device)
+    scratch = torch.empty(F * T, dtype=torch.float64, device=X.device)
+    _lib.check(lib.buddy_mpdr(_lib.ptr(Xr), _lib.ptr(Zr), _lib.ptr(scratch), F, D, T, reference, iterations, loading, _lib.stream_ptr()))
+    return torch.view_as_complex(Zr)
+
+
+def wpe_mc_mpdr_dereverb(y, taps=10, delay=3, iterations=3, reference=0, bf_iterations=2, loading=1e-6):
+    """y (B, D, L) float32 on the GPU -> (B, L) float32: stft -> D-channel WPE (the kernel and the bits of ``wpe_mc_dereverb``) -> wMPDR
+    beamformer towards ``reference`` -> istft, one library call in the workspace of ``wpe_mc_dereverb``."""
+    taps, delay, iterations = int(taps), int(delay), int(iterations)
+    reference, bf_iterations, loading = int(reference), int(bf_iterations), float(loading)
+    if y.dim() != 3 or y.shape[0] < 1 or y.shape[2] < 1 or y.dtype != torch.float32:
+        raise ValueError(f"wpe_mc_mpdr_dereverb: y must be (B, D, L) float32, got {tuple(y.shape)} {y.dtype}")
+    B, D, L = y.shape
+    _check_mc("wpe_mc_mpdr_dereverb", D, taps, delay, iterations)
+    _check_bf("wpe_mc_mpdr_dereverb", D, reference, bf_iterations, loading)
+    lib = _lib.require_gpu()
+    if not y.is_cuda:
+        raise _lib.BuddyHipError("wpe_mc_mpdr_dereverb: runs on the MI355X only (got a CPU tensor)")
+    yc = y.contiguous()
+    out = torch.empty(B, L, dtype=torch.float32, device=y.device)
+    work = torch.empty(int(lib.buddy_wpe_mc_mpdr_workspace_bytes(B, D, L)) // 8, dtype=torch.float64, device=y.device)
+    _lib.check(lib.buddy_wpe_mc_mpdr_dereverb(_lib.ptr(yc), _lib.ptr(out), _lib.ptr(work), B, D, L, taps, delay, iterations, reference, bf_iterations,
+                                              loading, _lib.stream_ptr()))
     return out

@@ -483,6 +483,23 @@ int buddy_wpe_mc(const double* Y, double* X, double* scratch, int rows, int D, i
 long long buddy_wpe_mc_workspace_bytes(int B, int D, int L);
 int buddy_wpe_mc_dereverb(const float* y, float* out, void* workspace, int B, int D, int L, int taps, int delay, int iterations, void* stream);
 
+/* ---- wMPDR beamformer after multichannel WPE (weighted-power minimisation distortionless response; with the WPE weights reused the factorised
+ * form of Nakatani & Kinoshita's convolutional beamformer, 2019/2020).  X: (rows, D, T) complex128 as interleaved doubles,
+ * Z: (rows, T), one problem per row (= item x frequency bin); scratch: rows*T doubles.  Per problem: Phi = sum_t x x^H; its principal
+ * eigenvector by TEN normalised squarings (A <- A / max|A_ij|, A <- A A, A <- (A + A^H) / 2), v = A[:, reference] / A[reference][reference];
+ * then `iterations` times lambda_t = max(p_t, 1e-10 max_t p_t) with p_t = mean_d |x_dt|^2 first and |z_t|^2 afterwards,
+ * R = sum_t x x^H / lambda_t + loading * tr(R) / D * I, u = R^-1 v by Cholesky, w = u / (v^H u), z_t = w^H x_t.  Pass-through z = x_reference
+ * where Phi is zero, |v_r|^2 < 1e-12 |v|^2 (or v_r = 0), a pivot is <= 0 or v^H u is 0 or not finite; z = 0 where max_t p_t = 0; D = 1 copies.
+ * Everything in double, fixed-order sums, a problem's bits independent of the other rows.  1 <= D <= 8, 0 <= reference < D, iterations >= 1,
+ * loading >= 0 and finite, rows >= 1, T >= 1; anything else: BUDDY_ERR_ARG before any launch. ---- */
+int buddy_mpdr(const double* X, double* Z, double* scratch, int rows, int D, int T, int reference, int iterations, double loading, void* stream);
+/* y (B, D, L) float32 -> out (B, L) float32 = istft(mpdr(wpe(stft(y)))): the transforms and the WPE kernel of buddy_wpe_mc_dereverb (the same
+ * bits), then the beamformer, one channel out.  workspace: buddy_wpe_mc_mpdr_workspace_bytes(B, D, L) = buddy_wpe_mc_workspace_bytes(B, D, L)
+ * (the beamformer's output takes the place of the observed spectra, which are no longer needed by then). */
+long long buddy_wpe_mc_mpdr_workspace_bytes(int B, int D, int L);
+int buddy_wpe_mc_mpdr_dereverb(const float* y, float* out, void* workspace, int B, int D, int L, int taps, int delay, int wpe_iterations,
+                               int reference, int bf_iterations, double loading, void* stream);
+
 /* ---- blind subband-filtering reverb operator, batched over U utterances; replaces testing/operators/subband_filtering.py
  * (BlindSubbandFiltering :142-351 incl. SubbandFiltering :8-136), utils/reverb_utils.py:3-23, utils/losses.py:59-64 and the
  * torch.optim.Adam loop of EulerHeunSamplerDPS.optimize_op (testing/EulerHeunSamplerDPS.py:71-113) with hand-written
