@@ -217,6 +217,10 @@ _SIGS = {
     "buddy_perturb": (C.c_int, [_f32p, _f32p, C.c_float, _f32p, C.c_longlong, C.c_void_p]),
     "buddy_philox_fill": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint, C.c_uint, C.c_int, C.c_void_p]),
     "buddy_perturb_philox": (C.c_int, [_f32p, C.c_void_p, C.c_uint, C.c_float, _f32p, C.c_int, C.c_int, C.c_void_p]),
+    "buddy_noise_tile": (C.c_int, []),
+    "buddy_noise_max_taps": (C.c_int, []),
+    "buddy_noise_bank": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong,
+                                   C.c_double, C.c_void_p]),
     "buddy_dps_update": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_float, C.c_float, C.c_float, C.c_float, _f32p, _f32p, _f32p,
                                    C.c_int, C.c_int, C.c_void_p]),
     "buddy_row_scale": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),

@@ -856,6 +856,25 @@ int buddy_shoebox_bands(const double* rooms, const double* beta, const double* a
                         double* u /* (B, nb, ldu) */, long long ldu, int* flags, void* stream);
 int buddy_band_combine(const double* u, int B, int nb, long long ldu, int N, const double* bank /* (nb, Nh) */, int Nh, float* h, long long ldh, void* stream);
 
+/* ---- diffuse noise fields by plane-wave superposition (buddy_amd/utils/noise.py, csrc/noise.hip; Habets & Gannot 2007; no
+ * reference counterpart).  Item b of a call is one file: D microphones, N white plane waves, L output samples.  Wave n of item b is the source
+ *   s_{b,n}[j], j = 0 .. L + 2 P - 1 = the kind-0 normals of buddy_philox_fill for (keys[b], purpose, draw0 + n, j), bit for bit,
+ * generated inside the kernel and never stored.  taps: DEVICE (B, N, D, W) doubles, first: DEVICE (B, N, D) ints -- per (wave, microphone) the W
+ * zero-padded coefficients of its fractional-delay filter and the integer lag of the first one; keys: DEVICE (B, 2) uint32; out: DEVICE (B, D, L) fp32.
+ *   out[b][d][i] = scale * sum_n sum_k taps[b][n][d][k] * s_{b,n}[i + P - first[b][n][d] - k],  i = 0 .. L - 1,
+ * where a source index outside [0, L + 2 P) contributes zero: that is the definition, so no `first` can make the kernel read out of bounds (a
+ * `first` whose filters leave the range is the caller's mistake all the same, and noise.noise_bank_hip refuses it before uploading).  The sum is
+ * accumulated in double in the fixed order n ascending, then k ascending, multiplied by scale and rounded once to fp32.  No atomics; a row's bits
+ * depend on its own key, taps and first only -- not on B, the grid or the run.  One path serves every L >= 1.
+ * BUDDY_ERR_ARG, with nothing launched, for: a null pointer; D outside 1..8; N outside 1..4096; W outside 1..buddy_noise_max_taps() = 80; P outside
+ * 0..4096; B outside 1..65535; L outside 1..2^33 (a draw's sample index has 34 bits); a scale that is not finite.  Nothing is written outside out;
+ * no workspace.  Work: B L N D W multiply-adds in double plus N (T + 2 P) / T normals per output sample, T = buddy_noise_tile() = 256 output
+ * samples per workgroup (the size around which the unit tests place their lengths). */
+int buddy_noise_tile(void);
+int buddy_noise_max_taps(void);
+int buddy_noise_bank(const double* taps /* (B,N,D,W) */, const int* first /* (B,N,D) */, const unsigned* keys /* (B,2) */, unsigned purpose, unsigned draw0,
+                     float* out /* (B,D,L) */, int B, int D, int N, int W, int P, long long L, double scale, void* stream);
+
 /* ---- the small fp32 kernels of the network, one entry per launcher (unit tests: tests/test_hip_small_ops.py).  All tensors NHWC with H = time, device
  * pointers, fp32.  Each entry returns BUDDY_ERR_ARG with a message, with nothing launched, for a null required pointer, an empty shape, or a shape its
  * kernels cannot compute (named per entry).

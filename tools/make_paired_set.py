@@ -6,6 +6,8 @@ file, its impulse response computed on the GPU by the image-source method.
                                     [--rir-seconds S] [--max-order K] [--num N] [--reverberant]
                                     [--bands [F0 F1 ...]] [--t60-slope LO HI] [--air A0 A1 ...]
                                     [--mics N] [--array-radius R]
+                                    [--snr LO HI] [--snr-reference rms|active] [--noise-field spherical|cylindrical] [--noise-waves N]
+                                    [--noise-tilt DB] [--sensor-snr DB]
 
 ``--clean`` holds ``<spk>/*.wav`` (a flat folder of wavs is the one speaker ``all``); int or float wavs of any rate, several channels averaged to
 mono; a file at another rate than ``--fs`` goes through the project's resampler.  Written under ``--out``, the layout ``VCTKTestPaired`` and with it
@@ -36,7 +38,20 @@ the room's receiver, horizontal, its orientation drawn from the file's own strea
 
 ``rooms.csv`` gains ``mics``, ``array_radius`` and ``array_angle``; its measured columns are microphone 0's.  Such a folder of N-channel wavs is what
 ``tester.real_recordings.channels: wpe`` and ``tools/wpe.py`` take.  ``--mics`` with ``--bands`` is refused.  Without ``--mics``, or with
-``--mics 1``, nothing changes."""
+``--mics 1``, nothing changes.
+
+``--snr LO HI`` (with ``--reverberant``) adds noise to the reverberant files (``buddy_amd/utils/noise.py``): a diffuse field at
+the array's microphones (``--noise-field``, ``--noise-waves`` plane waves, default 512; one microphone takes 1, because a sum of independent normals
+is a normal), white or tilted by ``--noise-tilt`` dB per octave (-3: pink), and with ``--sensor-snr DB`` independent white noise per microphone at
+that speech-to-sensor-noise ratio.  A file's SNR is uniform in dB in LO..HI, drawn from the file's own stream, and is the power of the reverberant
+speech of channel 0 (``--snr-reference active``: its ITU-T P.56 active power) over the power of ALL the noise of channel 0.  Then
+
+    reverberant/<spk>/<id>.wav  speech plus noise
+    noise/<spk>/<id>.wav        the scaled noise alone, same channels: reverberant - noise is the noiseless file
+
+and ``rooms.csv`` gains ``snr_db``, ``snr_reference`` (as used), ``snr_measured_db`` (recomputed in double from the two arrays as written),
+``noise_gain_diffuse``, ``noise_gain_sensor`` and ``noise_flags``.  The noise is a function of the seed, the name, the geometry and these flags, so
+the same call reproduces every file byte for byte.  ``--snr`` with ``--bands`` is refused.  Without ``--snr`` and ``--sensor-snr`` nothing changes."""
 import argparse
 import os
 import sys
@@ -47,7 +62,7 @@ from scipy.io import wavfile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from buddy_amd.datasets.vctk import _read  # noqa: E402
-from buddy_amd.utils import acoustics, resample, rooms  # noqa: E402
+from buddy_amd.utils import acoustics, noise, resample, rng, rooms  # noqa: E402
 
 
 def read_wav(path):
@@ -69,6 +84,44 @@ def list_clean(base):
     return out
 
 
+def add_noise(a, name, y, angle):
+    """y (D, L) float32, the reverberant microphone signals of one file -> (y + noise, noise, the file's columns of rooms.csv)"""
+    D, L = y.shape
+    key = np.array([rng.stream_key(a.seed, name)], dtype=np.uint32)
+    yt = torch.from_numpy(np.ascontiguousarray(y))[None].to(a.device)
+    diffuse = sensor = None
+    snr = float("nan")
+    if a.snr is not None:
+        snr = a.snr[0] + float(rng.uniforms(key[0], noise.NOISE_DRAWS, 0, 1)[0]) * (a.snr[1] - a.snr[0])
+        phi = angle + 2.0 * np.pi * np.arange(D) / D
+        pos = np.stack([a.array_radius * np.cos(phi), a.array_radius * np.sin(phi), np.zeros(D)], axis=1) if D > 1 else np.zeros((1, 3))
+        try:
+            diffuse = noise.diffuse_noise(pos, key, L, a.fs, waves=a.noise_waves if D > 1 else 1, field=a.noise_field, tilt=a.noise_tilt)
+        except ValueError as e:
+            raise SystemExit(f"make_paired_set: {name}: {e}")
+    if a.sensor_snr is not None:
+        sensor = noise.sensor_noise(key, D, L)
+    m = noise.mix_at_snr(yt, diffuse, sensor, snr, a.sensor_snr, a.fs, reference=a.snr_reference)
+    mixed, nz = m.mixed[0].cpu().numpy(), m.noise[0].cpu().numpy()
+    pn = float(np.sum(nz[0].astype(np.float64) ** 2))
+    ps = float(np.sum((mixed[0].astype(np.float64) - nz[0].astype(np.float64)) ** 2)) if m.reference[0] == "rms" else float(m.speech_power[0]) * L
+    cols = dict(snr_db=snr if a.snr is not None else float(a.sensor_snr), snr_reference=m.reference[0], snr_measured_db=10.0 * np.log10(ps / pn),
+                noise_gain_diffuse=float(m.gain_diffuse[0]), noise_gain_sensor=float(m.gain_sensor[0]), noise_flags=m.flags[0])
+    return mixed, nz, cols
+
+
+def write_reverberant(a, spk, uid, name, y, angle, row):
+    """y (D, L) float32 -> reverberant/<spk>/<id>.wav (mono for D = 1), with the noise flags also noise/<spk>/<id>.wav and the row's noise columns"""
+    out = [("reverberant", y)]
+    if a.snr is not None or a.sensor_snr is not None:
+        mixed, nz, cols = add_noise(a, name, y, angle)
+        row.update(cols)
+        out = [("reverberant", mixed), ("noise", nz)]
+    for sub, v in out:
+        os.makedirs(os.path.join(a.out, sub, spk), exist_ok=True)
+        wavfile.write(os.path.join(a.out, sub, spk, uid + ".wav"), a.fs, np.ascontiguousarray(v.T) if len(v) > 1 else v[0])
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--clean", required=True, help="folder of <spk>/*.wav (or of wavs)")
@@ -88,8 +141,25 @@ def main(argv=None):
     ap.add_argument("--air", type=float, nargs="+", default=None, metavar="A", help="with --bands: pressure attenuation of the air per band [Np/m] (default: zeros)")
     ap.add_argument("--mics", type=int, default=1, help="microphones of a uniform circular array around the receiver (default 1: the receiver itself)")
     ap.add_argument("--array-radius", type=float, default=rooms.ARRAY_RADIUS, help="with --mics: radius of the array [m]")
+    ap.add_argument("--snr", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="with --reverberant: add noise at a per-file SNR uniform in LO..HI dB")
+    ap.add_argument("--snr-reference", choices=("rms", "active"), default="rms", help="the speech power of an SNR: mean square, or ITU-T P.56 active power")
+    ap.add_argument("--noise-field", choices=("spherical", "cylindrical"), default="spherical")
+    ap.add_argument("--noise-waves", type=int, default=512, help="plane waves of the diffuse field (one microphone: 1)")
+    ap.add_argument("--noise-tilt", type=float, default=0.0, help="spectral tilt of the diffuse noise [dB per octave] (0 white, -3 pink)")
+    ap.add_argument("--sensor-snr", type=float, default=None, metavar="DB", help="with --reverberant: independent white noise per microphone at this SNR")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
+    noisy = a.snr is not None or a.sensor_snr is not None
+    if noisy and not a.reverberant:
+        raise SystemExit("make_paired_set: --snr / --sensor-snr needs --reverberant (the noise is added to the reverberant files)")
+    if noisy and a.bands is not None:
+        raise SystemExit("make_paired_set: --snr / --sensor-snr with --bands is not supported")
+    if a.snr is not None and not a.snr[0] <= a.snr[1]:
+        raise SystemExit("make_paired_set: --snr takes LO <= HI")
+    if a.snr is not None and not 1 <= a.noise_waves <= 4096:
+        raise SystemExit("make_paired_set: --noise-waves takes a count in 1..4096")
+    if a.snr is not None and a.sensor_snr is not None and not a.sensor_snr > a.snr[1]:
+        raise SystemExit("make_paired_set: --sensor-snr must lie above --snr HI (the SNR counts all the noise, the sensors' included)")
     if a.bands is None and a.air is not None:
         raise SystemExit("make_paired_set: --air needs --bands")
     if a.mics < 1:
@@ -159,8 +229,7 @@ def main(argv=None):
                 op = RIROperator(op_hp, time_kernel_size=len(k), sample_rate=a.fs, device=a.device)
                 op.update_params(k)
                 ys.append(op.degradation(xt[None])[0].detach().cpu().numpy().astype(np.float32))
-            os.makedirs(os.path.join(a.out, "reverberant", spk), exist_ok=True)
-            wavfile.write(os.path.join(a.out, "reverberant", spk, uid + ".wav"), a.fs, np.ascontiguousarray(np.stack(ys, axis=1)))
+            write_reverberant(a, spk, uid, name, np.stack(ys), angle, rows[-1])
         elif a.reverberant:
             hc = h[0].cpu()
             k = hc[int(torch.argmax(hc.abs())):]
@@ -168,8 +237,7 @@ def main(argv=None):
             op = RIROperator(op_hp, time_kernel_size=len(k), sample_rate=a.fs, device=a.device)
             op.update_params(k)
             y = op.degradation(xt[None])[0]
-            os.makedirs(os.path.join(a.out, "reverberant", spk), exist_ok=True)
-            wavfile.write(os.path.join(a.out, "reverberant", spk, uid + ".wav"), a.fs, y.detach().cpu().numpy().astype(np.float32))
+            write_reverberant(a, spk, uid, name, y.detach().cpu().numpy().astype(np.float32)[None], 0.0, rows[-1])
         print(f"{name}: {rm[0]:.2f} x {rm[1]:.2f} x {rm[2]:.2f} m, nominal T60 {nominal:.3f} s, {n} samples, measured T20 {rows[-1]['T20']:.3f} s")
     rooms.write_rooms(os.path.join(a.out, "rooms.csv"), rows)
     print(os.path.join(a.out, "rooms.csv"))
