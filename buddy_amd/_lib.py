@@ -221,6 +221,12 @@ _SIGS = {
     "buddy_noise_max_taps": (C.c_int, []),
     "buddy_noise_bank": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong,
                                    C.c_double, C.c_void_p]),
+    "buddy_denoise_frames": (C.c_longlong, [C.c_longlong]),
+    "buddy_denoise_spectra": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_longlong, _f32p, C.c_longlong, C.c_void_p]),
+    "buddy_denoise_gains": (C.c_int, [_f32p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_double, _f32p, _f32p, C.c_void_p]),
+    "buddy_denoise_synthesis_workspace": (C.c_longlong, [C.c_int, C.c_longlong]),
+    "buddy_denoise_synthesis": (C.c_int, [_f32p, _f32p, C.c_void_p, C.c_int, C.c_longlong, _f32p, C.c_longlong, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "buddy_denoise_stats": (C.c_int, [_f32p, _f32p, C.c_void_p, C.c_int, C.c_longlong, _f32p, _f32p, C.c_longlong, C.c_void_p, C.c_void_p]),
     "buddy_dps_update": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_float, C.c_float, C.c_float, C.c_float, _f32p, _f32p, _f32p,
                                    C.c_int, C.c_int, C.c_void_p]),
     "buddy_row_scale": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),

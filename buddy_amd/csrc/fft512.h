@@ -39,6 +39,34 @@ __device__ __forceinline__ void frame_load(FftLds& s, int wv, int lane, const fl
   }
 }
 
+// the windowed frame of 512 samples row[start .. start + 511] of a row of len samples, zeros where the index leaves [0, len), into buffer 0 of wave
+// wv (denoise.hip: frames that overhang both ends of the row; the tables must have been made for frame = 512).  live = false: zeros
+__device__ __forceinline__ void frame_load_clipped(FftLds& s, int wv, int lane, const float* row, long long start, long long len, bool live) {
+#pragma unroll
+  for (int i = 0; i < FFT_N / 64; ++i) {
+    const int n = lane + 64 * i;
+    const long long j = start + n;
+    s.buf[wv][0][n] = make_float2(live && j >= 0 && j < len ? __fmul_rn(s.win[n], row[j]) : 0.f, 0.f);
+  }
+}
+
+// the conjugate of the Hermitian spectrum Z[k] = g[k] Y[k], k = 0..256, Z[512 - k] = conj(Z[k]), into buffer 0 of wave wv: frame_fft of it is
+// 512 conj(z), z the inverse transform of Z, so Re(result) / 512 is the real signal (the imaginary parts of bins 0 and 256 fall out of the real part,
+// as in any real inverse transform).  Each product is one fp32 multiplication.  Y, g null: zeros
+__device__ __forceinline__ void spectrum_load_hermitian(FftLds& s, int wv, int lane, const float2* Y, const float* g) {
+#pragma unroll
+  for (int i = 0; i < FFT_N / 64; ++i) {
+    const int n = lane + 64 * i, k = n <= FFT_N / 2 ? n : FFT_N - n;     // every lane writes its own eight points
+    float2 v = make_float2(0.f, 0.f);
+    if (Y) {
+      const float2 y = Y[k];
+      const float re = __fmul_rn(g[k], y.x), im = __fmul_rn(g[k], y.y);
+      v = make_float2(re, n <= FFT_N / 2 ? -im : im);
+    }
+    s.buf[wv][0][n] = v;
+  }
+}
+
 // in: buffer 0 of wave wv, written by this wave.  Returns the buffer that holds the spectrum in natural order (nine stages: buffer 1).  Every wave of
 // the workgroup must call it (barriers); the result may be read after it returns
 __device__ __forceinline__ const float2* frame_fft(FftLds& s, int wv, int lane) {

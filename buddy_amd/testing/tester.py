@@ -57,6 +57,17 @@ def beamformer_options(rr):
     return use, iterations, loading
 
 
+def denoise_options(rr):
+    """(use, gain, floor_db) of the ``denoise`` block of a ``real_recordings`` block; a config written before the block existed means
+    (False, "lsa", -15.0).  use: the noise tracker and spectral post-filter (utils/denoise.py) as the last stage of the front
+    end, on whatever the channel rule hands the sampler.  gain: lsa | wiener; floor_db: the lowest gain in dB, a choice."""
+    dn = rr.get("denoise", None) or {}
+    use, gain, floor_db = bool(dn.get("use", False)), str(dn.get("gain", "lsa")), float(dn.get("floor_db", -15.0))
+    assert gain in ("lsa", "wiener"), f"real_recordings.denoise.gain is 'lsa' or 'wiener' (it is '{gain}')"
+    assert -120.0 <= floor_db <= 0.0, f"real_recordings.denoise.floor_db is a gain in dB in [-120, 0] (it is {floor_db})"
+    return use, gain, floor_db
+
+
 def rir_report_options(tester_cfg):
     """(use, octave centres) of the ``rir_report`` block of a tester config; a config written before the block existed means (False, the octaves)"""
     from ..utils.acoustics import OCTAVES
@@ -437,7 +448,9 @@ class Tester:
         ALL files are sampled as one pool of independent utterances in batches of ``batch_size``; then level match, cross-fade, undo the scaling,
         resample back.  Files go to ranks by index; every rank writes its own, nothing is gathered.  ``real_recordings.shared_rir``: the chunks
         of a file are tied rows of one operator -- one RIR estimate per file, fitted to all its chunks; a batch then never splits a file
-        (``longform.pool_plan_shared``).  ``self.rirs[name]`` keeps the per-chunk RIR estimates in both modes."""
+        (``longform.pool_plan_shared``).  ``self.rirs[name]`` keeps the per-chunk RIR estimates in both modes.  ``real_recordings.denoise.use``:
+        the spectral post-filter (utils/denoise.py) follows the channel rule, once per file before the scaling; ``denoised/`` holds what the sampler
+        observed, ``denoise.csv`` one line per file, and ``degraded/`` and ``wpe/`` the bytes of the run without it."""
         from . import longform
         from ..utils.resample import resample
         if self.test_set is None or len(self.test_set) == 0:
@@ -460,6 +473,21 @@ class Tester:
         levels = []    # level=active: one line of levels.csv per file
         ch_mode, ref_ch, wpe_hp = channel_options(rr)
         bf_use, bf_iterations, bf_loading = beamformer_options(rr)      # use: true without channels: wpe stops here, before anything is sampled
+        dn_use, dn_gain, dn_floor = denoise_options(rr)
+        dn_rows = []   # denoise.use: one line of denoise.csv per file
+        if dn_use:
+            from ..utils import denoise as dnz
+
+        def plain_gain(sig):
+            """denoise.use: the gain the run WITHOUT the post-filter gives the file, from the signal in front of it -- ``degraded/`` and ``wpe/`` are
+            written with it, so they hold the bytes of that run"""
+            g = float(rr.get("gain", 1.0)) * float(ps.warm_initialization.scaling_factor) / float(sig.std())
+            if level_rule == "active":
+                m = lv.speech_level(sig[None], sr)
+                if int(m.flags[0]) == 0:
+                    g = lv.active_gain(rr.get("gain", 1.0), ps.warm_initialization.scaling_factor, float(m.active_rms[0]), ref_activity)
+            return g
+
         for i in range(self.rank, len(self.test_set), self.world_size):
             recorded = None      # channels != mean: the reference channel as recorded, at the model's rate (y is then what the sampler observes)
             if ch_mode == "mean":
@@ -470,6 +498,11 @@ class Tester:
                 if y is None:
                     self.skipped.append(filename)
                     continue
+            front = None         # denoise.use: the signal in front of the post-filter
+            if dn_use:           # the last stage of the front end: once per file, on the whole signal the sampler would observe, before the level scaling
+                front = y
+                dn_res = dnz.denoise(y[None].contiguous(), gain=dn_gain, floor_db=dn_floor)
+                y = dn_res.out[0]
             std = float(y.std()) if y.numel() > 1 else 0.0
             if y.numel() < 1024 or not std > 0.0:       # below what the HIP STFT / loss kernels take (operators/reverb.py), or digital silence
                 print(f"skipping {filename}: {y.numel()} samples at {sr} Hz" + ("" if y.numel() < 1024 else ", silent"))
@@ -486,8 +519,13 @@ class Tester:
                     g = lv.active_gain(rr.get("gain", 1.0), ps.warm_initialization.scaling_factor, float(m.active_rms[0]), ref_activity)
                 levels += lv.report_rows([os.path.basename(filename)[:-4]], m, [{"rule": rule, "g": g}])
             files.append(dict(name=os.path.basename(filename)[:-4], fs=int(fs), n_in=len(audio), y=g * y, g=g))
+            g_plain = g
+            if dn_use:
+                dn_rows += dnz.report_rows([files[-1]["name"]], dn_res)
+                g_plain = plain_gain(front)
+                files[-1]["front"] = g_plain * front
             if recorded is not None:
-                files[-1]["recorded"] = g * recorded
+                files[-1]["recorded"] = g_plain * recorded
         shared, max_rows = shared_rir_options(rr)
         lengths = [f["y"].numel() for f in files]
         if shared:
@@ -505,6 +543,9 @@ class Tester:
         self.levels = levels if level_rule == "active" else None
         if writing and level_rule == "active":
             lv.write_report(os.path.join(self.paths[mode], "levels.csv" if self.world_size == 1 else f"levels.rank{self.rank}.csv"), levels)
+        self.denoise_rows = dn_rows if dn_use else None
+        if writing and dn_use:
+            dnz.write_report(os.path.join(self.paths[mode], "denoise.csv" if self.world_size == 1 else f"denoise.rank{self.rank}.csv"), dn_rows)
         report = writing and rir_report_options(self.args.tester)[0]
         srmr_on = writing and srmr_options(self.args.tester)
         heard = []     # SRMR report: (name, degraded at the model's rate, reconstructed at its own rate, no clean signal) per written file
@@ -530,10 +571,13 @@ class Tester:
             self.results.append((f["name"], pred.detach().cpu()))
             if not writing:
                 continue
-            degraded = f.get("recorded", f["y"])      # channels != mean: the reference channel as recorded, with the file's gain
+            front = f.get("front", f["y"])            # denoise.use: the front end's output before the post-filter, with the gain of the run without it
+            degraded = f.get("recorded", front)       # channels != mean: the reference channel as recorded, with the file's gain
             write_audio_file(degraded, sr, f["name"], path=self.paths[mode + "degraded"])
-            if ch_mode == "wpe":                      # what the sampler observed
-                write_audio_file(f["y"], sr, f["name"], path=self.paths[mode + "wpe"])
+            if ch_mode == "wpe":                      # the array front end's output: what the sampler observed, unless the post-filter follows
+                write_audio_file(front, sr, f["name"], path=self.paths[mode + "wpe"])
+            if dn_use:                                # what the sampler observed
+                write_audio_file(f["y"], sr, f["name"], path=self.paths[mode + "denoised"])
             p = write_audio_file(pred, f["fs"] if to_input_rate else sr, f["name"], path=self.paths[mode + "reconstructed"])
             if srmr_on:
                 heard.append((f["name"], (degraded.detach(), sr), (pred.detach(), f["fs"] if to_input_rate else sr), None))
@@ -635,6 +679,8 @@ class Tester:
                 subs = ["degraded", "reconstructed", "estimated_rir"]
                 if channel_options(self.args.tester.get("real_recordings", None) or {})[0] == "wpe":
                     subs.append("wpe")              # what the sampler observed: the reference channel after multichannel WPE, or the beamformer's output
+                if denoise_options(self.args.tester.get("real_recordings", None) or {})[0]:
+                    subs.append("denoised")         # what the sampler observed after the spectral post-filter
             elif "dereverberation" in mode:
                 subs.append("true_rir")
                 if mode == "blind_dereverberation":

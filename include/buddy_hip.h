@@ -875,6 +875,40 @@ int buddy_noise_max_taps(void);
 int buddy_noise_bank(const double* taps /* (B,N,D,W) */, const int* first /* (B,N,D) */, const unsigned* keys /* (B,2) */, unsigned purpose, unsigned draw0,
                      float* out /* (B,D,L) */, int B, int D, int N, int W, int P, long long L, double scale, void* stream);
 
+/* ---- noise power tracker and spectral post-filter of noisy recordings (buddy_amd/utils/denoise.py, csrc/denoise.hip; Gerkmann &
+ * Hendriks 2012, Ephraim & Malah 1984 / 1985; no reference counterpart).  The conventions of the evaluation entries hold: ragged rows inside a common
+ * stride, a DEVICE length array copied to the host once to be checked, nothing behind a row's end read, nothing outside the declared extents written,
+ * fixed-order sums without atomics, a row's bits independent of its batch.  Frames are N = 512 samples at hop H = 128 and overhang both ends of the
+ * row by P = 384 samples: frames(L) = (L - 1 + P) / H + 1 = buddy_denoise_frames(L) (-1 for L outside 1..2^30), frame t covers samples
+ * t H - P .. t H - P + 511, zeros outside [0, L); every sample lies in exactly four frames.  Window w[i] = 0.5 - 0.5 cos(2 pi (i + 1) / 513).
+ * Spectra Y are (B, ldt, 257) pairs of fp32 (re, im); G and sigma2 are (B, ldt, 257) fp32; ldt >= frames of the longest row.
+ * BUDDY_ERR_ARG, with nothing launched, for: a null pointer; B outside 1..65535; a length outside 1..2^30; ld below the longest row; ldt below its
+ * frames; a gain rule other than 0 or 1; g_min outside (0, 1]; a phi[b] that is negative or not finite; a workspace below the size its query states.
+ *
+ * buddy_denoise_spectra: Y[b][t][k], k = 0..256: the 512-point transform (fp32, radix 2, the transform of buddy_frame_spectra) of the windowed frame
+ *   (w rounded to fp32, one fp32 product per sample).
+ * buddy_denoise_gains: phi: DEVICE doubles (B), the row floor (0: an all-zero row, G = 1 and sigma2 = 0 everywhere).  Per bin, frames ascending, all in
+ *   double: sigma^2 starts as the mean of |Y|^2 over the first min(8, full frames) frames that lie inside the row (t >= 3; over all frames where none
+ *   does), lower-bounded by phi; Pbar = 0.5; A^2 = 0.  Per frame, xi1 = 10^1.5:  p = 1 / (1 + (1 + xi1) exp(-(|Y|^2 / sigma^2) xi1 / (1 + xi1)));
+ *   Pbar = 0.9 Pbar + 0.1 p, and p = min(p, 0.99) where Pbar > 0.99;  sigma^2 = max(0.8 sigma^2 + 0.2 (p sigma^2 + (1 - p) |Y|^2), phi);
+ *   gamma = clip(|Y|^2 / sigma^2, 1e-6, 1e3);  xi = max(0.98 A^2 / sigma^2 + 0.02 max(gamma - 1, 0), 10^-2.5);  a = xi / (1 + xi);  rule 0 (wiener)
+ *   G = a, rule 1 (lsa) G = min(a exp(E1(a gamma) / 2), 1);  G = max(G, g_min);  A^2 = G^2 |Y|^2.  G and the updated sigma^2 are rounded once to fp32.
+ *   One thread per (row, bin) and T dependent steps: latency-bound by construction.
+ * buddy_denoise_synthesis: x^_t = Re(inverse transform of G[t] Y[t]) (one fp32 product per component, the same fp32 transform on the conjugate, / 512)
+ *   into ws; out[b][n] = sum_t w[n - s_t] x^_t[n - s_t] / sum_t w^2[n - s_t] over the four frames that cover n (s_t = t H - P), t ascending, w and the
+ *   sums in double, rounded once.  ws: buddy_denoise_synthesis_workspace(B, ldt) bytes (-1 for arguments out of range).
+ * buddy_denoise_stats: stats (B, 4) doubles: snr_est_db = 10 log10(sum max(|Y|^2 - sigma2, 0) / sum sigma2) over all frames and bins,
+ *   noise_db = 10 log10(mean sigma2 / sum w^2), att_db = 10 log10(sum x^2 / sum out^2), and the flag word (1 ZERO: the row is all zeros, the three
+ *   values are NaN; 2 SHORT: no frame lies inside the row, L < 512; 4 NO_SPEECH: the numerator is 0, snr_est_db = -inf).  One workgroup per row. */
+long long buddy_denoise_frames(long long L);
+int buddy_denoise_spectra(const float* x, const int* lens, int B, long long ld, float* Y /* (B,ldt,257,2) */, long long ldt, void* stream);
+int buddy_denoise_gains(const float* Y, const int* lens, const double* phi, int B, long long ldt, int rule, double g_min, float* G, float* sigma2, void* stream);
+long long buddy_denoise_synthesis_workspace(int B, long long ldt);
+int buddy_denoise_synthesis(const float* Y, const float* G, const int* lens, int B, long long ldt, float* out, long long ld, void* ws, long long ws_bytes,
+                            void* stream);
+int buddy_denoise_stats(const float* x, const float* out, const int* lens, int B, long long ld, const float* Y, const float* sigma2, long long ldt, double* stats,
+                        void* stream);
+
 /* ---- the small fp32 kernels of the network, one entry per launcher (unit tests: tests/test_hip_small_ops.py).  All tensors NHWC with H = time, device
  * pointers, fp32.  Each entry returns BUDDY_ERR_ARG with a message, with nothing launched, for a null required pointer, an empty shape, or a shape its
  * kernels cannot compute (named per entry).
