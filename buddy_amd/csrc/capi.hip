@@ -602,19 +602,23 @@ int buddy_flash_attention_bwd(const float* q, const float* k, const float* v, co
 
 int buddy_axpby_rows(const float* x, const float* y, const float* a, const float* c, float* out, int B, int L, void* stream) {
   if (!x || !a || !out || (y && !c)) { set_error("null argument"); return BUDDY_ERR_ARG; }
+  if (B < 1 || L < 1) { set_error("axpby_rows: B and L must be >= 1"); return BUDDY_ERR_ARG; }
   launch_axpby_rows(x, y, a, c, out, B, L, (hipStream_t)stream);
   return finish();
 }
 
 int buddy_perturb(const float* x, const float* eps, float scale, float* out, long long n, void* stream) {
   if (!x || !eps || !out) { set_error("null argument"); return BUDDY_ERR_ARG; }
+  if (n < 1) { set_error("perturb: n must be >= 1"); return BUDDY_ERR_ARG; }
   launch_perturb(x, eps, scale, out, n, (hipStream_t)stream);
   return finish();
 }
 
 int buddy_dps_update(const float* x_hat, const float* x_den, const float* lh, const float* lh_scale, const float* den_scale, const float* base,
                      const float* d_prev, float t, float dt, float w_prev, float w_cur, float* out, float* d_out, float* x_den_out, int B, int L, void* stream) {
-  if (!x_hat || !x_den || !base || !out || t <= 0.f) { set_error("bad arguments"); return BUDDY_ERR_ARG; }
+  if (!x_hat || !x_den || !base || !out || !(t > 0.f) || B < 1 || L < 1) {       // !(t > 0): a NaN sigma is refused too
+    set_error("dps_update: null argument, t not > 0, or B / L < 1"); return BUDDY_ERR_ARG;
+  }
   launch_dps_update(x_hat, x_den, lh, lh_scale, den_scale, base, d_prev, t, dt, w_prev, w_cur, out, d_out, x_den_out, B, L, (hipStream_t)stream);
   return finish();
 }
@@ -631,12 +635,15 @@ int buddy_fill_rows4(float* out, int B, float v0, float v1, float v2, float v3, 
 
 int buddy_row_moments(const float* x, double* out, int B, int L, void* stream) {
   if (!x || !out) { set_error("null argument"); return BUDDY_ERR_ARG; }
+  if (B < 1 || L < 1) { set_error("row_moments: B and L must be >= 1"); return BUDDY_ERR_ARG; }
   launch_row_moments(x, out, B, L, (hipStream_t)stream);
   return finish();
 }
 
 int buddy_fir(const float* x, const float* h, long long h_stride, float* y, int B, int L, int M, int adjoint, void* stream) {
-  if (!x || !h || !y || M < 1) { set_error("bad fir arguments"); return BUDDY_ERR_ARG; }
+  if (!x || !h || !y || M < 1 || B < 1 || L < 1 || B > 65535) {      // the batch is gridDim.y
+    set_error("bad fir arguments (M, L >= 1, 1 <= B <= 65535)"); return BUDDY_ERR_ARG;
+  }
   launch_fir(x, h, h_stride, y, B, L, M, adjoint, (hipStream_t)stream);
   return finish();
 }

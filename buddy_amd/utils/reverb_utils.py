@@ -15,11 +15,13 @@ from .. import _lib
 class _FirFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, h):
+        B, L = x.shape
+        M = h.shape[-1]
+        if h.dim() not in (1, 2) or (h.dim() == 2 and h.shape[0] not in (1, B)):
+            raise ValueError(f"filter of shape {tuple(h.shape)} for {B} utterances: expected (M,), (1, M) or ({B}, M)")
         lib = _lib.require_gpu()
         x = x.contiguous().float()
         h = h.contiguous().float()
-        B, L = x.shape
-        M = h.shape[-1]
         stride = M if (h.dim() == 2 and h.shape[0] == B and B > 1) else 0
         y = torch.empty_like(x)
         _lib.check(lib.buddy_fir(_lib.ptr(x), _lib.ptr(h), stride, _lib.ptr(y), B, L, M, 0, _lib.stream_ptr()))

@@ -425,7 +425,8 @@ int buddy_flash_attention_bwd_split(const float* q, const float* k, const float*
                                     float* dq, float* dk, float* dv, int B, int T, int C, float scale, int splits, float* ws, void* stream);
 
 /* ---- sampler elementwise / reductions (replace the tensor expressions of testing/EulerHeunSampler.py:41-72,
- * testing/EulerHeunSamplerDPS.py:61-69,115-157, diff_params/edm.py:83-96), per-utterance (row) semantics ---- */
+ * testing/EulerHeunSamplerDPS.py:61-69,115-157, diff_params/edm.py:83-96), per-utterance (row) semantics.  Every entry returns BUDDY_ERR_ARG
+ * before any launch for B, L, n or M < 1; buddy_dps_update also for a t that is not > 0 (NaN included), buddy_fir for B > 65535 ---- */
 /* out[b][i] = a[b]*x[b][i] + c[b]*y[b][i] (y may be NULL) */
 int buddy_axpby_rows(const float* x, const float* y, const float* a, const float* c, float* out, int B, int L, void* stream);
 /* stochastic churn: out = x + scale * eps (EulerHeunSampler.py:41-45, scale = sqrt(t_hat^2 - t^2)) */
