@@ -193,6 +193,11 @@ _SIGS = {
                                       C.c_int, C.c_int, C.c_void_p]),
     "buddy_groupnorm_act_bwd": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_void_p, _f32p, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "buddy_groupnorm_view_fwd": (C.c_int, [_f32p, C.c_int, C.c_int, _f32p, C.c_int, C.c_int, _f32p, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p,
+                                           _f32p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "buddy_groupnorm_view_bwd": (C.c_int, [_f32p, C.c_int, C.c_int, _f32p, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int,
+                                           _f32p, C.c_int, C.c_float, _f32p, C.c_int, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, C.c_void_p, _f32p,
+                                           C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "buddy_fir_resample2": (C.c_int, [_f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p]),
     "buddy_ncsnpp_set_fir": (C.c_int, [C.c_void_p, C.c_int]),
     "buddy_ncsnpp_set_gemm": (C.c_int, [C.c_void_p, C.c_int]),

@@ -508,9 +508,33 @@ int buddy_gnbwd_upconv3x3_winograd6_f16(const float* h, const float* gamma, cons
   return gnbwd_conv3x3_winograd6(2, h, gamma, beta, stats, da, G, silu, nullptr, U1upT, y, scratch, stat_scratch, red, B, H, W, C, Cout, stream);
 }
 
+// What the stand-alone GroupNorm kernels (ops.hip) cannot compute, for all four entries below; nullptr = fine.  G is checked before it divides;
+// C <= 1024: a reduction block holds C / 4 <= 256 channel quads; mode 1 / extra_mode 2 read a tensor of H/2 x W/2 pixels at (h >> 1, w >> 1).
+static const char* gn_refusal(int B, int H, int W, int C, int G, int mode, int extra_mode) {
+  if (B < 1 || H < 1 || W < 1 || C < 1 || G < 1) return "groupnorm: B, H, W, C and G must be at least 1";
+  if (C % G != 0) return "groupnorm: C must be a multiple of G";
+  if ((C / G) % 4 != 0) return "groupnorm: the channels of a group must be a multiple of 4 (a thread holds one channel quad of one group)";
+  if (C > 1024) return "groupnorm: C must be at most 1024";
+  if (mode < 0 || mode > 2) return "groupnorm: mode must be 0 (same), 1 (2x down) or 2 (2x up)";
+  if (extra_mode < 0 || extra_mode > 2) return "groupnorm: extra_mode must be 0 (none), 1 (same resolution) or 2 (H/2 x W/2)";
+  if ((mode == 1 || extra_mode == 2) && ((H | W) & 1)) return "groupnorm: mode 1 and extra_mode 2 (tensors at H/2 x W/2) need even H and W";
+  return nullptr;
+}
+// a two-pointer channel view: the first part's width w0 (w1 = C - w0 for the second, where there is one) and the row strides
+static const char* gn_view_refusal(const void* p1, int w0, int w1, int ld0, int ld1, int C) {
+  if (p1 == nullptr && w0 != C) return "groupnorm: a single-pointer view has all C channels in its first part";
+  if (p1 != nullptr && (w0 < 4 || w1 < 4 || w0 + w1 != C)) return "groupnorm: both parts of a two-pointer view hold at least 4 channels, C in all";
+  if (w0 % 4 != 0) return "groupnorm: the first part of a view must be a multiple of 4 channels wide (a thread's channel quad lies in one part)";
+  if (ld0 < w0 || ld0 % 4 != 0) return "groupnorm: a row stride must be a multiple of 4 floats, at least the part's width";
+  if (p1 != nullptr && (ld1 < w1 || ld1 % 4 != 0)) return "groupnorm: a row stride must be a multiple of 4 floats, at least the part's width";
+  return nullptr;
+}
+#define GN_REFUSE(expr) do { const char* gn_msg_ = (expr); if (gn_msg_) { set_error(gn_msg_); return BUDDY_ERR_ARG; } } while (0)
+
 int buddy_groupnorm_act(const float* x, const float* gamma, const float* beta, float* y, float* stats, void* scratch, int B, int H, int W, int C,
                         int G, int mode, int silu, void* stream) {
-  if (!x || !y || !stats || !scratch || C % 4 || (C / G) % 4 || C > 1024) { set_error("bad groupnorm arguments"); return BUDDY_ERR_ARG; }
+  GN_REFUSE((!x || !gamma || !beta || !y || !stats || !scratch) ? "groupnorm: null pointer" : nullptr);
+  GN_REFUSE(gn_refusal(B, H, W, C, G, mode, 0));
   Src2 s; s.p0 = x; s.p1 = nullptr; s.C0 = C; s.ld0 = C; s.ld1 = 0;
   launch_gn_stats(s, B, H * W, C, G, 1e-6f, (double*)scratch, stats, (hipStream_t)stream);
   launch_gn_apply(s, stats, gamma, beta, B, H, W, C, G, mode, silu, y, nullptr, (hipStream_t)stream);
@@ -519,10 +543,54 @@ int buddy_groupnorm_act(const float* x, const float* gamma, const float* beta, f
 
 int buddy_groupnorm_act_bwd(const float* x, const float* gamma, const float* beta, const float* stats, const float* dy, float* dx, void* scratch,
                             float* red, int B, int H, int W, int C, int G, int mode, int silu, void* stream) {
-  if (!x || !dy || !dx || !stats || !scratch || !red || C % 4 || (C / G) % 4 || C > 1024) { set_error("bad groupnorm arguments"); return BUDDY_ERR_ARG; }
+  GN_REFUSE((!x || !gamma || !beta || !dy || !dx || !stats || !scratch || !red) ? "groupnorm: null pointer" : nullptr);
+  GN_REFUSE(gn_refusal(B, H, W, C, G, mode, 0));
   Src2 s; s.p0 = x; s.p1 = nullptr; s.C0 = C; s.ld0 = C; s.ld1 = 0;
   Dst2 d; d.p0 = dx; d.p1 = nullptr; d.C0 = C; d.ld0 = C; d.ld1 = 0; d.acc0 = 0; d.acc1 = 0;
   launch_gn_bwd(s, stats, gamma, beta, dy, B, H, W, C, G, mode, silu, nullptr, 0, 0.f, (double*)scratch, red, d, (hipStream_t)stream);
+  return finish();
+}
+
+// The stand-alone GroupNorm launchers with everything they take: a (concatenated, strided) source view, both statistics routes, pooled_raw; and
+// in the backward the extra gradient and a two-destination gradient view (tests/test_hip_groupnorm.py).
+int buddy_groupnorm_view_fwd(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, const float* gamma, const float* beta, int G, int mode,
+                             int silu, float* y, float* pooled_raw, float* stats, int route, double* csum0, double* csum1, double* scratch, int B,
+                             int H, int W, void* stream) {
+  GN_REFUSE((!x0 || !gamma || !beta || !y || !stats || !scratch) ? "groupnorm: null pointer" : nullptr);
+  const int C = x1 ? C0 + C1 : C0;
+  GN_REFUSE((C0 < 1 || (x1 && C1 < 1)) ? "groupnorm: B, H, W, C and G must be at least 1" : nullptr);
+  GN_REFUSE(gn_refusal(B, H, W, C, G, mode, 0));
+  GN_REFUSE(gn_view_refusal(x1, C0, C1, ld0, ld1, C));
+  GN_REFUSE((route < 0 || route > 1) ? "groupnorm: route must be 0 (one reduction over the view) or 1 (per-source channel sums)" : nullptr);
+  GN_REFUSE((route == 1 && (!csum0 || (x1 && !csum1))) ? "groupnorm: route 1 needs a csum buffer per source" : nullptr);
+  GN_REFUSE((pooled_raw && mode != 1) ? "groupnorm: pooled_raw exists in mode 1 only" : nullptr);
+  hipStream_t st = (hipStream_t)stream;
+  Src2 s; s.p0 = x0; s.p1 = x1; s.C0 = C0; s.ld0 = ld0; s.ld1 = x1 ? ld1 : 0;
+  if (route == 0) {
+    launch_gn_stats(s, B, H * W, C, G, 1e-6f, scratch, stats, st);
+  } else {
+    launch_chan_sums(x0, B, H * W, C0, scratch, csum0, st, ld0);
+    if (x1) launch_chan_sums(x1, B, H * W, C1, scratch, csum1, st, ld1);
+    launch_gn_stats_csum(csum0, x1 ? csum1 : nullptr, C0, B, H * W, C, G, 1e-6f, stats, st);
+  }
+  launch_gn_apply(s, stats, gamma, beta, B, H, W, C, G, mode, silu, y, pooled_raw, st);
+  return finish();
+}
+
+int buddy_groupnorm_view_bwd(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, const float* gamma, const float* beta,
+                             const float* stats, const float* dy, int G, int mode, int silu, const float* extra, int extra_mode, float extra_scale,
+                             float* dx0, int ldd0, int acc0, float* dx1, int ldd1, int acc1, int Cd0, double* scratch, float* red, int B, int H,
+                             int W, void* stream) {
+  GN_REFUSE((!x0 || !gamma || !beta || !stats || !dy || !dx0 || !scratch || !red) ? "groupnorm: null pointer" : nullptr);
+  const int C = x1 ? C0 + C1 : C0;
+  GN_REFUSE((C0 < 1 || (x1 && C1 < 1)) ? "groupnorm: B, H, W, C and G must be at least 1" : nullptr);
+  GN_REFUSE(gn_refusal(B, H, W, C, G, mode, extra_mode));
+  GN_REFUSE(gn_view_refusal(x1, C0, C1, ld0, ld1, C));
+  GN_REFUSE(gn_view_refusal(dx1, Cd0, C - Cd0, ldd0, ldd1, C));
+  GN_REFUSE(((extra_mode != 0) != (extra != nullptr)) ? "groupnorm: extra and extra_mode go together" : nullptr);
+  Src2 s; s.p0 = x0; s.p1 = x1; s.C0 = C0; s.ld0 = ld0; s.ld1 = x1 ? ld1 : 0;
+  Dst2 d; d.p0 = dx0; d.p1 = dx1; d.C0 = Cd0; d.ld0 = ldd0; d.ld1 = dx1 ? ldd1 : 0; d.acc0 = acc0 ? 1 : 0; d.acc1 = (dx1 && acc1) ? 1 : 0;
+  launch_gn_bwd(s, stats, gamma, beta, dy, B, H, W, C, G, mode, silu, extra, extra_mode, extra_scale, scratch, red, d, (hipStream_t)stream, 0);
   return finish();
 }
 

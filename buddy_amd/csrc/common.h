@@ -146,10 +146,11 @@ int  gn_num_chunks(int HW);
 void launch_gn_stats(Src2 x, int B, int HW, int C, int G, float eps, double* partial, float* stats /*[B][G][2]*/, hipStream_t st);
 // per-(utterance, channel) sums kept with a tensor (csum[b][c][2] = sum, sum of squares, fp64) so that every GroupNorm reading it -- alone or
 // as one half of a skip concatenation -- gets its statistics without another pass over the tensor:
-//   launch_chan_sums      one pass over a single-source tensor (for tensors whose producer does not leave partials)
+//   launch_chan_sums      one pass over a single-source tensor (for tensors whose producer does not leave partials); ld: its row stride in
+//                         floats, 0 = C (dense)
 //   launch_csum_collapse  partial[b][chunks][C][2] (a producer's epilogue, wino4 stat) -> csum
 //   launch_gn_stats_csum  (mean, rstd) per group from the csums of the one or two sources of a view
-void launch_chan_sums(const float* x, int B, int HW, int C, double* partial, double* csum, hipStream_t st);
+void launch_chan_sums(const float* x, int B, int HW, int C, double* partial, double* csum, hipStream_t st, int ld = 0);
 void launch_csum_collapse(const double* partial, int chunks, int B, int C, double* csum, hipStream_t st);
 void launch_gn_stats_partial(const double* partial, int chunks, int B, int HW, int C, int G, float eps, float* stats, hipStream_t st);
 void launch_gn_stats_csum(const double* csum0, const double* csum1, int C0, int B, int HW, int C, int G, float eps, float* stats, hipStream_t st);

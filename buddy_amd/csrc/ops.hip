@@ -1064,8 +1064,8 @@ void launch_gn_stats(Src2 x, int B, int HW, int C, int G, float eps, double* par
 void launch_csum_collapse(const double* partial, int chunks, int B, int C, double* csum, hipStream_t st) {
   hipLaunchKernelGGL(csum_collapse_kernel, dim3((C + 15) / 16, B), dim3(256), 0, st, partial, chunks, C, csum);
 }
-void launch_chan_sums(const float* x, int B, int HW, int C, double* partial, double* csum, hipStream_t st) {
-  Src2 s; s.p0 = x; s.p1 = nullptr; s.C0 = C; s.ld0 = C; s.ld1 = 0;
+void launch_chan_sums(const float* x, int B, int HW, int C, double* partial, double* csum, hipStream_t st, int ld) {
+  Src2 s; s.p0 = x; s.p1 = nullptr; s.C0 = C; s.ld0 = ld > 0 ? ld : C; s.ld1 = 0;
   RedArgs a = make_red(s, B, 1, HW, C, 1, partial);
   prof_hbm_begin(4.0 * B * HW * C, st);                                   // one read of x
   hipLaunchKernelGGL(chan_reduce_kernel<0>, dim3(a.chunks, B), dim3(256), 0, st, a);

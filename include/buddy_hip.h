@@ -357,6 +357,25 @@ int buddy_groupnorm_act(const float* x, const float* gamma, const float* beta, f
 /* input-gradient of the above given dy (at the resampled resolution). red: [B][G][2] scratch. */
 int buddy_groupnorm_act_bwd(const float* x, const float* gamma, const float* beta, const float* stats, const float* dy, float* dx,
                             void* scratch, float* red, int B, int H, int W, int C, int G, int mode, int silu, void* stream);
+/* The same two operations with everything the network's GroupNorm launchers take (unit tests).  Source view: channels [0, C0) from x0 at a row
+ * stride of ld0 floats, and with x1 != NULL channels [C0, C0 + C1) from x1 at ld1 (C = C0 + C1; x1 NULL: C = C0, ld1 and C1 unused).  route 0:
+ * statistics by one reduction over the view; route 1: per-source channel sums csum0 [B][C0][2] / csum1 [B][C1][2] (sum, sum of squares, float64,
+ * outputs) and the statistics from them, as the network does.  pooled_raw (optional, mode 1 only): the 2x2 mean of x itself, (B, H/2, W/2, C).
+ * y dense at the resampled resolution; stats [B][G][2] out; scratch >= B*256*C*16 bytes.
+ * All four GroupNorm entries refuse (BUDDY_ERR_ARG, before any launch): a null required pointer; B, H, W, C, G < 1; C % G; (C / G) % 4; C > 1024;
+ * C0 % 4 (Cd0 % 4); a row stride below its width or not a multiple of 4; odd H or W with mode 1 or extra_mode 2; pooled_raw outside mode 1; a
+ * mode, extra_mode or route out of range. */
+int buddy_groupnorm_view_fwd(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, const float* gamma, const float* beta, int G,
+                             int mode, int silu, float* y, float* pooled_raw, float* stats, int route, double* csum0, double* csum1,
+                             double* scratch, int B, int H, int W, void* stream);
+/* Input-gradient: dx = GroupNorm backward of dy (dense, at the resampled resolution) + the extra gradient: extra_mode 1: extra_scale * extra
+ * (B, H, W, C); extra_mode 2: 0.25 * extra_scale * extra (B, H/2, W/2, C) at (h >> 1, w >> 1); extra_mode 0: extra NULL.  Destination view:
+ * channels [0, Cd0) to dx0 at a row stride of ldd0, the rest to dx1 at ldd1 (dx1 NULL: Cd0 = C); a part whose acc flag is set is added to,
+ * the other overwritten.  stats: the forward's; red [B][G][2] out; scratch >= B*256*C*16 bytes. */
+int buddy_groupnorm_view_bwd(const float* x0, int ld0, int C0, const float* x1, int ld1, int C1, const float* gamma, const float* beta,
+                             const float* stats, const float* dy, int G, int mode, int silu, const float* extra, int extra_mode,
+                             float extra_scale, float* dx0, int ldd0, int acc0, float* dx1, int ldd1, int acc1, int Cd0, double* scratch,
+                             float* red, int B, int H, int W, void* stream);
 
 /* fir=True resampling (networks/ncsnpp_utils/up_or_down_sampling.py:195-257 upsample_2d / downsample_2d -> upfirdn2d, op/upfirdn2d_kernel.cu)
  * with the (1,3,3,1) kernel, factor 2, NHWC: up != 0: (H,W) -> (2H,2W), else (H,W) -> (H/2,W/2); y = (accumulate ? y : 0) + scale * resample(x).
