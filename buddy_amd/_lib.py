@@ -226,6 +226,11 @@ _SIGS = {
     "buddy_noise_max_taps": (C.c_int, []),
     "buddy_noise_bank": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_uint, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong,
                                    C.c_double, C.c_void_p]),
+    "buddy_tail_tile": (C.c_int, []),
+    "buddy_tail_fit": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "buddy_tail_mix": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_longlong, C.c_void_p, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p]),
     "buddy_denoise_frames": (C.c_longlong, [C.c_longlong]),
     "buddy_denoise_spectra": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_longlong, _f32p, C.c_longlong, C.c_void_p]),
     "buddy_denoise_gains": (C.c_int, [_f32p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_double, _f32p, _f32p, C.c_void_p]),

@@ -174,11 +174,12 @@ def shaping_fir(fs, tilt, taps=SHAPING_TAPS):
     return t[np.arange(-P, P + 1) % G] * 0.5 * (1.0 + np.cos(np.pi * np.arange(-P, P + 1, dtype=np.float64) / (P + 1)))
 
 
-def diffuse_noise(pos, keys, L, fs, waves=512, field="spherical", tilt=0.0, c=343.0, taps=SHAPING_TAPS):
+def diffuse_noise(pos, keys, L, fs, waves=512, field="spherical", tilt=0.0, c=343.0, taps=SHAPING_TAPS, purpose=NOISE_FIELD):
     """(B, D, L) float32 on the GPU: per file b a diffuse field of about unit power per channel at the microphones ``pos`` ((D, 3), or (B, D, 3): one
     geometry per file) [m from the array centre], from ``waves`` plane waves of the file's stream ``keys[b]`` (purpose ``NOISE_FIELD``, draw n = wave n).
     ``tilt`` != 0 shapes the spectrum by ``shaping_fir`` -- the field is generated ``taps - 1`` samples longer, all channels go through ``buddy_fir`` with
-    the one kernel, and the filter's transient is cut; the power then is that of the shaped spectrum, which ``mix_at_snr`` measures anyway."""
+    the one kernel, and the filter's transient is cut; the power then is that of the shaped spectrum, which ``mix_at_snr`` measures anyway.
+    ``purpose`` names the draws' purpose in the stream (default ``NOISE_FIELD``; a room's diffuse tail takes ``rooms.TAIL``)."""
     kh = _keys_host(keys)
     B = kh.shape[0]
     pos = np.asarray(pos, dtype=np.float64)
@@ -193,10 +194,10 @@ def diffuse_noise(pos, keys, L, fs, waves=512, field="spherical", tilt=0.0, c=34
     both = [delay_taps(p, dirs, fs, c) for p in pos]
     tp, fr = np.stack([t for t, _ in both]), np.stack([f for _, f in both])
     if float(tilt) == 0.0:
-        return noise_bank_hip(tp, fr, kh, L)
+        return noise_bank_hip(tp, fr, kh, L, purpose=purpose)
     h = shaping_fir(fs, tilt, taps)
     M = len(h)
-    x = noise_bank_hip(tp, fr, kh, L + M - 1)
+    x = noise_bank_hip(tp, fr, kh, L + M - 1, purpose=purpose)
     D = x.shape[1]
     x = x.reshape(B * D, L + M - 1)
     y = torch.empty_like(x)

@@ -8,6 +8,8 @@ speed of sound c [m/s].  ``eyring_beta`` / ``eyring_t60`` convert between a nomi
 one room per file name from the project's counter-based generator; ``room_rows`` / ``write_rooms`` make ``rooms.csv``: what each room is, next to what
 ``utils/acoustics.rir_acoustics`` measures on its simulated response.  The two are not expected to agree: specular images in a rectangular room decay
 more slowly than Eyring's diffuse-field formula says (a 0.30 s nominal room measured T20 = 0.43 s), which is why the file carries both.
+``shoebox_rir_hybrid`` (``--diffuse-tail``) closes that gap: images up to a crossover after the direct sound, then a diffuse
+noise tail under the room's nominal decay (``csrc/tail.hip``), so the measured T30 meets the nominal T60 and responses of seconds stay cheap.
 
 Banded rooms give the walls their own coefficients per octave band and the air an attenuation per band:
 ``shoebox_rir_bands`` computes the band responses in double and combines them through ``octave_bank``; ``draw_band_rooms`` tilts the nominal T60 of
@@ -23,6 +25,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import noise as _noise
 from . import rng as _rng
 from .acoustics import write_report
 
@@ -35,6 +38,9 @@ ARRAY = 6                                            # purpose number of a file'
 ARRAY_RADIUS = 0.1                                   # default radius of a circular array [m]: the REVERB challenge's 8-microphone array
 BAND_CENTRES = (125, 250, 500, 1000, 2000, 4000)     # default octave centres of banded rooms [Hz]
 BANK_TAPS = 1023                                     # default length of octave_bank's rows: a choice (see there)
+TAIL = 10                                            # purpose number of a file's diffuse-tail noise: the next free one after noise.NOISE_SENSOR = 9
+TAIL_MS, TAIL_RAMP, TAIL_WAVES = 80.0, 256, 512      # defaults of the diffuse tail: choices nobody has measured
+TAIL_PURE, TAIL_ZERO = 2, 4                          # flag bits 1 and 2 of a hybrid response: no tail (n <= n_e); a fit window without energy
 
 
 def room_row(dims, source, receiver, beta, c=343.0):
@@ -261,12 +267,19 @@ def _host(a):
     return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
 
 
-def shoebox_rir_bands(rooms, beta, fs, n, bank, air=None, max_order=-1, max_images=2e8, return_bands=False):
+def shoebox_rir_bands(rooms, beta, fs, n, bank, air=None, max_order=-1, max_images=2e8, return_bands=False, t60s=None, keys=None, tail_ms=None,
+                      ramp=TAIL_RAMP):
     """``rooms`` (B, 16), ``beta`` (B, nb, 6) pressure reflection coefficients per band and wall, ``air`` (nb,) or (B, nb) pressure attenuations in
     Np/m (None: zeros), all float64 arrays or GPU tensors; ``bank`` (nb, Nh) float64 (``octave_bank``) -> (h (B, n) float32 on the GPU, flags (B,)
     int32 on the CPU[, u (B, nb, n) float64 on the GPU, the band responses]).  The rows' own six coefficients are not read.  h = sum_k bank[k] * u_k
     applied causally: sample n sits at time (n - Hw - P) / fs, P = (Nh - 1) / 2.  An invalid row is zeros with flag 0.  Refuses above ``max_images``
-    exactly as ``shoebox_rir`` does.  No CPU form."""
+    exactly as ``shoebox_rir`` does.  No CPU form.
+
+    ``tail_ms`` (default None: nothing changes) gives every band a diffuse late tail (``shoebox_rir_hybrid``): the band responses
+    are computed up to n_e = n_x + ``ramp`` samples only -- that length is what ``max_images`` then judges -- and mixed in the band domain with ONE
+    noise sequence per row (stream ``keys[b]``, purpose ``TAIL``) under the band's own decay 3 ln 10 / ``t60s[b, k]`` + c air[b, k], before the
+    combination.  ``t60s`` (B, nb) float64 [s] and ``keys`` (B, 2) uint32 are then required, and the result gains a third value before ``u``:
+    (h, flags, info[, u]) with flags and info as ``shoebox_rir_hybrid`` returns them."""
     is_tensor = isinstance(rooms, torch.Tensor)
     host = _host(rooms)
     if host.ndim != 2 or host.shape[1] != 16 or host.dtype != np.float64:
@@ -289,6 +302,22 @@ def shoebox_rir_bands(rooms, beta, fs, n, bank, air=None, max_order=-1, max_imag
             raise ValueError(f"shoebox_rir_bands takes (nb,) or (B, nb) float64 air, got {ah.dtype} {tuple(ah.shape)}")
         ah = np.array(np.broadcast_to(ah, (B, nb)))
     fs, n, max_order = int(fs), int(n), int(max_order)
+    n_out, tail = n, None
+    if tail_ms is not None:
+        if t60s is None or keys is None:
+            raise ValueError("shoebox_rir_bands: a tail needs t60s (B, nb) and keys (B, 2)")
+        th = _host(t60s)
+        if th.dtype != np.float64 or th.shape != (B, nb) or not np.all(np.isfinite(th) & (th > 0)):
+            raise ValueError(f"shoebox_rir_bands takes (B, nb) = {(B, nb)} positive finite float64 t60s, got {th.dtype} {tuple(th.shape)}")
+        kh = _noise._keys_host(keys, B)
+        win = tail_window(host, fs, tail_ms, ramp)
+        delta = 3.0 * math.log(10.0) / th + host[:, 15:16] * (0.0 if ah is None else ah)
+        if not np.all(np.isfinite(delta)):
+            raise ValueError("shoebox_rir_bands: a band's decay 3 ln 10 / T60 + c air is not finite")
+        if n < 1:
+            raise ValueError("shoebox_rir_bands: n >= 1")
+        n = min(n_out, int(win[:, 3].max()))                             # the image-source part: what the kernel computes and max_images judges
+        tail = (win, delta, kh)
     est = estimated_images(host, fs, n, max_order)
     for b, v in enumerate(est):
         if v > float(max_images):
@@ -304,13 +333,165 @@ def shoebox_rir_bands(rooms, beta, fs, n, bank, air=None, max_order=-1, max_imag
     at = None if ah is None else on(ah)
     kt = on(bk)
     u = torch.empty(B, nb, n, dtype=torch.float64, device=dev)
-    h = torch.empty(B, n, dtype=torch.float32, device=dev)
     flags = torch.empty(B, dtype=torch.int32, device=dev)
     st = _lib.stream_ptr()
     _lib.check(lib.buddy_shoebox_bands(r.data_ptr(), bt.data_ptr(), None if at is None else at.data_ptr(), B, nb, fs, n, max_order, u.data_ptr(), n,
                                        flags.data_ptr(), st))
+    info = None
+    if tail is not None:
+        u, amp, tf = _tail_mix(u, n_out, 1, tail[0], int(ramp), tail[1], None, None, tail[2], fs)
+        info = _tail_info(tail[0], tail[1], amp, None, 1, int(ramp), float(tail_ms))
+        info["ism_samples"], n = n, n_out
+    h = torch.empty(B, n, dtype=torch.float32, device=dev)
     _lib.check(lib.buddy_band_combine(u.data_ptr(), B, nb, n, n, kt.data_ptr(), bk.shape[1], _lib.ptr(h), n, st))
-    return (h, flags.cpu(), u) if return_bands else (h, flags.cpu())
+    if tail is None:
+        return (h, flags.cpu(), u) if return_bands else (h, flags.cpu())
+    fl = flags.cpu() | torch.from_numpy(tf.astype(np.int32))
+    return (h, fl, info, u) if return_bands else (h, fl, info)
+
+
+# ---- diffuse late tail: images up to a crossover after the direct sound, then noise under the room's nominal decay --------
+def _half_up(x):
+    return int(math.floor(x + 0.5))
+
+
+def tail_window(rooms, fs, tail_ms, ramp, mics=1):
+    """(G, 4) int64, G = B / ``mics`` groups of consecutive rows (the microphones of one room): per group (n_d, n_f, n_x, n_e) -- the sample of the
+    direct sound n_d = Hw + half_up(min over the group's rows of |s - r| fs / c), the fit window [n_f, n_x) = n_d + half_up(0.5 ``tail_ms`` fs / 1000)
+    .. n_d + half_up(``tail_ms`` fs / 1000), and the length n_e = n_x + ``ramp`` of the image-source part.  Host only.  ValueError for rooms that are
+    not (B, 16) float64 with B a multiple of ``mics``, a distance or speed that is not positive and finite, ``tail_ms`` not positive and finite,
+    ``ramp`` < 1, or an n_e above 2^20 (what the simulator takes)."""
+    host = _host(rooms)
+    mics, ramp, fs = int(mics), int(ramp), int(fs)
+    if host.ndim != 2 or host.shape[1] != 16 or host.dtype != np.float64:
+        raise ValueError(f"tail_window takes (B, 16) float64 rooms, got {host.dtype} {tuple(host.shape)}")
+    if not 1 <= mics <= 8 or host.shape[0] < 1 or host.shape[0] % mics != 0:
+        raise ValueError(f"tail_window: mics in 1..8 and a multiple of it in rows, got mics = {mics}, B = {host.shape[0]}")
+    if not (math.isfinite(float(tail_ms)) and float(tail_ms) > 0.0) or ramp < 1 or fs < 1:
+        raise ValueError("tail_window: tail_ms positive and finite, ramp >= 1, fs >= 1")
+    with np.errstate(all="ignore"):
+        lag = np.linalg.norm(host[:, 3:6] - host[:, 6:9], axis=1) * float(fs) / host[:, 15]
+    if not np.all(np.isfinite(lag) & (lag > 0.0)):
+        raise ValueError("tail_window: every row needs a positive finite distance |s - r| and speed c")
+    Hw = _lib.load().buddy_ism_half_width()
+    out = np.empty((host.shape[0] // mics, 4), dtype=np.int64)
+    for g, v in enumerate(lag.reshape(-1, mics).min(axis=1)):
+        n_d = Hw + _half_up(float(v))
+        n_x = n_d + _half_up(float(tail_ms) * 1e-3 * fs)
+        out[g] = (n_d, n_d + _half_up(0.5 * float(tail_ms) * 1e-3 * fs), n_x, n_x + ramp)
+    if np.any(out[:, 1] >= out[:, 2]) or int(out[:, 3].max()) > 2 ** 20:
+        raise ValueError("tail_window: tail_ms of at least two samples, and n_e = n_x + ramp of at most 2^20")
+    return out
+
+
+def _tail_mix(u, n, D, win, R, delta, nu, z, kh, fs):
+    """``u`` (B, nb, len) fp32 or fp64 on the GPU, the image-source part; ``win`` (G, 4) of ``tail_window``; ``delta`` (G, nb); ``nu`` (B,) or None;
+    ``z`` (B, n) fp32 on the GPU, or None with the rows' stream keys ``kh`` (B, 2) uint32 -> (out (B, nb, n) of u's type, amp (B, nb) float64 as
+    ``buddy_tail_fit`` left it (A / nu; 0 for a row without tail), flags (B,): TAIL_PURE for a row of a group with n <= n_e, whose output is u itself,
+    TAIL_ZERO from the fit).  The kernels run on the groups that get a tail; a row's bits do not depend on the others."""
+    lib = _lib.require_gpu()
+    B, nb, ln = u.shape
+    G = B // D
+    dev, st = u.device, _lib.stream_ptr()
+    hyb = n > win[:, 3]
+    amp, flags = np.zeros((B, nb), dtype=np.float64), np.where(np.repeat(hyb, D), 0, TAIL_PURE).astype(np.int32)
+    if not hyb.any():
+        return u, amp, flags                                             # ln = n: every n_e is at least n
+    out = torch.empty(B, nb, n, dtype=u.dtype, device=dev)
+    if not hyb.all():
+        out.copy_(u)                                                     # ln = n here too; the rows with a tail are written again below
+    rows = np.nonzero(np.repeat(hyb, D))[0]
+    sel = torch.from_numpy(rows).to(dev)
+    pick = (lambda a: a) if hyb.all() else (lambda a: a.index_select(0, sel).contiguous())
+    on = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    us = pick(u.contiguous())
+    Bs = us.shape[0]
+    wt, dt = on(win[hyb][:, 1:3].astype(np.int32)), on(np.asarray(delta, dtype=np.float64)[hyb])
+    nt = None if nu is None else on(np.asarray(nu, dtype=np.float64)[rows])
+    zt = None if z is None else pick(z.contiguous())
+    kt = None if kh is None else _noise._keys_device(np.ascontiguousarray(kh[rows]), dev)
+    at = torch.empty(Bs, nb, dtype=torch.float64, device=dev)
+    ft = torch.empty(Bs // D, dtype=torch.int32, device=dev)
+    os_ = out if hyb.all() else torch.empty(Bs, nb, n, dtype=u.dtype, device=dev)
+    f64 = int(u.dtype == torch.float64)
+    _lib.check(lib.buddy_tail_fit(us.data_ptr(), f64, Bs, nb, D, nb * ln, ln, ln, wt.data_ptr(), dt.data_ptr(), None if nt is None else nt.data_ptr(), fs,
+                                  at.data_ptr(), ft.data_ptr(), st))
+    _lib.check(lib.buddy_tail_mix(us.data_ptr(), f64, Bs, nb, D, nb * ln, ln, ln, wt.data_ptr(), R, dt.data_ptr(), at.data_ptr(),
+                                  None if zt is None else zt.data_ptr(), n, None if kt is None else kt.data_ptr(), TAIL, fs, n, os_.data_ptr(), nb * n, n, st))
+    if not hyb.all():
+        out.index_copy_(0, sel, os_)
+    amp[rows] = at.cpu().numpy()
+    flags[rows] |= np.repeat(ft.cpu().numpy(), D)
+    return out, amp, flags
+
+
+def _tail_info(win, delta, amp, nu, D, ramp, tail_ms):
+    """what ``shoebox_rir_hybrid`` reports: the windows, the decays and the fitted amplitudes A (G, nb) -- the kernel's A / nu of a group's first row
+    times that row's nu"""
+    A = amp[::D] * (1.0 if nu is None else np.asarray(nu)[::D, None])
+    return dict(tail_ms=float(tail_ms), ramp=int(ramp), windows=win, n_d=win[:, 0], n_f=win[:, 1], n_x=win[:, 2], n_e=win[:, 3], delta=delta, amp=A,
+                amp_rows=amp, nu=nu)
+
+
+def tail_field(rooms, mics, fs, waves=TAIL_WAVES, field="spherical"):
+    """host part of an array's tail field: per group of ``mics`` rows the microphone positions relative to their mean (G, mics, 3) and
+    nu (B,) float64, nu_m = sqrt(sum_waves sum_j taps[n, m, j]^2 / waves) -- the analytic standard deviation of the plane-wave field of
+    ``noise.diffuse_noise`` at microphone m, from ``noise.delay_taps`` with the group's own speed of sound"""
+    host = _host(rooms)
+    pos = host[:, 6:9].reshape(-1, int(mics), 3)
+    pos = pos - pos.mean(axis=1, keepdims=True)
+    dirs = _noise.directions(field, waves)
+    nu = np.concatenate([np.sqrt((_noise.delay_taps(p, dirs, fs, float(c))[0] ** 2).sum(axis=(0, 2)) / len(dirs))
+                         for p, c in zip(pos, host[::int(mics), 15])])
+    return pos, nu
+
+
+def shoebox_rir_hybrid(rooms, fs, n, t60, keys, tail_ms=TAIL_MS, ramp=TAIL_RAMP, mics=1, waves=TAIL_WAVES, field="spherical", max_order=-1, max_images=2e8):
+    """The image-source response with a diffuse late tail.  ``rooms`` (B, 16) float64, an array or a tensor on the GPU, in
+    groups of ``mics`` consecutive rows (``array_rows``); ``t60`` [s], one value, (G,) or (B,) (a group takes its first row's): the Eyring time the
+    room was drawn with; ``keys`` (G, 2) uint32, the stream of each group's file -> (h (B, n) float32 on the GPU, flags (B,) int32 on the CPU,
+    info).  Per group the image-source part is computed up to n_e = n_x + ``ramp`` samples only (``tail_window``; one call of ``shoebox_rir`` at the
+    largest n_e of the batch, which is what ``max_images`` judges), its energy in [n_f, n_x) over all the group's rows fits ONE amplitude A of the
+    envelope A exp(-delta t), delta = 3 ln 10 / T60, and from n_x the response cross-fades over ``ramp`` samples into that envelope times white
+    Gaussian noise: kind-0 normals of purpose ``TAIL``, draw 0, of the group's stream for ``mics`` = 1; for an array the plane-wave diffuse field of
+    ``noise.diffuse_noise`` (``waves`` draws of purpose ``TAIL``, ``field``) at the microphones, each row divided by its analytic standard deviation.
+    Below n_x the result is ``shoebox_rir``'s, bit for bit.  flags: bit 0 the simulator's (valid row), bit 1 (``TAIL_PURE``) n <= n_e, the pure
+    response of n samples, bit 2 (``TAIL_ZERO``) a fit window without energy (amplitude 0).  info: ``windows`` (G, 4) with its columns as ``n_d``,
+    ``n_f``, ``n_x``, ``n_e``; ``delta`` (G, 1); ``amp`` (G, 1) the fitted A; ``amp_rows`` (B, 1) A / nu as applied; ``nu`` (B,) or None;
+    ``ism_samples``.  No CPU form."""
+    is_tensor = isinstance(rooms, torch.Tensor)
+    host = _host(rooms)
+    fs, n, D, R, waves = int(fs), int(n), int(mics), int(ramp), int(waves)
+    win = tail_window(host, fs, tail_ms, R, D)
+    B, G = host.shape[0], host.shape[0] // D
+    if n < 1:
+        raise ValueError("shoebox_rir_hybrid: n >= 1")
+    th = np.asarray(_host(t60), dtype=np.float64)
+    if th.shape == (B,) and D > 1:
+        th = th[::D]
+    if th.shape not in ((), (1,), (G,)) or not np.all(np.isfinite(th) & (th > 0)):
+        raise ValueError(f"shoebox_rir_hybrid takes one positive finite t60, or one per group ({G}) or row ({B}), got {tuple(th.shape)}")
+    delta = (3.0 * math.log(10.0) / np.broadcast_to(th, (G,))).reshape(G, 1)
+    kh = _noise._keys_host(keys, G)
+    if D > 1 and not 1 <= waves <= 4096:
+        raise ValueError("shoebox_rir_hybrid: waves in 1..4096")
+    pos = nu = None
+    if D > 1:
+        pos, nu = tail_field(host, D, fs, waves, field)
+    ln = min(n, int(win[:, 3].max()))
+    u, iflags = shoebox_rir(rooms, fs, ln, max_order=max_order, max_images=max_images)
+    z = None
+    if D > 1 and bool(np.any(n > win[:, 3])):
+        cs = host[::D, 15]
+        if np.all(cs == cs[0]):
+            z = _noise.diffuse_noise(pos, kh, n, fs, waves=waves, field=field, c=float(cs[0]), purpose=TAIL)
+        else:
+            z = torch.cat([_noise.diffuse_noise(pos[g], kh[g:g + 1], n, fs, waves=waves, field=field, c=float(cs[g]), purpose=TAIL) for g in range(G)])
+        z = z.reshape(B, n)
+    out, amp, tf = _tail_mix(u[:, None, :], n, D, win, R, delta, nu, z, kh if D == 1 else None, fs)
+    info = _tail_info(win, delta, amp, nu, D, R, tail_ms)
+    info["ism_samples"] = ln
+    return out[:, 0, :], iflags | torch.from_numpy(tf), info
 
 
 def band_label(f):

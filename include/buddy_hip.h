@@ -895,6 +895,35 @@ int buddy_noise_max_taps(void);
 int buddy_noise_bank(const double* taps /* (B,N,D,W) */, const int* first /* (B,N,D) */, const unsigned* keys /* (B,2) */, unsigned purpose, unsigned draw0,
                      float* out /* (B,D,L) */, int B, int D, int N, int W, int P, long long L, double scale, void* stream);
 
+/* ---- diffuse late tail of simulated rooms (buddy_amd/utils/rooms.py, csrc/tail.hip; no reference counterpart).  The
+ * image-source response u of a row, computed for len samples only, is cross-faded after a crossover n_x into Gaussian noise z under the exponential
+ * envelope exp(-delta t_n), t_n = (n - Hw) / fs, Hw = buddy_ism_half_width(), level-matched to u's energy in the fit window [n_f, n_x).  Rows come in
+ * groups of D consecutive rows (the microphones of one room), G = B / D groups; a group shares win, delta and its amplitude.  u: DEVICE, fp32 (f64 = 0)
+ * or double (f64 = 1), sample n of band k of row b at u[b ldr + k ldk + n], n < len; win: DEVICE (G, 2) ints (n_f, n_x); delta: DEVICE (G, nb) doubles
+ * [1/s]; nu: DEVICE (B,) doubles, the standard deviation of z per row (NULL: ones).
+ *   buddy_tail_fit:  E_k = sum_rows sum_{n_f <= n < n_x} u_k[n]^2,  S_k = D sum_{n_f <= n < n_x} exp(-2 delta_k t_n),  amp[b][k] = sqrt(E_k / S_k) / nu[b],
+ * amp DEVICE (B, nb) doubles; E_k = 0 gives amp = 0 and flags[g] = 4 (bit 2), else flags[g] = 0; flags DEVICE (G,) ints.  One workgroup per (group,
+ * band); both sums in double, each thread adding its elements (flat index d W + j, W = n_x - n_f, stride 256, ascending), then lanes and waves in the
+ * fixed order of the evaluation entries: no atomics, a group's bits do not depend on B.
+ *   buddy_tail_mix:  th(n) = (pi / 2) clip((n - n_x + 1/2) / R, 0, 1),
+ *   out[b][k][n] = u_k[n] for n < n_x (its bits),  cos th(n) u_k[n] + sin th(n) amp[b][k] exp(-delta_k t_n) z_b[n] for n_x <= n < N,  u_k[n] = 0 for n >= n_x + R,
+ * in double, rounded once to the type of u, which is the type of out (sample n of band k of row b at out[b ldor + k ldok + n]).  z: DEVICE (B, ldz)
+ * fp32, read for n_x <= n < N; or NULL: z_b[n] = kind-0 normal n of draw 0 of `purpose` of the stream keys[b] (DEVICE (B, 2) uint32), the bits
+ * buddy_philox_fill stores, generated in the kernel once per four samples and used for every band.  One thread per four consecutive samples; fp32
+ * rows whose bases and strides are multiples of 16 bytes move as 16-byte vectors, with the same bits as the element form.  u is read below n_x + R
+ * only; nothing is written outside out[b][k][0..N - 1].  No atomics; a row's bits depend on its own u, win, delta, amp and z or key only.
+ * BUDDY_ERR_ARG, with nothing launched, for: a null pointer (nu may be NULL; z or keys may be NULL, not both); B outside 1..65535; nb outside
+ * 1..buddy_ism_max_bands(); D outside 1..8; B % D != 0; fs outside 1000..1000000; len outside 1..2^20; ldr < len, or ldk < len with nb > 1; R outside
+ * 1..2^20; N outside 1..2^30; ldz < N; ldok < N with nb > 1, or ldor < (nb - 1) ldok + N; and, read from the device once after the work queued on
+ * `stream`: a window without 0 <= n_f < n_x, n_x + R > len (buddy_tail_fit: n_x > len), a delta that is not finite, a nu that is not positive and
+ * finite.  No workspace.  buddy_tail_tile: output samples per workgroup of buddy_tail_mix (the size around which the unit tests place their lengths). */
+int buddy_tail_tile(void);
+int buddy_tail_fit(const void* u, int f64, int B, int nb, int D, long long ldr, long long ldk, int len, const int* win /* (G,2) */,
+                   const double* delta /* (G,nb) */, const double* nu /* (B,) or NULL */, int fs, double* amp /* (B,nb) */, int* flags /* (G,) */, void* stream);
+int buddy_tail_mix(const void* u, int f64, int B, int nb, int D, long long ldr, long long ldk, int len, const int* win /* (G,2) */, int R,
+                   const double* delta /* (G,nb) */, const double* amp /* (B,nb) */, const float* z /* (B,ldz) or NULL */, long long ldz,
+                   const unsigned* keys /* (B,2) or NULL */, unsigned purpose, int fs, int N, void* out, long long ldor, long long ldok, void* stream);
+
 /* ---- noise power tracker and spectral post-filter of noisy recordings (buddy_amd/utils/denoise.py, csrc/denoise.hip; Gerkmann &
  * Hendriks 2012, Ephraim & Malah 1984 / 1985; no reference counterpart).  The conventions of the evaluation entries hold: ragged rows inside a common
  * stride, a DEVICE length array copied to the host once to be checked, nothing behind a row's end read, nothing outside the declared extents written,

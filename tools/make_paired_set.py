@@ -8,6 +8,7 @@ file, its impulse response computed on the GPU by the image-source method.
                                     [--mics N] [--array-radius R]
                                     [--snr LO HI] [--snr-reference rms|active] [--noise-field spherical|cylindrical] [--noise-waves N]
                                     [--noise-tilt DB] [--sensor-snr DB]
+                                    [--diffuse-tail [MS]] [--tail-ramp N] [--tail-waves N]
 
 ``--clean`` holds ``<spk>/*.wav`` (a flat folder of wavs is the one speaker ``all``); int or float wavs of any rate, several channels averaged to
 mono; a file at another rate than ``--fs`` goes through the project's resampler.  Written under ``--out``, the layout ``VCTKTestPaired`` and with it
@@ -51,7 +52,19 @@ speech of channel 0 (``--snr-reference active``: its ITU-T P.56 active power) ov
 
 and ``rooms.csv`` gains ``snr_db``, ``snr_reference`` (as used), ``snr_measured_db`` (recomputed in double from the two arrays as written),
 ``noise_gain_diffuse``, ``noise_gain_sensor`` and ``noise_flags``.  The noise is a function of the seed, the name, the geometry and these flags, so
-the same call reproduces every file byte for byte.  ``--snr`` with ``--bands`` is refused.  Without ``--snr`` and ``--sensor-snr`` nothing changes."""
+the same call reproduces every file byte for byte.  ``--snr`` with ``--bands`` is refused.  Without ``--snr`` and ``--sensor-snr`` nothing changes.
+
+``--diffuse-tail [MS]`` (bare: 80) makes every response a hybrid (``rooms.shoebox_rir_hybrid``): the image-source response up
+to MS milliseconds after the direct sound, cross-faded over ``--tail-ramp`` samples (default 256) into Gaussian noise under the exponential envelope of
+the room's own nominal T60, level-matched to the image-source energy just before the crossover.  Without it a room's measured decay is 1.4 to 2
+times the nominal one (specular images of a shoebox decay slowly); with it T20 and T30 land within a few percent of the nominal T60, and responses of
+several seconds become simulable, because the images end about MS + ramp after the direct sound whatever the length.  With ``--bands`` the decay is
+per band (air included) and one noise sequence serves all bands; with ``--mics`` the tail is a diffuse field at the microphones (``--tail-waves``
+plane waves, default 512, the field of ``--noise-field``) with one amplitude for the array.  The length rule (1.5 x nominal) stays.  ``rooms.csv``
+gains ``tail_ms``, ``tail_direct`` and ``tail_start`` (the samples of the direct sound and of the crossover), ``tail_ramp``, ``ism_samples`` (the
+length of the image-source part), ``tail_amp`` (per band ``tail_amp_<f>``) and ``tail_flags`` (2: the response is shorter than the image-source part
+and has no tail; 4: nothing to fit the level to).  The tail is a function of the seed, the name, the geometry and these flags, so the same call
+reproduces every file byte for byte.  Without ``--diffuse-tail`` nothing changes."""
 import argparse
 import os
 import sys
@@ -147,6 +160,10 @@ def main(argv=None):
     ap.add_argument("--noise-waves", type=int, default=512, help="plane waves of the diffuse field (one microphone: 1)")
     ap.add_argument("--noise-tilt", type=float, default=0.0, help="spectral tilt of the diffuse noise [dB per octave] (0 white, -3 pink)")
     ap.add_argument("--sensor-snr", type=float, default=None, metavar="DB", help="with --reverberant: independent white noise per microphone at this SNR")
+    ap.add_argument("--diffuse-tail", type=float, nargs="?", const=rooms.TAIL_MS, default=None, metavar="MS",
+                    help="diffuse late tail from MS milliseconds after the direct sound (bare: 80)")
+    ap.add_argument("--tail-ramp", type=int, default=rooms.TAIL_RAMP, help="with --diffuse-tail: samples of the cross-fade")
+    ap.add_argument("--tail-waves", type=int, default=rooms.TAIL_WAVES, help="with --diffuse-tail and --mics: plane waves of the tail's diffuse field")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args(argv)
     noisy = a.snr is not None or a.sensor_snr is not None
@@ -166,6 +183,15 @@ def main(argv=None):
         raise SystemExit("make_paired_set: --mics takes a count >= 1")
     if a.mics > 1 and a.bands is not None:
         raise SystemExit("make_paired_set: --mics with --bands is not supported (banded rooms are simulated for one receiver)")
+    tailed = a.diffuse_tail is not None
+    if tailed and not (a.diffuse_tail > 0.0 and np.isfinite(a.diffuse_tail)):
+        raise SystemExit("make_paired_set: --diffuse-tail takes a positive number of milliseconds")
+    if tailed and a.tail_ramp < 1:
+        raise SystemExit("make_paired_set: --tail-ramp takes a count >= 1")
+    if tailed and a.mics > 8:
+        raise SystemExit("make_paired_set: --diffuse-tail with --mics takes at most 8 microphones")
+    if tailed and a.mics > 1 and not 1 <= a.tail_waves <= 4096:
+        raise SystemExit("make_paired_set: --tail-waves takes a count in 1..4096")
     files = list_clean(a.clean)
     if a.num > 0:
         files = files[:a.num]
@@ -205,18 +231,43 @@ def main(argv=None):
                 rm = rm_all[0]
             else:
                 rm_all = rm[None]
-            h, flags = rooms.shoebox_rir(torch.from_numpy(np.ascontiguousarray(rm_all)).to(a.device), a.fs, n, max_order=a.max_order)
+            rt = torch.from_numpy(np.ascontiguousarray(rm_all)).to(a.device)
+            if not tailed:
+                h, flags = rooms.shoebox_rir(rt, a.fs, n, max_order=a.max_order)
+            else:
+                try:
+                    h, flags, info = rooms.shoebox_rir_hybrid(rt, a.fs, n, nominal, np.array([rng.stream_key(a.seed, name)], dtype=np.uint32), a.diffuse_tail,
+                                                              a.tail_ramp, a.mics, a.tail_waves, a.noise_field, max_order=a.max_order)
+                except ValueError as e:
+                    raise SystemExit(f"make_paired_set: {name}: {e}")
             ac = acoustics.rir_acoustics(h[:1], a.fs)
-            rows += rooms.room_rows([name], rm[None], a.fs, n, ac, flags)
+            rows += rooms.room_rows([name], rm[None], a.fs, n, ac, flags & 1)
             if a.mics > 1:
                 rows[-1].update(mics=a.mics, array_radius=float(a.array_radius), array_angle=angle)
                 os.makedirs(os.path.join(a.out, "rir_array", spk), exist_ok=True)
                 wavfile.write(os.path.join(a.out, "rir_array", spk, uid + ".wav"), a.fs, np.ascontiguousarray(h.cpu().numpy().astype(np.float32).T))
         else:           # the longest band decides the length, and the bank's delay comes on top of it
             n = int(round((a.rir_seconds if a.rir_seconds is not None else 1.5 * float(band_t60[u].max())) * a.fs)) + delay
-            h, flags = rooms.shoebox_rir_bands(torch.from_numpy(rm[None]).to(a.device), band_beta[u:u + 1], a.fs, n, bank, air=air, max_order=a.max_order)
+            if not tailed:
+                h, flags = rooms.shoebox_rir_bands(torch.from_numpy(rm[None]).to(a.device), band_beta[u:u + 1], a.fs, n, bank, air=air, max_order=a.max_order)
+            else:
+                try:
+                    h, flags, info = rooms.shoebox_rir_bands(torch.from_numpy(rm[None]).to(a.device), band_beta[u:u + 1], a.fs, n, bank, air=air,
+                                                             max_order=a.max_order, t60s=band_t60[u:u + 1],
+                                                             keys=np.array([rng.stream_key(a.seed, name)], dtype=np.uint32), tail_ms=a.diffuse_tail,
+                                                             ramp=a.tail_ramp)
+                except ValueError as e:
+                    raise SystemExit(f"make_paired_set: {name}: {e}")
             ac = acoustics.rir_acoustics(h, a.fs, centres=centres)
-            rows += rooms.room_rows([name], rm[None], a.fs, n, ac, flags, bands=(centres, band_beta[u:u + 1]))
+            rows += rooms.room_rows([name], rm[None], a.fs, n, ac, flags & 1, bands=(centres, band_beta[u:u + 1]))
+        if tailed:
+            rows[-1].update(tail_ms=float(a.diffuse_tail), tail_direct=int(info["n_d"][0]), tail_start=int(info["n_x"][0]), tail_ramp=int(a.tail_ramp),
+                            ism_samples=int(info["ism_samples"]))
+            if a.bands is None:
+                rows[-1]["tail_amp"] = float(info["amp"][0, 0])
+            else:
+                rows[-1].update({"tail_amp_" + rooms.band_label(f): float(info["amp"][0, k]) for k, f in enumerate(centres)})
+            rows[-1]["tail_flags"] = int(flags[0]) & (rooms.TAIL_PURE | rooms.TAIL_ZERO)
         for sub, v in (("clean", xt), ("rir", h[0])):
             os.makedirs(os.path.join(a.out, sub, spk), exist_ok=True)
             wavfile.write(os.path.join(a.out, sub, spk, uid + ".wav"), a.fs, v.cpu().numpy().astype(np.float32))
