@@ -231,6 +231,12 @@ _SIGS = {
                                  C.c_void_p, C.c_void_p, C.c_void_p]),
     "buddy_tail_mix": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_longlong, C.c_void_p, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p]),
+    "buddy_compare_max_pairs": (C.c_int, []),
+    "buddy_compare_bootstrap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_uint, C.c_void_p, C.c_void_p]),
+    "buddy_compare_select": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "buddy_compare_signflip": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_uint, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "buddy_compare_count_ge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p]),
     "buddy_denoise_frames": (C.c_longlong, [C.c_longlong]),
     "buddy_denoise_spectra": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_longlong, _f32p, C.c_longlong, C.c_void_p]),
     "buddy_denoise_gains": (C.c_int, [_f32p, C.c_void_p, C.c_void_p, C.c_int, C.c_longlong, C.c_int, C.c_double, _f32p, _f32p, C.c_void_p]),

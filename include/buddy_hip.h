@@ -924,6 +924,37 @@ int buddy_tail_mix(const void* u, int f64, int B, int nb, int D, long long ldr, 
                    const double* delta /* (G,nb) */, const double* amp /* (B,nb) */, const float* z /* (B,ldz) or NULL */, long long ldz,
                    const unsigned* keys /* (B,2) or NULL */, unsigned purpose, int fs, int N, void* out, long long ldor, long long ldok, void* stream);
 
+/* ---- paired comparison of two runs (buddy_amd/utils/compare.py, csrc/compare.hip; no reference counterpart): the resampling
+ * behind bootstrap intervals and the sign-flip randomisation test of columns of paired differences.  A call holds C ragged columns of finite doubles,
+ * element j of column c at d[c ld + j], j < lens[c]; lens: DEVICE (C,) ints, read once on the host to be checked; keys: DEVICE (C, 2) uint32, the Philox
+ * stream of each column (utils/rng.py: sample i of draw q of purpose p is word i & 3 of the block with counter (i >> 2, q, p, 0)).  A column's bits
+ * depend on its own data, length, key and draw0 only: not on C, on its position or on the other columns.  All sums have one association whatever the
+ * call.  buddy_compare_max_pairs() = 8192: the longest column (the bootstrap's LDS counters).
+ *   buddy_compare_bootstrap: s holds each column SORTED ascending.  Resample r < R draws n = lens[c] ranks, rank j = (w_j n) >> 32 in 64-bit integers
+ * with w_j sample j of draw draw0 + r of purpose 11 (bias of a rank's probability at most n / 2^32), counted in cnt[k] (integer LDS atomics).
+ * out: DEVICE (C, 2, R) doubles; out[c][0][r] = (sum_k cnt[k] s[k]) / n, thread t of 256 adding k = t, t + 256, ... ascending, then lanes and waves in
+ * the fixed order of the evaluation entries; out[c][1][r] = the median of the drawn values by numpy's rule, s[k_m] for odd n and (s[k_a] + s[k_b]) * 0.5
+ * for even n, the ranks found in the prefix sum of cnt: integer work, exact.  One workgroup per (resample, column).
+ *   buddy_compare_select: out[m][q] = the element of rank ranks[q] (0-based, ascending) of row m of x (M rows of R doubles, row stride ldx), by an
+ * 8-bit radix select on the order-preserving 64-bit key: exact, any R; -0 ranks below +0; no NaN.  ranks: DEVICE (K,) ints; out: DEVICE (M, K).
+ *   buddy_compare_signflip: T[c][r] = sum_j sigma_rj d[c][j], j ascending in one double accumulator, the sign applied by negation.  modes: DEVICE (C,)
+ * ints.  Mode 0 (random): r < P, sigma_rj = -1 where bit j & 31 of sample j >> 5 of draw draw0 + r of purpose 12 is set.  Mode 1 (exhaustive):
+ * r < 2^n, sigma_rj = -1 where bit j of r is set; T[c][r] for r >= 2^n is not written.  T: DEVICE (C, P) doubles; tobs: DEVICE (C,) doubles, the same
+ * loop with every sign +, the bits of pattern 0 of mode 1.  One thread per pattern.
+ *   buddy_compare_count_ge: out[c] = #{r < counts[c] : |T[c][r]| >= thr[c]}, T rows of stride ldt; counts: DEVICE (C,) ints; thr: DEVICE (C,) doubles;
+ * out: DEVICE (C,) 64-bit integers.  Exact.
+ * BUDDY_ERR_ARG, with nothing launched, for: a null pointer; C, M or K outside 1..65535; R outside 1..2^24 (select: R < 1); P outside 1..2^30;
+ * draw0 + R (or + P) above 2^32; a length outside 1..buddy_compare_max_pairs(); ld below a length; ldx < R; a rank outside 0..R-1; a mode other than
+ * 0 or 1; an exhaustive column with 2^n > P; a count outside 1..ldt.  No workspace; nothing outside the stated extents is written. */
+int buddy_compare_max_pairs(void);
+int buddy_compare_bootstrap(const double* s /* (C,ld) */, const int* lens /* (C,) */, const unsigned* keys /* (C,2) */, int C, long long ld, int R,
+                            unsigned draw0, double* out /* (C,2,R) */, void* stream);
+int buddy_compare_select(const double* x /* (M,ldx) */, int M, int R, long long ldx, const int* ranks /* (K,) */, int K, double* out /* (M,K) */, void* stream);
+int buddy_compare_signflip(const double* d /* (C,ld) */, const int* lens /* (C,) */, const int* modes /* (C,) */, const unsigned* keys /* (C,2) */, int C,
+                           long long ld, int P, unsigned draw0, double* T /* (C,P) */, double* tobs /* (C,) */, void* stream);
+int buddy_compare_count_ge(const double* T /* (C,ldt) */, const int* counts /* (C,) */, const double* thr /* (C,) */, int C, long long ldt,
+                           long long* out /* (C,) */, void* stream);
+
 /* ---- noise power tracker and spectral post-filter of noisy recordings (buddy_amd/utils/denoise.py, csrc/denoise.hip; Gerkmann &
  * Hendriks 2012, Ephraim & Malah 1984 / 1985; no reference counterpart).  The conventions of the evaluation entries hold: ragged rows inside a common
  * stride, a DEVICE length array copied to the host once to be checked, nothing behind a row's end read, nothing outside the declared extents written,
