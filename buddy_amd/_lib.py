@@ -103,6 +103,12 @@ _SIGS = {
                                             C.c_longlong, C.c_void_p, C.c_void_p]),
     "buddy_srmr_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "buddy_decay_regions_tile": (C.c_int, []),
+    "buddy_decay_energies": (C.c_int, [_f32p, C.c_void_p, C.c_int, C.c_longlong, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_longlong,
+                                       C.c_void_p, C.c_void_p]),
+    "buddy_decay_regions": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "buddy_decay_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]),
     "buddy_level_tile": (C.c_int, []),
     "buddy_level_counts_tile": (C.c_int, []),
     "buddy_level_stats_workspace": (C.c_longlong, [C.c_int, C.c_longlong]),

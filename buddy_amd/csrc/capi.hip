@@ -992,6 +992,49 @@ int buddy_srmr_scores(const double* E, const int* frames, int B, int J, int K, l
   return finish();
 }
 
+// ---- blind decay time of single signals (decay.hip) ----
+int buddy_decay_regions_tile(void) { return decay_regions_tile(); }
+
+int buddy_decay_energies(const float* x, const int* lens, int B, long long ld, const int* lo_bins, const int* hi_bins, int NB, double* E, long long ldm,
+                         int* frames, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_decay_energies: ") + why); return BUDDY_ERR_ARG; };
+  if (!x || !lens || !lo_bins || !hi_bins || !E || !frames) return bad("null pointer");
+  if (NB < 1 || NB > 8) return bad("NB must be in 1..8");
+  for (int i = 0; i < NB; ++i)
+    if (lo_bins[i] < 0 || hi_bins[i] < lo_bins[i] || hi_bins[i] > decay_bins()) return bad("every band must be a bin range 0 <= lo <= hi <= 257");
+  int longest;
+  if (int rc = check_rows(lens, B, ld, 1, stream, "buddy_decay_energies", &longest)) return rc;
+  const long long maxF = frames_of(longest, decay_frame(), decay_hop());
+  if (ldm < at_least_one(maxF)) return bad("ldm is smaller than the frames of the longest row");
+  launch_decay_energies(x, lens, B, ld, maxF, lo_bins, hi_bins, NB, E, ldm, frames, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_decay_regions(const double* E, const int* frames, int B, int NB, long long ldm, int K, int lmin, double q, double floor_rel, double* T, int* len,
+                        void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_decay_regions: ") + why); return BUDDY_ERR_ARG; };
+  if (!E || !frames || !T || !len) return bad("null pointer");
+  if (NB < 1 || NB > 8) return bad("NB must be in 1..8");
+  if (K < 1 || K > 8) return bad("K must be in 1..8");
+  if (lmin < 2) return bad("lmin must be >= 2");
+  if (!(q > 0.0 && q <= 1.0)) return bad("q must be in (0, 1]");
+  if (!(floor_rel >= 0.0 && floor_rel < 1.0)) return bad("floor_rel must be in [0, 1)");
+  int longest;
+  if (int rc = check_rows(frames, B, ldm, 0, stream, "buddy_decay_regions", &longest)) return rc;
+  launch_decay_regions(E, frames, B, NB, ldm, K, lmin, q, floor_rel, T, len, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_decay_select(const double* T, const int* frames, int B, int NB, long long ldm, double* out, int* counts, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_decay_select: ") + why); return BUDDY_ERR_ARG; };
+  if (!T || !frames || !out || !counts) return bad("null pointer");
+  if (NB < 1 || NB > 8) return bad("NB must be in 1..8");
+  int longest;
+  if (int rc = check_rows(frames, B, ldm, 0, stream, "buddy_decay_select", &longest)) return rc;
+  launch_decay_select(T, frames, B, NB, ldm, out, counts, (hipStream_t)stream);
+  return finish();
+}
+
 // ---- active speech level of single signals (level.hip) ----
 int buddy_level_tile(void) { return level_tile(); }
 int buddy_level_counts_tile(void) { return level_counts_tile(); }

@@ -234,6 +234,17 @@ void launch_modulation_energies(const float* env, const int* lens, int B, int J,
                                 int* frames, hipStream_t st);
 void launch_srmr_scores(const double* E, const int* frames, int B, int J, long long ldm, const double* erb, const double* l, double* out, double* Ebar, int* flags,
                         hipStream_t st);
+// blind decay time of single signals (decay.hip): ragged rows, device length and frame-count arrays; arguments, lengths and strides
+// are checked by the C entries, which pass the most frames of a row (max_frames) for the grid.  lo, hi: host arrays of NB <= 8 bin ranges
+int decay_regions_tile();                    // frames per LDS tile of the region kernel
+int decay_frame();
+int decay_hop();
+int decay_bins();                            // 257: a band's bins lie in 0..257
+void launch_decay_energies(const float* x, const int* lens, int B, long long ld, long long max_frames, const int* lo, const int* hi, int NB, double* E, long long ldm,
+                           int* frames, hipStream_t st);
+void launch_decay_regions(const double* E, const int* frames, int B, int NB, long long ldm, int K, int lmin, double q, double floor_rel, double* T, int* len,
+                          hipStream_t st);
+void launch_decay_select(const double* T, const int* frames, int B, int NB, long long ldm, double* out, int* counts, hipStream_t st);
 // active speech level of single signals (level.hip): ragged rows, device length arrays; arguments, lengths, strides and
 // workspaces are checked by the C entries, which pass the longest row (max_len) for the grids.  offset (or null), ref: device doubles per row
 int level_tile();                            // samples per workgroup of the envelope kernels

@@ -7,9 +7,8 @@
 //             has no order.  Mean: thread t adds cnt[k] s[k] over k = t, t + 256, ... ascending in double, then the fixed-order workgroup sum of
 //             reduce.h, / n.  Median: each thread owns CH consecutive counters (CH odd: conflict-free LDS strides), a workgroup scan of the CH-sums
 //             gives every thread the count before its chunk, and the thread whose chunk holds sorted position (n - 1) / 2 (and n / 2) walks to it.
-//   select    one workgroup per (rank, row): 8-bit radix select on the order-preserving 64-bit key of a double, most significant byte first.  A
-//             pass counts the byte of the elements that share the prefix found so far (256 LDS counters), a scan finds the byte at which the
-//             count passes the rank.  After eight passes the key is the element: exact for any R, no copy of the row.
+//   select    one workgroup per (rank, row): the 8-bit radix select of select.h on the order-preserving 64-bit key of a double.  After eight
+//             passes the key is the element: exact for any R, no copy of the row.
 //   signflip  one thread per pattern: T = sum_j (+-) d[j], j ascending, one accumulator in double (the signs are applied by negation: no product,
 //             nothing to contract).  Random columns take bit j & 31 of sample j >> 5 of draw draw0 + r of purpose 12 (one Philox block per 128
 //             elements), exhaustive columns bit j of r.  Pattern 0 of the first workgroup also runs the same loop with all signs + into tobs.
@@ -19,6 +18,7 @@
 #include "net.h"
 #include "philox.h"
 #include "reduce.h"
+#include "select.h"
 
 #include <cmath>
 #include <cstring>
@@ -32,25 +32,7 @@ constexpr int CP_T = 256;                     // threads per workgroup
 constexpr int CP_MAXN = 8192;                 // pairs per column at most: 32 KiB of LDS counters
 constexpr unsigned CP_BOOT = 11, CP_SIGN = 12;   // purposes of the two draws (utils/compare.py COMPARE_BOOT, COMPARE_SIGN)
 
-// exclusive prefix of one unsigned per thread over the workgroup (thread order); ``ws`` holds the wave totals
-__device__ __forceinline__ unsigned block_excl_scan(unsigned v, unsigned (&ws)[CP_T / 64], int tid, unsigned* total) {
-  const int lane = tid & 63, wave = tid >> 6;
-  unsigned inc = v;
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned o = __shfl_up(inc, off);
-    if (lane >= off) inc += o;
-  }
-  __syncthreads();                            // the previous use of ws has been read
-  if (lane == 63) ws[wave] = inc;
-  __syncthreads();
-  unsigned before = 0, all = 0;
-  for (int w = 0; w < CP_T / 64; ++w) {
-    if (w < wave) before += ws[w];
-    all += ws[w];
-  }
-  if (total) *total = all;
-  return before + inc - v;
-}
+static_assert(CP_T == SEL_T, "the scan and the select of select.h run on workgroups of 256 threads");
 
 __global__ __launch_bounds__(CP_T) void boot_kernel(const double* __restrict__ s, long long ld, const int* __restrict__ lens,
                                                     const uint32_t* __restrict__ keys, int R, uint32_t draw0, double* __restrict__ out) {
@@ -104,44 +86,14 @@ __global__ __launch_bounds__(CP_T) void boot_kernel(const double* __restrict__ s
   }
 }
 
-// the order-preserving key of a double: negative values complemented, the others with the sign bit set (-0 sorts below +0)
-__device__ __forceinline__ unsigned long long key_of(double x) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-
-__device__ __forceinline__ double value_of(unsigned long long k) {
-  const unsigned long long b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-  return __longlong_as_double((long long)b);
-}
-
 __global__ __launch_bounds__(CP_T) void select_kernel(const double* __restrict__ x, long long ldx, int R, const int* __restrict__ ranks, int K,
                                                       double* __restrict__ out) {
   __shared__ unsigned hist[256];
   __shared__ unsigned ws[CP_T / 64];
   __shared__ unsigned pick[2];
   const int q = blockIdx.x, m = blockIdx.y, tid = threadIdx.x;
-  const double* row = x + (long long)m * ldx;
-  unsigned long long prefix = 0;              // the bytes found so far, in place
-  unsigned rank = (unsigned)ranks[q];
-  for (int pass = 0; pass < 8; ++pass) {
-    const int shift = 56 - 8 * pass;
-    hist[tid] = 0u;
-    __syncthreads();
-    for (int i = tid; i < R; i += CP_T) {
-      const unsigned long long k = key_of(row[i]);
-      if (pass == 0 || (k >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(unsigned)(k >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    const unsigned mine = hist[tid];
-    const unsigned before = block_excl_scan(mine, ws, tid, nullptr);
-    if (rank >= before && rank < before + mine) { pick[0] = (unsigned)tid; pick[1] = rank - before; }
-    __syncthreads();
-    prefix |= (unsigned long long)pick[0] << shift;
-    rank = pick[1];
-    __syncthreads();                          // pick and hist are free for the next pass
-  }
-  if (tid == 0) out[(long long)m * K + q] = value_of(prefix);
+  const double v = radix_select<false>(x + (long long)m * ldx, R, (unsigned)ranks[q], hist, ws, pick, tid);
+  if (tid == 0) out[(long long)m * K + q] = v;
 }
 
 // MODE 0: the signs of a random pattern, 1: of an exhaustive one, 2: all +

@@ -40,4 +40,17 @@ __device__ __forceinline__ void block_sum(double (&v)[K], double (&lds)[NW][K], 
     v[q] = s;
   }
 }
+
+// the maximum over a workgroup of NW waves, in every thread: the same butterfly and the same wave order (a maximum has one value in any order; the
+// fixed order keeps a NaN's path fixed too).  ``lds`` may be reused by the next call: the leading barrier covers it
+template <int NW>
+__device__ __forceinline__ double block_max(double v, double (&lds)[NW], int tid) {
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
+  __syncthreads();                            // the previous use of lds has been read
+  if ((tid & 63) == 0) lds[tid >> 6] = v;
+  __syncthreads();
+  double s = lds[0];
+  for (int w = 1; w < NW; ++w) s = fmax(s, lds[w]);
+  return s;
+}
 }  // namespace buddy

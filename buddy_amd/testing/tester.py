@@ -111,6 +111,12 @@ def srmr_options(tester_cfg):
     return False if sm is None else bool(sm.get("use", False))
 
 
+def decay_options(tester_cfg):
+    """use of the ``decay`` block of a tester config; a config written before the block existed means False"""
+    dc = tester_cfg.get("decay", None)
+    return False if dc is None else bool(dc.get("use", False))
+
+
 def spectral_options(tester_cfg):
     """(use, values) of the ``spectral`` block of a tester config; a config written before the block existed means (False, all three values)"""
     from ..utils.spectral import VALUES
@@ -237,8 +243,9 @@ class Tester:
         scoring = metrics_options(self.args.tester)[0] and not self.in_training and bool(self.paths)
         scored = []      # evaluation and spectral reports: (name, clean, degraded, reconstructed) per written utterance, as written to the wavs
         spectral_on = spectral_options(self.args.tester)[0] and not self.in_training and bool(self.paths)
+        decay_on = decay_options(self.args.tester) and not self.in_training and bool(self.paths)
         srmr_on = srmr_options(self.args.tester) and not self.in_training and bool(self.paths)
-        heard = []     # SRMR report: (name, degraded, reconstructed, clean) per written utterance, each row with the rate of its wav
+        heard = []     # SRMR and decay-time reports: (name, degraded, reconstructed, clean) per written utterance, each row with the rate of its wav
         for s in range(0, len(mine), self.batch_size):
             idx = mine[s:s + self.batch_size]
             items = [self.test_set[i] + (i,) for i in idx]
@@ -275,7 +282,7 @@ class Tester:
                         rep.append((name, est[b] if est.dim() == 2 else est, rirs[b], {k: v if k == "freqs" else v[b] for k, v in par.items()}))
                     if scoring or spectral_on:
                         scored.append((name, seg[b].detach(), y[b].detach(), pred[b].detach()))
-                    if srmr_on:
+                    if srmr_on or decay_on:
                         heard.append((name, (y[b].detach(), sr), (pred[b].detach(), sr), (seg[b].detach(), sr)))
                     print(p)
         if report:
@@ -286,6 +293,8 @@ class Tester:
             self._write_spectral_report(mode, scored, sr)
         if srmr_on:
             self._write_srmr_report(mode, heard)
+        if decay_on:
+            self._write_decay_report(mode, heard)
         # utterance-batch data parallelism: ONE gather at the end of the run (RCCL over xGMI on the GPU box) -- afterwards every rank, in
         # particular rank 0, holds all predictions in utterance order, independent of the world size
         from .. import dist as bdist
@@ -385,6 +394,23 @@ class Tester:
         srmr.write_report(os.path.join(self.paths[mode], f"srmr{tag}.csv"), rows)
         srmr.write_report(os.path.join(self.paths[mode], f"srmr_summary{tag}.csv"), srmr.summary_rows(rows))
         self.srmr_report = rows
+
+    def _write_decay_report(self, mode, items):
+        """Decay-time report of a mode (``tester.decay.use``; utils/decay.py), once per mode after sampling: ``decay.csv`` (per
+        written utterance the blind decay time of the degraded and of the reconstructed signal, broadband and per octave band, their difference, the
+        kept regions, the spread and the flags, and in a paired mode the clean signal's, the floor speech itself sets) and ``decay_summary.csv`` (n,
+        mean, median, std per decay-time column) in the mode's directory.  ``items`` as in ``_write_srmr_report``; rank-tagged names as there."""
+        from ..utils import decay
+        self.decay_report = None
+        if not items:
+            return
+        paired = items[0][3] is not None
+        cols = [decay.score_signals([(it[k][0].flatten().float(), it[k][1]) for it in items], self.device) for k in ((1, 2, 3) if paired else (1, 2))]
+        rows = decay.report_rows([it[0] for it in items], cols[0], cols[1], cols[2] if paired else None)
+        tag = f".rank{self.rank}" if self.world_size > 1 else ""
+        decay.write_report(os.path.join(self.paths[mode], f"decay{tag}.csv"), rows)
+        decay.write_report(os.path.join(self.paths[mode], f"decay_summary{tag}.csv"), decay.summary_rows(rows))
+        self.decay_report = rows
 
     def _sample_concurrent(self, grp, L, blind, S):
         """one equal-length group as ``S`` concurrent sub-batches (testing/concurrent.py)"""
@@ -548,7 +574,8 @@ class Tester:
             dnz.write_report(os.path.join(self.paths[mode], "denoise.csv" if self.world_size == 1 else f"denoise.rank{self.rank}.csv"), dn_rows)
         report = writing and rir_report_options(self.args.tester)[0]
         srmr_on = writing and srmr_options(self.args.tester)
-        heard = []     # SRMR report: (name, degraded at the model's rate, reconstructed at its own rate, no clean signal) per written file
+        decay_on = writing and decay_options(self.args.tester)
+        heard = []     # SRMR and decay-time reports: (name, degraded at the model's rate, reconstructed at its own rate, no clean signal) per written file
         for batch in batches:
             yb = torch.stack([files[f]["parts"][k] for f, k in batch])
             pred, est = self.sample_observed(yb, [f"{files[f]['name']}_c{k}.wav" for f, k in batch],
@@ -579,7 +606,7 @@ class Tester:
             if dn_use:                                # what the sampler observed
                 write_audio_file(f["y"], sr, f["name"], path=self.paths[mode + "denoised"])
             p = write_audio_file(pred, f["fs"] if to_input_rate else sr, f["name"], path=self.paths[mode + "reconstructed"])
-            if srmr_on:
+            if srmr_on or decay_on:
                 heard.append((f["name"], (degraded.detach(), sr), (pred.detach(), f["fs"] if to_input_rate else sr), None))
             if shared:       # one estimate per file (per run where shared_rir_max_chunks cut it): the chunks of a run hold the same RIR
                 for j, (lo, _) in enumerate(f["runs"]):
@@ -594,6 +621,8 @@ class Tester:
             self._write_rir_report(mode, rep, sr)
         if srmr_on:
             self._write_srmr_report(mode, heard)
+        if decay_on:
+            self._write_decay_report(mode, heard)
 
     def _observed_channel(self, i, ch_mode, ref_ch, wpe_hp, sr, bf_hp=None):
         """file ``i`` read with its channels unmixed (``real_recordings.channels: reference | wpe``) -> (observed signal, reference channel as

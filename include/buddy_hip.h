@@ -761,6 +761,38 @@ int buddy_modulation_energies(const float* env, const int* lens, int B, int J, l
 int buddy_srmr_scores(const double* E, const int* frames, int B, int J, int K, long long ldm, const double* erb /*host*/, const double* l /*host*/, double* out,
                       double* Ebar, int* flags, void* stream);
 
+/* ---- blind decay time of single signals (buddy_amd/utils/decay.py, csrc/decay.hip; no reference counterpart): the decay time,
+ * extrapolated to 60 dB, of a signal's own free decays after speech offsets, per band.  The conventions of the evaluation entries above hold: ragged rows
+ * inside a common stride, DEVICE length and frame-count arrays copied to the host once to be checked, nothing behind a row's end read, nothing outside the
+ * declared extents written, fixed-order double sums without floating-point atomics, a row's bits independent of its batch.  The analysis is defined at
+ * 16 kHz: frames of 512 samples at hop 128.
+ * BUDDY_ERR_ARG, with nothing launched, for: a null pointer; B outside 1..65535; a length outside 1..2^30 (0..2^30 for frame counts); a stride smaller
+ * than the longest row it holds; NB outside 1..8; the limits named per entry.
+ *
+ * buddy_decay_energies: frames[b] = M = (lens[b] - 512) / 128 + 1 full frames (0 below 512 samples); E (B, NB, ldm) doubles, E[b][i][m] = sum over the bins
+ *   lo_bins[i] <= k < hi_bins[i], ascending in one double accumulator, of |X[k]|^2, X the 512-point transform (fp32, radix 2, the transform and window of
+ *   buddy_frame_spectra) of frame m < M; the squares are taken in double.  lo_bins, hi_bins: HOST arrays of NB ints, 0 <= lo <= hi <= 257 (lo = hi: an
+ *   empty band, E = 0).  ldm >= max(frames, 1).  Four frames per workgroup; entries m >= M are not written.
+ *
+ * buddy_decay_regions: S[m] = (((E[m] + E[m+1]) + E[m+2]) + ...) + E[m+K-1] for m <= M - K; floor = floor_rel * max_m S[m]; frame m steps down when
+ *   S[m+1] < S[m] and S[m+1] > floor.  A region is a maximal run of steps at frames m0 .. m1 - 1; it spans the m1 - m0 + 1 values S[m0] .. S[m1] and is
+ *   kept when that number is >= lmin, S[m0] > floor and S[m1] <= S[m0] * q (doubles compared, no logarithm).  Its slope is the least-squares fit of
+ *   d[j] = 10 log10(S[m0+j] / S[m0]) against j = 0 .. m1 - m0, the sums in double in ascending j, no product fused into a sum; its value is
+ *   -60 / slope * 128 / 16000 seconds (dropped should the slope not be negative).  T, len (B, NB, ldm): T[b][i][m0] = the value and len[b][i][m0] =
+ *   m1 - m0 + 1 where a kept region starts, NaN and 0 at every other frame m < M; nothing at m >= M.  K in 1..8, lmin >= 2, 0 < q <= 1,
+ *   0 <= floor_rel < 1.  buddy_decay_regions_tile: the frames per LDS tile of the walk (the frame counts around which the unit tests place their
+ *   rows; buddy_decay_tile above belongs to buddy_decay_metrics).
+ *
+ * buddy_decay_select: counts (B, NB) ints = n, the entries of T[b][i][0 .. frames[b] - 1] that are not NaN; out (B, NB, 3) doubles = their order statistics
+ *   of rank (n - 1) / 2, (n - 1) / 4 and 3 (n - 1) / 4 (integer divisions; 0-based, ascending): the lower median and the quartiles, by an exact radix
+ *   select; three NaN where n = 0.  B * NB workgroups per rank. */
+int buddy_decay_regions_tile(void);
+int buddy_decay_energies(const float* x, const int* lens, int B, long long ld, const int* lo_bins /*host*/, const int* hi_bins /*host*/, int NB, double* E,
+                         long long ldm, int* frames, void* stream);
+int buddy_decay_regions(const double* E, const int* frames, int B, int NB, long long ldm, int K, int lmin, double q, double floor_rel, double* T, int* len,
+                        void* stream);
+int buddy_decay_select(const double* T, const int* frames, int B, int NB, long long ldm, double* out, int* counts, void* stream);
+
 /* ---- active speech level of single signals (buddy_amd/utils/level.py; ITU-T P.56 method B as restated there; no reference
  * counterpart).  The conventions of the evaluation entries above hold: ragged rows inside a common stride, DEVICE length arrays copied to the host once
  * to be checked, nothing at or behind lengths[b] read or written, fixed-order sums without atomics, a row's result independent of B, of the grid and of
