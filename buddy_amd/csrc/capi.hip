@@ -10,21 +10,6 @@
 
 using namespace buddy;
 
-namespace buddy {
-void launch_axpby_rows(const float* x, const float* y, const float* a, const float* c, float* out, int B, int L, hipStream_t st);
-void launch_row_moments(const float* x, double* out, int B, int L, hipStream_t st);
-void launch_perturb(const float* x, const float* eps, float scale, float* out, long long n, hipStream_t st);
-void launch_dps_update(const float* x_hat, const float* x_den, const float* lh, const float* lh_scale_b, const float* den_scale_b, const float* base, const float* d_prev,
-                       float t, float dt, float w_prev, float w_cur, float* out, float* d_out, float* x_den_out, int B, int L, hipStream_t st);
-void launch_row_scale(const float* x, float* out, int B, int L, int mode, float p0, float p1, hipStream_t st);
-void launch_fill_rows4(float* out, int B, float v0, float v1, float v2, float v3, hipStream_t st);
-void launch_mfma_ubench(const float* seed, float* out, int blocks, int iters, unsigned long long* clk, hipStream_t st);
-void launch_mfma_ubench_bf16(const float* seed, float* out, int blocks, int iters, unsigned long long* clk, hipStream_t st);
-int launch_hbm_ubench(const void* src, void* dst, long long bytes, int mode, int nt, int blocks, hipStream_t st);
-void launch_fir(const float* x, const float* h, long long h_stride, float* y, int B, int L, int M, int adjoint, hipStream_t st);
-void launch_transpose_sq(const float* src, float* dst, int batch, int n, hipStream_t st);
-}
-
 static int finish() {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { set_error(std::string("kernel launch: ") + hipGetErrorString(e)); return BUDDY_ERR_HIP; }

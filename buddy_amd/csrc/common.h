@@ -306,6 +306,20 @@ void launch_softmax_bwd_rows(const float* P, float* dP /*in: dP, out: dS*/, int 
 void launch_linear(const float* x, const float* W, const float* b, float* y, int B, int K, int N, int silu_in, hipStream_t st);
 void launch_fourier(const float* cnoise, const float* Wf, float* out, int B, int nf, hipStream_t st);
 void launch_mix2(const float* x, const float* w /*[2][2]*/, const float* b, float* y, long long npix, int transpose, int accumulate, hipStream_t st);
+void launch_transpose_sq(const float* src, float* dst, int batch, int n, hipStream_t st);   // dst[b] = src[b]^T, n x n, n % 32 == 0
+
+// ---- sampler steps, time-domain FIR, calibration loops (sampler.hip) -----------------------------------------
+void launch_axpby_rows(const float* x, const float* y, const float* a, const float* c, float* out, int B, int L, hipStream_t st);
+void launch_row_moments(const float* x, double* out, int B, int L, hipStream_t st);
+void launch_perturb(const float* x, const float* eps, float scale, float* out, long long n, hipStream_t st);
+void launch_dps_update(const float* x_hat, const float* x_den, const float* lh, const float* lh_scale_b, const float* den_scale_b, const float* base, const float* d_prev,
+                       float t, float dt, float w_prev, float w_cur, float* out, float* d_out, float* x_den_out, int B, int L, hipStream_t st);
+void launch_row_scale(const float* x, float* out, int B, int L, int mode, float p0, float p1, hipStream_t st);
+void launch_fill_rows4(float* out, int B, float v0, float v1, float v2, float v3, hipStream_t st);
+void launch_fir(const float* x, const float* h, long long h_stride, float* y, int B, int L, int M, int adjoint, hipStream_t st);
+void launch_mfma_ubench(const float* seed, float* out, int blocks, int iters, unsigned long long* clk, hipStream_t st);
+void launch_mfma_ubench_bf16(const float* seed, float* out, int blocks, int iters, unsigned long long* clk, hipStream_t st);
+int launch_hbm_ubench(const void* src, void* dst, long long bytes, int mode, int nt, int blocks, hipStream_t st);
 
 // ---- STFT / iSTFT glue ------------------------------------------------------------------------------------
 void launch_reflect_pad(const float* x, float* xp, int B, int L, int pad, int Lp, float scale, const float* scale_b, hipStream_t st);

@@ -1952,7 +1952,6 @@ int blindop_rec_loss_grad(BlindOp* o, const float* x_den, float weight, float* l
 
 // informed likelihood (reference RIROperator.degradation = fast_apply_RIR, reverb.py:33-35, + the same STFT loss): time-domain FIR with the
 // known RIR (U, M) instead of the subband filter; loss_u = weight * l2_comp_stft_summean(y, x_den * rir), g = d sum_u loss_u / d x_den
-void launch_fir(const float* x, const float* h, long long h_stride, float* y, int B, int L, int M, int adjoint, hipStream_t st);
 int blindop_fir_loss_grad(BlindOp* o, const float* x_den, const float* rir, long long rir_stride, int M, float weight, float* loss, float* g_x,
                           hipStream_t st) {
   o->st = st;

@@ -3,7 +3,6 @@ fixtures recorded by tests/golden/make_golden_attn.py), parameter counts of the 
 construction and forward would disagree, the config / checkpoint surface.  No GPU needed."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -104,10 +103,6 @@ def test_instantiate_override_and_checkpoint_load():
 
 def test_header_and_exports_agree():
     from buddy_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "buddy_hip.h")).read()
-    declared = set(re.findall(r"\b(buddy_[A-Za-z0-9_]+)\s*\(", hdr))
-    assert {"buddy_ncsnpp_param_count_attn", "buddy_ncsnpp_create_attn"} <= declared
-    assert declared == set(_lib.EXPORTED), declared ^ set(_lib.EXPORTED)
     lib = _lib.load()
-    for name in declared:
-        assert hasattr(lib, name)
+    for name in ("buddy_ncsnpp_param_count_attn", "buddy_ncsnpp_create_attn"):       # header = signatures = exports: tests/test_abi_host.py
+        assert name in _lib.EXPORTED and hasattr(lib, name)

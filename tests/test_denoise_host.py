@@ -30,11 +30,10 @@ RULES = ("wiener", "lsa")
 
 # ---- symbols, the frame rule, refusals --------------------------------------------------------------------------------------------------------------
 def test_new_symbols_are_declared_bound_and_exported():
-    header = open(os.path.join(ROOT, "include", "buddy_hip.h")).read()
     lib = _lib.load()
     for name in ENTRIES:
-        assert name + "(" in header and name in _lib.EXPORTED and getattr(lib, name) is not None
-    assert "denoise" in open(os.path.join(ROOT, "buddy_amd", "csrc", "build.sh")).read().split()
+        assert name in _lib.EXPORTED and getattr(lib, name) is not None       # header = signatures = exports: tests/test_abi_host.py
+    assert os.path.isfile(os.path.join(ROOT, "buddy_amd", "csrc", "denoise.hip"))          # build.sh compiles and links every csrc/*.hip
     assert (D.N, D.HOP, D.PAD, D.BINS) == (R.N, R.H, R.P, R.BINS) == (512, 128, 384, 257)
     assert (D.ZERO, D.SHORT, D.NO_SPEECH) == (R.ZERO, R.SHORT, R.NO_SPEECH) and D.ROW_FLOOR == R.FLOOR and D.GAINS == RULES
 

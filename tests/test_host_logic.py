@@ -34,12 +34,7 @@ def test_config_access_idioms():
 
 def test_library_exports_declared_symbols():
     from buddy_amd import _lib
-    lib = _lib.load()
-    hdr = open(os.path.join(ROOT, "include", "buddy_hip.h")).read()
-    declared = set(re.findall(r"\b(buddy_[A-Za-z0-9_]+)\s*\(", hdr))
-    assert declared == set(_lib.EXPORTED), declared ^ set(_lib.EXPORTED)
-    for name in declared:
-        assert hasattr(lib, name)
+    lib = _lib.load()                              # header = signatures = exports, for every name: tests/test_abi_host.py
     assert lib.buddy_version() >= 1
     cm = (ctypes.c_int * 4)(1, 2, 2, 2)
     n = ctypes.c_longlong()

@@ -32,14 +32,12 @@ def table_room(L, s, r, t60):
 
 # ---- symbols, windows, refusals -----------------------------------------------------------------------------------------------------------------
 def test_new_symbols_are_declared_bound_and_exported():
-    header = open(os.path.join(ROOT, "include", "buddy_hip.h")).read()
     lib = _lib.load()
     for name in ("buddy_tail_fit", "buddy_tail_mix", "buddy_tail_tile"):
-        assert name + "(" in header and name in _lib.EXPORTED and getattr(lib, name) is not None
+        assert name in _lib.EXPORTED and getattr(lib, name) is not None       # header = signatures = exports: tests/test_abi_host.py
     assert lib.buddy_tail_tile() == 1024 and rooms.TAIL == 10 == NZ.NOISE_SENSOR + 1 and TR.HW == lib.buddy_ism_half_width()
     assert (rooms.TAIL_PURE, rooms.TAIL_ZERO) == (TR.PURE, TR.ZERO) == (2, 4)
-    src = open(os.path.join(ROOT, "buddy_amd", "csrc", "build.sh")).read()
-    assert " tail " in src and "obj/tail.o" in src
+    assert os.path.isfile(os.path.join(ROOT, "buddy_amd", "csrc", "tail.hip"))             # build.sh compiles and links every csrc/*.hip
 
 
 def test_tail_window_by_hand():
