@@ -930,6 +930,44 @@ int buddy_align_pair(const float* e, const float* x, const int* lens, const int*
   return finish();
 }
 
+// ---- projection SDR of a pair over filter lengths (sdr.hip) ----
+int buddy_sdr_tile(void) { return sdr_tile(); }
+int buddy_sdr_lag_tile(void) { return sdr_lag_tile(); }
+
+long long buddy_sdr_products_workspace(int B, long long max_len, int N) {
+  if (B < 1 || B > 65535 || max_len < 1 || max_len > (1LL << 30) || N < 1 || N > sdr_max_order()) return -1;
+  return 8LL * sdr_products_workspace_doubles(B, max_len, N);
+}
+
+int buddy_sdr_products(const float* e, const float* x, const int* lens, int B, long long ld, int N, double* r, double* d, double* ee, void* ws, long long ws_bytes,
+                       void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_sdr_products: ") + why); return BUDDY_ERR_ARG; };
+  if (!e || !x || !lens || !r || !d || !ee || !ws) return bad("null pointer");
+  if (N < 1 || N > sdr_max_order()) return bad("N must be in 1..2048");
+  int longest;
+  if (int rc = check_rows(lens, B, ld, 1, stream, "buddy_sdr_products", &longest)) return rc;
+  if (ws_bytes < buddy_sdr_products_workspace(B, longest, N)) return bad("the workspace is smaller than buddy_sdr_products_workspace(B, longest row, N)");
+  launch_sdr_products(e, x, lens, B, ld, longest, N, r, d, ee, (double*)ws, (hipStream_t)stream);
+  return finish();
+}
+
+int buddy_sdr_solve(const double* r, const double* d, const double* ee, const int* lens, int B, int N, const int* orders, int J, double loading, double* sdr,
+                    double* p, int* flags, double* h, void* stream) {
+  auto bad = [](const char* why) { set_error(std::string("buddy_sdr_solve: ") + why); return BUDDY_ERR_ARG; };
+  if (!r || !d || !ee || !lens || !orders || !sdr || !p || !flags) return bad("null pointer");
+  if (N < 1 || N > sdr_max_order()) return bad("N must be in 1..2048");
+  if (J < 1 || J > sdr_max_orders()) return bad("J must be in 1..8");
+  for (int j = 0; j < J; ++j)
+    if (orders[j] < 1 || orders[j] > N || (j && orders[j] <= orders[j - 1])) return bad("the orders must be strictly ascending within 1..N");
+  if (!(loading >= 0.0) || !std::isfinite(loading)) return bad("the loading must be finite and >= 0");
+  int longest;
+  if (int rc = check_rows(lens, B, 1LL << 30, 1, stream, "buddy_sdr_solve", &longest)) return rc;
+  if (launch_sdr_solve(r, d, ee, lens, B, N, orders, J, loading, sdr, p, flags, h, (hipStream_t)stream)) {
+    set_error("buddy_sdr_solve: LDS request refused"); return BUDDY_ERR_HIP;
+  }
+  return finish();
+}
+
 // ---- non-intrusive SRMR of single signals (srmr.hip) ----
 int buddy_srmr_tile(void) { return srmr_tile(); }
 int buddy_modulation_chunk(void) { return modulation_chunk(); }

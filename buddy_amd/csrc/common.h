@@ -222,6 +222,17 @@ void launch_xcorr_lag(const float* e, const float* x, const int* lens, int B, lo
                       double* ws, hipStream_t st);
 void launch_align_pair(const float* e, const float* x, const int* lens, const int* lag, int B, long long ld, float* eo, float* xo, long long ldo, int* lens_out,
                        hipStream_t st);
+// projection SDR of a pair over filter lengths (sdr.hip): ragged rows, device length arrays; arguments, lengths, strides, orders
+// and the workspace are checked by the C entries, which pass the longest row (max_len) for the grids.  orders: a host array of J ascending orders
+int sdr_tile();                              // samples per chunk of the lag-product kernel
+int sdr_lag_tile();                          // lags per tile of the lag-product kernel
+int sdr_max_order();                         // the largest N
+int sdr_max_orders();                        // the largest J
+long long sdr_products_workspace_doubles(int B, long long max_len, int N);
+void launch_sdr_products(const float* e, const float* x, const int* lens, int B, long long ld, int max_len, int N, double* r, double* d, double* ee, double* ws,
+                         hipStream_t st);
+int launch_sdr_solve(const double* r, const double* d, const double* ee, const int* lens, int B, int N, const int* orders, int J, double loading, double* sdr,
+                     double* p, int* flags, double* h, hipStream_t st);   // non-zero: the LDS request was refused
 // non-intrusive SRMR of single signals (srmr.hip): ragged rows, device length arrays; arguments, lengths and strides are checked by the C entries, which
 // pass the longest row (max_len) for the grid.  tap_off, coef, erb and l are host arrays
 int srmr_tile();                             // outputs per workgroup of the envelope kernel

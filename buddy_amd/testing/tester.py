@@ -123,6 +123,16 @@ def spectral_options(tester_cfg):
     return _values_options(tester_cfg, "spectral", VALUES)
 
 
+def sdr_options(tester_cfg):
+    """(use, taps) of the ``sdr`` block of a tester config; a config written before the block existed means (False, the four default filter lengths)"""
+    from ..utils.sdr import TAPS
+    sd = tester_cfg.get("sdr", None)
+    if sd is None:
+        return False, TAPS
+    t = sd.get("taps", None)
+    return bool(sd.get("use", False)), TAPS if t is None else tuple(int(m) for m in t)
+
+
 class Tester:
     def __init__(self, args, network, diff_params, test_set=None, device=None, in_training=False, batch_size=1, rank=0, world_size=1):
         self.args = args
@@ -241,8 +251,9 @@ class Tester:
         report = blind and rir_report_options(self.args.tester)[0] and not self.in_training and bool(self.paths)
         rep = []         # room-acoustics report: (name, estimated RIR, true RIR, the operator's parameters of that row) per written RIR wav
         scoring = metrics_options(self.args.tester)[0] and not self.in_training and bool(self.paths)
-        scored = []      # evaluation and spectral reports: (name, clean, degraded, reconstructed) per written utterance, as written to the wavs
+        scored = []      # evaluation, spectral and SDR reports: (name, clean, degraded, reconstructed) per written utterance, as written to the wavs
         spectral_on = spectral_options(self.args.tester)[0] and not self.in_training and bool(self.paths)
+        sdr_on = sdr_options(self.args.tester)[0] and not self.in_training and bool(self.paths)
         decay_on = decay_options(self.args.tester) and not self.in_training and bool(self.paths)
         srmr_on = srmr_options(self.args.tester) and not self.in_training and bool(self.paths)
         heard = []     # SRMR and decay-time reports: (name, degraded, reconstructed, clean) per written utterance, each row with the rate of its wav
@@ -280,7 +291,7 @@ class Tester:
                         write_audio_file(est[b] if est.dim() == 2 else est, sr, name, path=self.paths[mode + "estimated_rir"])
                     if report:
                         rep.append((name, est[b] if est.dim() == 2 else est, rirs[b], {k: v if k == "freqs" else v[b] for k, v in par.items()}))
-                    if scoring or spectral_on:
+                    if scoring or spectral_on or sdr_on:
                         scored.append((name, seg[b].detach(), y[b].detach(), pred[b].detach()))
                     if srmr_on or decay_on:
                         heard.append((name, (y[b].detach(), sr), (pred[b].detach(), sr), (seg[b].detach(), sr)))
@@ -291,6 +302,8 @@ class Tester:
             self._write_metrics_report(mode, scored, sr)
         if spectral_on:
             self._write_spectral_report(mode, scored, sr)
+        if sdr_on:
+            self._write_sdr_report(mode, scored, sr)
         if srmr_on:
             self._write_srmr_report(mode, heard)
         if decay_on:
@@ -345,7 +358,7 @@ class Tester:
         self.metrics_report = self._write_pair_report(mode, scored, sr, metrics, "metrics", metrics_options(self.args.tester)[1])
 
     def _write_pair_report(self, mode, scored, sr, module, stem, values):
-        """the body of the two paired reports: ``module`` (utils/metrics.py or utils/spectral.py) scores the degraded and the reconstructed rows of
+        """the body of the paired reports: ``module`` (utils/metrics.py, utils/spectral.py or utils/sdr.py) scores the degraded and the reconstructed rows of
         ``scored`` against the clean ones, equal lengths as one batch, after ``tester.metrics.align`` where it is in use, and writes ``<stem>.csv`` and
         ``<stem>_summary.csv`` into the mode's directory -> the rows, or None where nothing was scored"""
         if not scored:
@@ -376,6 +389,15 @@ class Tester:
         multi-rank run as a whole."""
         from ..utils import spectral
         self.spectral_report = self._write_pair_report(mode, scored, sr, spectral, "spectral", spectral_options(self.args.tester)[1])
+
+    def _write_sdr_report(self, mode, scored, sr):
+        """Projection SDR report of a paired mode (``tester.sdr.use``; utils/sdr.py), once per mode after sampling: ``sdr.csv`` (per
+        written utterance the BSS-Eval SDR of the degraded and of the reconstructed signal against the clean one at every filter length of
+        ``tester.sdr.taps``, and the difference) and ``sdr_summary.csv`` (n, mean, median, std per column) in the mode's directory.  ``scored`` as in
+        ``_write_metrics_report``, and ``tester.metrics.align`` is honoured in the same way.  Every rank writes its own rows (``sdr.rank<r>.csv`` when
+        there are several); nothing is gathered -- ``tools/sdr.py`` scores the directory of a multi-rank run as a whole."""
+        from ..utils import sdr
+        self.sdr_report = self._write_pair_report(mode, scored, sr, sdr, "sdr", sdr_options(self.args.tester)[1])
 
     def _write_srmr_report(self, mode, items):
         """SRMR report of a mode (``tester.srmr.use``; utils/srmr.py), once per mode after sampling: ``srmr.csv`` (per written

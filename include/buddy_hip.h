@@ -730,6 +730,38 @@ int buddy_xcorr_lag(const float* e, const float* x, const int* lens, int B, long
 int buddy_align_pair(const float* e, const float* x, const int* lens, const int* lag, int B, long long ld, float* eo, float* xo, long long ldo, int* lens_out,
                      void* stream);
 
+/* ---- projection SDR of a pair over filter lengths (buddy_amd/utils/sdr.py; no reference counterpart): the BSS-Eval SDR of one
+ * source (Vincent et al. 2006) -- the estimate e projected onto the clean signal x and its delayed copies 0..m - 1 -- at up to 8 filter lengths m from
+ * one Levinson recursion.  The conventions of the evaluation entries above hold: ragged rows inside a common stride, DEVICE length arrays copied to the
+ * host once to be checked, nothing behind lens[b] - 1 read, nothing outside the declared extents written, fixed-order sums without atomics, a row's
+ * result independent of its batch.  BUDDY_ERR_ARG, with nothing launched, for: a null pointer (h may be NULL); B outside 1..65535; a length outside
+ * 1..2^30; a stride smaller than the longest row it holds; N outside 1..2048; J outside 1..8 or orders not strictly ascending within 1..N; a loading
+ * that is negative or not finite; a workspace below the size stated.
+ *
+ * buddy_sdr_products: for row b with n = lens[b], k = 0..N - 1: r[b][k] = sum_{t = 0}^{n - 1 - k} x[t] x[t + k], d[b][k] = sum_{t = 0}^{n - 1 - k} e[t + k] x[t]
+ *   (zero where there is no term: n < N is allowed), ee[b] = sum_t e[t]^2.  No means are removed.  r, d: (B, N) doubles, ee: (B) doubles.  Every product
+ *   and sum in double on the exact fp32 inputs: a direct correlation, no FFT, so |r[k] - exact| <= about (n + 4) 2^-53 sum_t |x[t]| |x[t + k]|, and the
+ *   same for d and ee with their own factors.  ws: buddy_sdr_products_workspace(B, longest row, N) bytes (-1 for arguments out of range).  Work:
+ *   2 n N multiply-adds per row.  buddy_sdr_tile: samples per chunk, buddy_sdr_lag_tile: lags per tile of the kernel (the sizes around which the unit
+ *   tests place their rows and orders).
+ *
+ * buddy_sdr_solve: r, d (B, N) and ee (B) DEVICE doubles as above, lens (B) DEVICE ints (only n >= 2 is taken from them), orders: J HOST ints, strictly
+ *   ascending within 1..N.  R_m = the m x m symmetric Toeplitz matrix of r with r[0] replaced by r[0] (1 + loading); h_m = R_m^-1 d[0..m - 1] by the
+ *   symmetric Levinson recursion from f = (1 / R[0][0]), h = (d[0] / R[0][0]): at step n = 1..N - 1, eps_f = sum_{i < n} r[n - i] f[i],
+ *   eps_x = sum_{i < n} r[n - i] h[i], f <- (f (+) 0 - eps_f rev(f (+) 0)) / (1 - eps_f^2), h <- h (+) 0 + (d[n] - eps_x) rev(f).  For each order m asked:
+ *   p[b][j] = p_m = sum_{i < m} h_m[i] d[i], the energy of the projection, and sdr[b][j] = 10 log10(p_m / max(ee - p_m, 1e-12 ee)).  sdr, p: (B, J) doubles.
+ *   flags[b]: bit 0 = defined (n >= 2, r[0] > 0, ee > 0, both finite, every pivot 1 - eps_f^2 > 0, every p_m > 0; else every sdr and p of the row is NaN
+ *   and h is zeros); bit 1 = ee - p_m < 4 loading ee at some order asked (the ceiling the loading sets: e = x reads about -10 log10(loading) dB);
+ *   bit 2 = a pivot fell below 2^-26 (h is ill-determined; the values are reported all the same).  h: (B, N) doubles, the filter of order N, or NULL.
+ *   One workgroup per row and N dependent steps: latency-bound by construction. */
+int buddy_sdr_tile(void);
+int buddy_sdr_lag_tile(void);
+long long buddy_sdr_products_workspace(int B, long long max_len, int N);
+int buddy_sdr_products(const float* e, const float* x, const int* lens, int B, long long ld, int N, double* r, double* d, double* ee, void* ws, long long ws_bytes,
+                       void* stream);
+int buddy_sdr_solve(const double* r, const double* d, const double* ee, const int* lens, int B, int N, const int* orders, int J, double loading, double* sdr,
+                    double* p, int* flags, double* h, void* stream);
+
 /* ---- non-intrusive score of single signals (buddy_amd/utils/srmr.py): the speech-to-reverberation modulation energy ratio.
  * The conventions of the evaluation entries above hold: ragged rows inside a common stride, DEVICE length arrays copied to the host once to be checked,
  * nothing behind lens[b] read, nothing outside the declared extents written, fixed-order sums without atomics, a row's result independent of its batch.

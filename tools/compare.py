@@ -2,7 +2,7 @@
 """Compare two runs over the same files (buddy_amd/utils/compare.py): per score column of their reports the mean and median
 paired difference (run B minus run A) with percentile bootstrap intervals, a sign-flip randomisation test, the sign test and Holm-adjusted p-values.
 
-    python tools/compare.py RUN_A RUN_B                      # every report both runs hold: metrics, spectral, srmr, decay, denoise, levels
+    python tools/compare.py RUN_A RUN_B                      # every report both runs hold: metrics, spectral, sdr, srmr, decay, denoise, levels
     python tools/compare.py RUN_A RUN_B --report metrics --columns si_sdr_out stoi_out
     python tools/compare.py a/metrics.csv b/metrics.csv      # two CSV files of one report
     python tools/compare.py RUN                              # one run: its own *_delta columns against zero (does the method improve on its input?)
@@ -18,7 +18,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from buddy_amd.utils import compare  # noqa: E402
 
-REPORTS = ("metrics", "spectral", "srmr", "decay", "denoise", "levels")
+REPORTS = ("metrics", "spectral", "sdr", "srmr", "decay", "denoise", "levels")
 
 
 def report_paths(run_a, run_b, asked):
